@@ -17,6 +17,15 @@ independent instance (different seed) — proofs are independent units, so there
 row-sharded over the ranks, with one RCCL all-gather of the 32-byte commitments per commit (SURVEY.md §8e, K1);
 "scaling": "strong", `value` = one proof's constraints / time. Each sharded proof is checked against the unsharded bytes.
 
+A plain run (no --full) does only what the headline needs: set up, warm up, time --steps proofs, and print the line
+(metric, value, unit, ms_per_step, the proof's digest). --full adds everything else measured beside it: the untimed
+fully-instrumented step and the roofline (with the ALU and gather ceilings from bench/ubench_fpmul and bench/gather_probe),
+the resident-assignment variant, the concurrent-proofs throughput, NIZK::prove / SNARK::encode, the CPU baselines and, with
+N > 1, the strong-scaling leg.
+
+--dump-outputs DIR writes the proof of the last timed step as DIR/proof.npy (its bytes, one float64 per byte; other ranks:
+proof_rank<r>.npy). Instance and tape are seeded, so the same arguments give the same proof on every run.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse, ctypes, json, os, sys, time
@@ -297,6 +306,14 @@ def side_metrics(P, ctx, inst, gens, N, s, tape_seed, steps):
     return out
 
 
+def dump_outputs(outdir, proof, rank):
+    """the proof of the last timed step, as its caller receives it (bincode bytes), one float64 per byte (exact; 181 KB at 2^20 -> 1.4 MB)"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    name = "proof.npy" if rank == 0 else "proof_rank%d.npy" % rank
+    np.save(os.path.join(outdir, name), np.frombuffer(proof, dtype=np.uint8).astype(np.float64))
+
+
 def enable_sharding(P, ctx, dist, rank, world):
     """row-shard every commitment of `ctx` over the ranks: RCCL inside the library when the job runs on the nccl backend
     (rank 0 draws the ncclUniqueId, one broadcast hands it to everyone), the torch.distributed byte gather otherwise (gloo tests)"""
@@ -383,7 +400,12 @@ def main():
     ap.add_argument("--plumbing-only", action="store_true", help="TEST HOOK (tests/test_bench_dist.py): launch, rendezvous, rank count and aggregation only; no GPU, no proof, value null")
     ap.add_argument("--no-strong", action="store_true", help="N>1: skip the strong-scaling leg (one sharded proof) that follows the replica measurement")
     ap.add_argument("--phases", action="store_true", help="also print the per-phase span times (timer.rs names) to stderr")
+    ap.add_argument("--full", action="store_true", help="also run everything measured beside the headline: profiling step, roofline and ceilings, resident "
+                    "assignment, concurrent proofs, side metrics, CPU baselines, strong-scaling leg (the --no-* / --concurrent switches apply within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the proof of the last timed step to DIR/proof.npy (bytes as float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world, dist = dist_setup(args.gpus)
     if args.plumbing_only:
@@ -426,8 +448,9 @@ def main():
     tape_seed = P.seed_scalar(b"tape", args.tape_offset + seed)
 
     # the headline step takes the assignment as a host buffer, as a Rust caller's `&[Scalar]` would arrive (the H2D
-    # of `vars` is inside the metric); the VarsAssignment-resident variant is timed separately below (`resident_assignment`)
-    assignment = P.VarsAssignment(ctx, inst.vars)
+    # of `vars` is inside the metric); the VarsAssignment-resident variant is timed separately below (`resident_assignment`, --full)
+    full = args.full
+    assignment = P.VarsAssignment(ctx, inst.vars) if full else None
 
     def step(times=None, resident=False):
         return P.SNARK.prove(ctx, inst, enc, assignment if resident else inst.vars, inst.inputs, gens, b"snark_example", tape_seed, times)
@@ -456,9 +479,9 @@ def main():
 
     proof = None
     raw = ctx.raw()
-    ceil = measured_ceilings() if rank == 0 else None
+    ceil = measured_ceilings() if rank == 0 and full else None
     gath = None
-    if rank == 0 and not os.environ.get("BENCH_NO_GATHER_PROBE"):
+    if rank == 0 and full and not os.environ.get("BENCH_NO_GATHER_PROBE"):
         wb = [gens.window_bits(0), gens.window_bits(1)]
         # entries per (point, window) sub-table = 2^(c-1); the stride of a table entry follows from the table's size
         ent = [(len(gens.stream(k)) // 32) * (-(-254 // wb[k])) * (1 << (wb[k] - 1)) for k in (0, 1)]
@@ -480,21 +503,23 @@ def main():
         proof = p2
     # Untimed profiling step: HIP events on every kernel family -> per-family breakdown and the dominant kernel.
     # (Each recorded launch costs two hipEventRecord calls; with ~1500 launches per proof that is ~10% of a step,
-    # so the timed region below instruments the dominant family only.)
-    capi.lib.sp_prof_reset(raw); capi.lib.sp_prof_select(raw, None); capi.lib.sp_prof_enable(raw, ctypes.c_int(1))
-    proof = step()
-    capi.lib.sp_prof_enable(raw, ctypes.c_int(0))
-    breakdown = read_prof()
-    fq_big = {}   # throughput-sized launches (>= 64 MB of algorithmic bytes) of the F_q families, from the same instrumented step
-    for name in breakdown:
-        if name != "msm_rows_fixed":
-            for e_ in read_shapes(name):
-                if e_["rows"] == 0x40000000 and e_["cols"] == 1:   # the pseudo-shape 0x4000000000000001 (include/spartan_hip.h)
-                    fq_big[name] = e_
-    dom = max(breakdown, key=lambda n: breakdown[n]["ms"])
-    capi.lib.sp_prof_reset(raw)
-    if not os.environ.get("BENCH_NO_PROF"):
-        capi.lib.sp_prof_select(raw, dom.encode()); capi.lib.sp_prof_enable(raw, ctypes.c_int(1))
+    # so the timed region below instruments the dominant family only.) --full only: a plain run times uninstrumented steps.
+    breakdown, fq_big, dom = {}, {}, None
+    if full:
+        capi.lib.sp_prof_reset(raw); capi.lib.sp_prof_select(raw, None); capi.lib.sp_prof_enable(raw, ctypes.c_int(1))
+        proof = step()
+        capi.lib.sp_prof_enable(raw, ctypes.c_int(0))
+        breakdown = read_prof()
+        # fq_big: throughput-sized launches (>= 64 MB of algorithmic bytes) of the F_q families, from the same instrumented step
+        for name in breakdown:
+            if name != "msm_rows_fixed":
+                for e_ in read_shapes(name):
+                    if e_["rows"] == 0x40000000 and e_["cols"] == 1:   # the pseudo-shape 0x4000000000000001 (include/spartan_hip.h)
+                        fq_big[name] = e_
+        dom = max(breakdown, key=lambda n: breakdown[n]["ms"])
+        capi.lib.sp_prof_reset(raw)
+        if not os.environ.get("BENCH_NO_PROF"):
+            capi.lib.sp_prof_select(raw, dom.encode()); capi.lib.sp_prof_enable(raw, ctypes.c_int(1))
     if sharded:
         ctx.shard_stats(reset=True)
     dist_barrier(dist)
@@ -510,26 +535,29 @@ def main():
     dist_barrier(dist)
     dt = time.perf_counter() - t0
     dt = dist_max(dist, dt, dev if dist is not None and dist.get_backend() == "nccl" else "cpu")
-    capi.lib.sp_prof_enable(raw, ctypes.c_int(0))
-    # the same proof from an assignment already uploaded by VarsAssignment::new (no PCIe copy of `vars` inside the call): reported, never `value`
-    k_host = min(args.steps, 10)
     shard_stats_timed = ctx.shard_stats() if sharded else None
-    torch.cuda.synchronize()
-    trips0 = capi.lib.sp_ctx_trips(raw)
-    t0h = time.perf_counter()
-    for _ in range(k_host):
-        if step(resident=True) != proof:
-            raise SystemExit("resident-assignment proof differs from the host-buffer proof")
-    dt_host = (time.perf_counter() - t0h) / k_host
-    fs_trips = (capi.lib.sp_ctx_trips(raw) - trips0) / k_host
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof, rank)
+    if full:
+        capi.lib.sp_prof_enable(raw, ctypes.c_int(0))
+        # the same proof from an assignment already uploaded by VarsAssignment::new (no PCIe copy of `vars` inside the call): reported, never `value`
+        k_host = min(args.steps, 10)
+        torch.cuda.synchronize()
+        trips0 = capi.lib.sp_ctx_trips(raw)
+        t0h = time.perf_counter()
+        for _ in range(k_host):
+            if step(resident=True) != proof:
+                raise SystemExit("resident-assignment proof differs from the host-buffer proof")
+        dt_host = (time.perf_counter() - t0h) / k_host
+        fs_trips = (capi.lib.sp_ctx_trips(raw) - trips0) / k_host
     n_ranks_seen = int(round(dist_sum(dist, 1.0, dev if dist is not None and dist.get_backend() == "nccl" else "cpu")))
     if n_ranks_seen != args.gpus:
         raise SystemExit("bench.py: %d ranks answered the all-reduce, --gpus %d: no line is printed for a job of another size" % (n_ranks_seen, args.gpus))
-    strong = None
-    fam = read_prof() or {dom: breakdown[dom]}
-    shapes = read_shapes(dom) if dom == "msm_rows_fixed" else []
-    spans = read_spans(dom) if dom == "msm_rows_fixed" else []
-    capi.lib.sp_prof_select(raw, None)
+    if full:
+        fam = read_prof() or {dom: breakdown[dom]}
+        shapes = read_shapes(dom) if dom == "msm_rows_fixed" else []
+        spans = read_spans(dom) if dom == "msm_rows_fixed" else []
+        capi.lib.sp_prof_select(raw, None)
 
     # dominant kernel (HIP events recorded inside the timed region) -> roofline
     roofline = None
@@ -650,7 +678,6 @@ def main():
                                   "note": "each family split into its throughput-sized launches (>= 64 MB of algorithmic bytes: the first rounds of the large layers) and the launch-sized rest (most of a proof's ~400 rounds run on tables that halve every round: latency-bound, their GB/s says nothing); per kernel and launch size with PMC bytes: profiles/r6_fq_bandwidth_2p20.txt / _2p22.txt"}
 
     if rank == 0:
-        gpu_ms_total = sum(v["ms"] for v in breakdown.values())
         value = (1 if sharded else world) * N * args.steps / dt
         out = {
             "metric": "R1CS constraints/sec in SNARK::prove (synthetic 2^%d); bit-exact proof" % s,
@@ -669,22 +696,25 @@ def main():
                        "proof_bytes": len(proof), "proof_sha256": __import__("hashlib").sha256(proof).hexdigest(),
                        "parallelism": ("1 proof, row commitments sharded over %d GPUs + all-gather" % world) if sharded else ("1 proof per GPU, %d independent proofs (replicas: no data-path collective)" % world),
                        "inputs": "instance, generators and computation commitment resident in HBM; the satisfying assignment `vars` is a host buffer uploaded inside the timed SNARK::prove (SURVEY 8d); inputs io on the host",
-                       "resident_assignment": {"ms_per_step": round(dt_host * 1e3, 3), "value": N * world / dt_host if not sharded else N / dt_host, "steps": k_host,
-                                               "note": "same proof from a VarsAssignment already in HBM (uploaded once by its constructor, outside prove): reported beside the headline, never as `value`"},
                        "bit_exact_against": "the in-repo oracle (oracle/: CPU restatement of the reference prover, pinned to RFC 9496 / Merlin / reference F_q vectors; no libspartan run exists here)",
-                       "fs_trips_per_proof": fs_trips,
                        "table_GB": {"gens_r1cs_sat": round(gens.table_bytes(0) / 1e9, 2), "gens_r1cs_eval": round(gens.table_bytes(1) / 1e9, 2),
                                     "window_bits": [gens.window_bits(0), gens.window_bits(1)], "windows": [gens.windows(0), gens.windows(1)]},
                        "host_cores_busy": world, "host_note": "each proving thread spins on its completion flag and runs Merlin, the 2..5-term Sigma-protocol commitments, ~150 point encodes (in pairs), the challenge inversions and the end of every inner-product argument: one host core per GPU, flat out; a helper thread computes the tape-only halves of the ZK sum-checks' commitments ahead of the rounds (~0.5 ms of a second core per proof), another issues the witness upload",
                        "host_keccak": P.keccak_variant()},
-            "roofline": roofline,
-            "kernel_ms_per_step": {n: round(v["ms"], 4) for n, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms"])},
-            "gpu_busy_ms_per_step": round(gpu_ms_total, 3),
-            "kernel_ms_note": "per-family totals from one untimed fully-instrumented step; roofline from the timed steps. Families OVERLAP (the background row-MSM runs under the sum-checks and openings, sparse evaluations on a low-priority stream): the sum exceeds ms_per_step, and event times of kernels that share the chip include what they wait",
             "phases_ms": {k_: round(v * 1e3, 3) for k_, v in phase.items()},
             "us_per_scalar": {"polycommit": round(phase.get("polycommit", 0) / N * 1e6, 5), "commit_nondet_witness": round(phase.get("commit_nondet_witness", 0) / (8 * N) * 1e6, 5),
                               "readme_i7_1065G7_one_core": README_US_PER_SCALAR, "note": "wall time of the phase / committed scalars (2^s and 8 * 2^s, zero padding included as in the README)"},
         }
+        if full:
+            out["config"]["resident_assignment"] = {"ms_per_step": round(dt_host * 1e3, 3), "value": N * world / dt_host if not sharded else N / dt_host, "steps": k_host,
+                                                    "note": "same proof from a VarsAssignment already in HBM (uploaded once by its constructor, outside prove): reported beside the headline, never as `value`"}
+            out["config"]["fs_trips_per_proof"] = fs_trips
+            out["roofline"] = roofline
+            out["kernel_ms_per_step"] = {n: round(v["ms"], 4) for n, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms"])}
+            out["gpu_busy_ms_per_step"] = round(sum(v["ms"] for v in breakdown.values()), 3)
+            out["kernel_ms_note"] = ("per-family totals from one untimed fully-instrumented step; roofline from the timed steps. Families OVERLAP (the background row-MSM runs "
+                                     "under the sum-checks and openings, sparse evaluations on a low-priority stream): the sum exceeds ms_per_step, and event times of kernels "
+                                     "that share the chip include what they wait")
         if s in (16, 20, 22) and not sharded and world == 1:   # the committed oracle digest of this very proof (tests/golden/make_golden.py --big)
             try:
                 g_ = json.load(open(os.path.join(ROOT, "tests", "golden", "proof_digests.json")))["big"]["snark"].get(f"s{s}_seed0")
@@ -698,11 +728,11 @@ def main():
             out["config"]["all_gather_bytes_per_proof"] = st_["bytes"] / args.steps
             out["config"]["shard_transport"] = shard_transport
         out["n_ranks_seen"] = n_ranks_seen
-        if args.concurrent > 1 and world == 1:
+        if full and args.concurrent > 1 and world == 1:
             out["throughput_concurrent"] = concurrent_throughput(P, local_rank, s, args.concurrent, max(2, args.steps))
-        if world == 1 and not args.no_side_metrics:
+        if full and world == 1 and not args.no_side_metrics:
             out.update(side_metrics(P, ctx, inst, gens, N, s, tape_seed, max(2, args.steps)))
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             # (1) the oracle at the METRIC'S OWN SIZE on this box, all cores (bounded: ~20-40 s on the GPU box's host): its proof is compared with
             # the GPU proof timed above — a live check, next to the committed digest
             nthr = min(os.cpu_count() or 1, args.cpu_threads)
@@ -725,8 +755,10 @@ def main():
             print("phases (s):", json.dumps({k_: round(v, 5) for k_, v in phase.items()}), file=sys.stderr)
     else:
         out = None
-    assignment.free(); enc.free(); gens.free(); inst.free()   # the strong leg builds its own sets (up to 2^24: 177 GB of window tables) in the room this leaves
-    if dist is not None and not sharded and not args.no_strong:
+    if assignment is not None:
+        assignment.free()
+    enc.free(); gens.free(); inst.free()   # the strong leg builds its own sets (up to 2^24: 177 GB of window tables) in the room this leaves
+    if full and dist is not None and not sharded and not args.no_strong:
         # The same command also reports ONE proof's latency over all ranks (strong scaling), at every size of --strong-log2 (default
         # 2^20, 2^22, 2^24: BASELINE configs 4 and 5 and the size where most of a proof is throughput-bound). It runs after everything
         # above is measured; a watchdog guarantees the job ends (and rank 0 still prints the replica line with the sizes finished so

@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 export BENCH_NO_GATHER_PROBE=1
 R=$(pwd); O=$R/gpurun_out/p22r4; mkdir -p $O
-B="python $R/bench.py --log2-cons 22 --no-cpu-baseline --concurrent 0 --steps 2 --warmup 1 --no-side-metrics --no-strong"
+B="python $R/bench.py --full --log2-cons 22 --no-cpu-baseline --concurrent 0 --steps 2 --warmup 1 --no-side-metrics --no-strong"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/stats -- $B > $O/stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=$(pwd)
 O=$R/gpurun_out/r3prof
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
+B="python $R/bench.py --full --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/stats -- $B > $O/stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -17,7 +17,7 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_I
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d $O/pmc_tcc -- $B > $O/pmc_tcc.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INST_CYCLES_VMEM --output-format csv -d $O/pmc_wait -- $B > $O/pmc_wait.log 2>&1
 cd $R
-python bench.py > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 # keep what travels back small: the counter CSVs and the stats database summary
 # (bench.py also runs bench/ubench_fpmul as a child process: every pass leaves one small file for it — take the largest)
 largest() { find "$1" -name "$2" -printf "%s %p\n" | sort -n | tail -1 | cut -d" " -f2; }

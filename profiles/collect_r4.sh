@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 R=$(pwd)
 O=$R/gpurun_out/r4prof
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
+B="python $R/bench.py --full --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
 export BENCH_NO_GATHER_PROBE=1   # the profiled command is the prover alone (the gather probe is a separate process with its own 80 GB buffer)
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/stats -- $B > $O/stats.log 2>&1
@@ -28,14 +28,14 @@ python profiles/pmc_summarize.py $O/pmc_FETCH_SIZE.csv $O/pmc_WRITE_SIZE.csv r4_
 python profiles/pmc_counters.py $O/pmc_sq.csv $O/pmc_tcc.csv $O/pmc_wait.csv > $O/pmc_kernels.txt 2>&1
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
 # the headline line (with the traffic of the file just written), then the in-kernel stamps, then the other sizes
-python bench.py > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 SPARTAN_KTIME=1 timeout 300 python bench/ktime_probe.py > $O/ktime_probe.txt 2>&1
 # the same stamps with the round 1-3 tree (A, B, C, D through LDS, three barriers per level): make variant NAME=ktime_treelds FLAGS="-DSP_KTIME -DSP_TREE_LDS"
 [ -f spartan_amd/lib/libspartan_hip_ktime_treelds.so ] && SPARTAN_HIP_LIB=$R/spartan_amd/lib/libspartan_hip_ktime_treelds.so SPARTAN_KTIME=1 timeout 300 python bench/ktime_probe.py > $O/ktime_probe_lds_tree.txt 2>&1
 # background share of the CUs under the round-4 kernels (line-aligned entries)
 bash scripts/gpu_ab.sh r4prof 2 "bg4:SPARTAN_BG_EIGHTHS=4" "bg5:" "bg6:SPARTAN_BG_EIGHTHS=6" "treelds:LD_PRELOAD=$R/spartan_amd/lib/libspartan_hip_treelds.so,SPARTAN_HIP_LIB=$R/spartan_amd/lib/libspartan_hip_treelds.so" "packed96:LD_PRELOAD=$R/spartan_amd/lib/libspartan_hip_packed96.so,SPARTAN_HIP_LIB=$R/spartan_amd/lib/libspartan_hip_packed96.so" > $O/ab_final.txt 2>&1
-for s in 16 18; do python bench.py --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
-python bench.py --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
-python bench.py --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
+for s in 16 18; do python bench.py --full --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
+python bench.py --full --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
+python bench.py --full --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
 ./bench/ubench_fpmul > $O/ubench_fpmul.txt 2>&1
 ls -la $O

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=$(pwd)
 O=$R/gpurun_out/r4prof2
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
+B="python $R/bench.py --full --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
 export BENCH_NO_GATHER_PROBE=1
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/stats -- $B > $O/stats.log 2>&1
@@ -26,11 +26,11 @@ rm -rf $O/stats $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_sq $O/pmc_tcc $O/pmc_
 python profiles/pmc_summarize.py $O/pmc_FETCH_SIZE.csv $O/pmc_WRITE_SIZE.csv r4_pmc_hbm_traffic.txt > $O/pmc_hbm_traffic.txt 2>&1
 python profiles/pmc_counters.py $O/pmc_sq.csv $O/pmc_tcc.csv $O/pmc_wait.csv > $O/pmc_kernels.txt 2>&1
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
-python bench.py > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 SPARTAN_KTIME=1 timeout 300 python bench/ktime_probe.py > $O/ktime_probe.txt 2>&1
 SPARTAN_CALLSTATS=1 timeout 300 $B > /dev/null 2> $O/callstats.err; grep callstats $O/callstats.err | tail -52 > $O/callstats.txt
-for s in 16 18; do python bench.py --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
-python bench.py --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
-python bench.py --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
+for s in 16 18; do python bench.py --full --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
+python bench.py --full --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
+python bench.py --full --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
 ./bench/ubench_fpmul > $O/ubench_fpmul.txt 2>&1
 ls -la $O

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 R=$(pwd)
 O=$R/gpurun_out/r5prof
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
+B="python $R/bench.py --full --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
 export BENCH_NO_GATHER_PROBE=1
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/stats -- $B > $O/stats.log 2>&1
@@ -39,13 +39,13 @@ python profiles/pmc_summarize.py $O/pmc_FETCH_SIZE.csv $O/pmc_WRITE_SIZE.csv r5_
 python profiles/pmc_counters.py $O/pmc_sq.csv $O/pmc_tcc.csv $O/pmc_wait.csv > $O/pmc_kernels.txt 2>&1
 python profiles/pmc_counters.py $O/forms_pmc_wait.csv $O/forms_pmc_wait.csv $O/forms_pmc_wait.csv > $O/forms_pmc_kernels.txt 2>&1
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
-python bench.py > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 SPARTAN_OPTIONS=testing.unlock=1,host.callstats=1 timeout 300 $B > /dev/null 2> $O/callstats.err; grep callstats $O/callstats.err | tail -52 > $O/callstats.txt
-for s in 16 18; do python bench.py --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
-python bench.py --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
-python bench.py --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
+for s in 16 18; do python bench.py --full --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
+python bench.py --full --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
+python bench.py --full --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
 # the small-memory configuration (LDS-staged row MSM + 10-bit tables for the latency kernels: 15 GB instead of 118 GB at 2^20)
-SPARTAN_OPTIONS=msm.lds_bits=10,msm.form=1,msm.wbits=10 python bench.py --no-cpu-baseline --concurrent 0 --no-side-metrics > $O/bench_line_small_memory.json 2> $O/bench_line_small_memory.err
+SPARTAN_OPTIONS=msm.lds_bits=10,msm.form=1,msm.wbits=10 python bench.py --full --no-cpu-baseline --concurrent 0 --no-side-metrics > $O/bench_line_small_memory.json 2> $O/bench_line_small_memory.err
 ./bench/ubench_fpmul > $O/ubench_fpmul.txt 2>&1
 ls -la $O
 # A/B of the row-MSM forms in the proof at 2^22 (BASELINE config 5's size)

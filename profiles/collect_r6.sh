@@ -24,7 +24,7 @@ trace() { # trace NAME -- cmd...  -> $O/NAME.db
 DET=k_ipa_round,k_msm_reduce,k_msm_q,k_msm_flat,k_msm_rows,k_cubic_bind2_eval,k_cubic_bind_eval_batched_eq,k_cubic_eval_batched_eq,k_sc_bind_eval,k_sc_eval
 for s in 20 22; do
   steps=4; [ $s = 22 ] && steps=2
-  B="python $R/bench.py --log2-cons $s --no-cpu-baseline --concurrent 0 --steps $steps --warmup 1 --no-side-metrics --no-strong"
+  B="python $R/bench.py --full --log2-cons $s --no-cpu-baseline --concurrent 0 --steps $steps --warmup 1 --no-side-metrics --no-strong"
   trace stats$s -- $B
   python profiles/summarize.py $O/stats$s.db --detail $DET > $O/kernel_stats_2p$s.txt 2>$O/summarize$s.err
   pmc fetch$s FETCH_SIZE -- $B
@@ -37,12 +37,12 @@ for s in 20 22; do
 done
 # the small-memory configuration (LDS-staged row MSM + 10-bit tables for the latency kernels) at 2^20: its own traffic entry
 SM=msm.form=1,msm.lds_bits=10,msm.wbits=10
-B20="python $R/bench.py --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
+B20="python $R/bench.py --full --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong"
 SPARTAN_OPTIONS=$SM pmc fetch_sm FETCH_SIZE -- $B20
 SPARTAN_OPTIONS=$SM pmc write_sm WRITE_SIZE -- $B20
 python profiles/pmc_summarize.py $O/fetch_sm.csv $O/write_sm.csv r6_pmc_hbm_traffic_small_memory.txt 20 "$SM" > $O/pmc_hbm_traffic_small_memory.txt 2>&1
 # 2^24: kernel trace only
-trace stats24 -- python $R/bench.py --log2-cons 24 --no-cpu-baseline --concurrent 0 --steps 1 --warmup 1 --no-side-metrics --no-strong
+trace stats24 -- python $R/bench.py --full --log2-cons 24 --no-cpu-baseline --concurrent 0 --steps 1 --warmup 1 --no-side-metrics --no-strong
 python profiles/summarize.py $O/stats24.db --detail k_msm_q,k_msm_flat,k_msm_reduce > $O/kernel_stats_2p24.txt 2>>$O/summarize24.err
 # the queue form standalone under the wait / VALU counters (and the forms it replaced beside it)
 pmc probe_wait "SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU" -- python $R/bench/msm_queue_probe.py 22 12/2/32,8/2/32 h
@@ -52,12 +52,12 @@ timeout 900 python bench/msm_queue_probe.py 22 12/2/32,8/2/32 w,h > $O/queue_pro
 unset BENCH_NO_GATHER_PROBE
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
 # bench lines (they read the traffic entries written above)
-python bench.py > $O/bench_line.json 2> $O/bench_line.err
-SPARTAN_OPTIONS=testing.unlock=1,host.callstats=1 timeout 300 python bench.py --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong > /dev/null 2> $O/callstats.err; grep callstats $O/callstats.err | tail -56 > $O/callstats.txt
-for s in 16 18; do python bench.py --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
-python bench.py --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
-python bench.py --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics --no-strong > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
-SPARTAN_OPTIONS=$SM python bench.py --no-cpu-baseline --concurrent 0 > $O/bench_line_small_memory.json 2> $O/bench_line_small_memory.err
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
+SPARTAN_OPTIONS=testing.unlock=1,host.callstats=1 timeout 300 python bench.py --full --no-cpu-baseline --concurrent 0 --steps 4 --warmup 1 --no-side-metrics --no-strong > /dev/null 2> $O/callstats.err; grep callstats $O/callstats.err | tail -56 > $O/callstats.txt
+for s in 16 18; do python bench.py --full --log2-cons $s --cpu-log2-cons 0 --no-cpu-baseline > $O/bench_line_2p$s.json 2> $O/bench_line_2p$s.err; done
+python bench.py --full --log2-cons 22 --no-cpu-baseline --steps 8 > $O/bench_line_2p22.json 2> $O/bench_line_2p22.err
+python bench.py --full --log2-cons 24 --no-cpu-baseline --steps 3 --concurrent 0 --no-side-metrics --no-strong > $O/bench_line_2p24.json 2> $O/bench_line_2p24.err
+SPARTAN_OPTIONS=$SM python bench.py --full --no-cpu-baseline --concurrent 0 > $O/bench_line_small_memory.json 2> $O/bench_line_small_memory.err
 ./bench/ubench_fpmul > $O/ubench_fpmul.txt 2>&1
 rm -f $O/*.db $O/fetch*.csv $O/write*.csv $O/wait*.csv $O/tcc*.csv $O/probe_wait.csv
 ls -la $O

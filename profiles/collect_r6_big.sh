@@ -10,7 +10,7 @@ R=$(pwd); O=$R/gpurun_out/r6big_$TAG; mkdir -p $O
 largest() { find "$1" -name "$2" -printf "%s %p\n" | sort -n | tail -1 | cut -d" " -f2; }
 for s in 22 24; do
   steps=2; [ $s = 24 ] && steps=1
-  B="python $R/bench.py --log2-cons $s --no-cpu-baseline --concurrent 0 --steps $steps --warmup 1 --no-side-metrics --no-strong"
+  B="python $R/bench.py --full --log2-cons $s --no-cpu-baseline --concurrent 0 --steps $steps --warmup 1 --no-side-metrics --no-strong"
   cd /tmp
   rocprofv3 --kernel-trace --stats -d $O/stats$s -- $B > $O/stats$s.log 2>&1
   cd $R

@@ -4,7 +4,7 @@ set -u
 export TMPDIR=/tmp
 R=$(pwd); O=$R/gpurun_out/$1; shift
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --concurrent 0 --steps 8 --warmup 1 --no-side-metrics --no-strong"
+B="python $R/bench.py --full --no-cpu-baseline --concurrent 0 --steps 8 --warmup 1 --no-side-metrics --no-strong"
 cd /tmp
 env "$@" timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats -- $B > $O/stats.log 2>&1
 cd $R

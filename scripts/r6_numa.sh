@@ -17,7 +17,7 @@ PY
 )
 echo "one thread per core: $(echo $NODE | cut -c1-60)..."
 Q="--no-cpu-baseline --concurrent 0 --steps 30 --warmup 2 --no-side-metrics --no-strong"
-run() { local name=$1; shift; BENCH_NO_GATHER_PROBE=1 "$@" python bench.py $Q 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', round(d['ms_per_step'],3), 'resident', round(d['config']['resident_assignment']['ms_per_step'],3), 'spark', d['phases_ms']['evalproof_layered_network'])"; }
+run() { local name=$1; shift; BENCH_NO_GATHER_PROBE=1 "$@" python bench.py --full $Q 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', round(d['ms_per_step'],3), 'resident', round(d['config']['resident_assignment']['ms_per_step'],3), 'spark', d['phases_ms']['evalproof_layered_network'])"; }
 for rep in 1 2 3 4 5 6; do
   run "node (default)   " env
   run "one thread / core" taskset -c $NODE

@@ -18,7 +18,7 @@ def test_sharded_commit_proof_is_byte_identical(s):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    BENCH_DIST_BACKEND="gloo", BENCH_FORCE_DEVICE="0", BENCH_NO_PROF="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shard-commits", "--log2-cons", str(s),
-                                       "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--concurrent", "0"],
+                                       "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--concurrent", "0", "--full"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
@@ -43,7 +43,7 @@ def test_default_multi_rank_run_reports_replicas_and_strong_leg():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BENCH_DIST_BACKEND="gloo", BENCH_FORCE_DEVICE="0", BENCH_NO_PROF="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log2-cons", "14", "--steps", "2", "--warmup", "1",
-                        "--strong-log2", "12,14"], env=env, capture_output=True, text=True, timeout=900)
+                        "--strong-log2", "12,14", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                                                              # rank 0 alone prints
