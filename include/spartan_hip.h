@@ -294,6 +294,15 @@ int32_t sp_sparse_evaluate(sp_ctx* ctx, const sp_sparse* m, const sp_table* tx, 
  * order): SNARK::prove (src/lib.rs:393-400) starts R1CSInstance::evaluate as soon as ry is known and collects the three values after
  * the witness opening. tx and ty must outlive the job. */
 int32_t sp_sparse_evaluate_begin(sp_ctx* ctx, const sp_sparse* const* ms, size_t count, const sp_table* tx, const sp_table* ty, sp_job** out);
+/* R1CSShape::is_sat (r1cs.rs:240-266): (A z)[r] * (B z)[r] == (C z)[r] for every row r; z has >= num_cols elements.
+ * *violated = number of failing rows, *first_row = the smallest failing index (UINT64_MAX when none);
+ * rows_out (may be NULL) receives the min(*violated, rows_cap) lowest failing indices in ascending order.
+ * One fused pass over the CSR copies: no Az, Bz, Cz tables are written and nothing but the two words crosses PCIe (one round trip; with
+ * rows_cap > 0 and a failing row, a second one for a bitmap of num_rows bits). Entries with the same (row, col) add up, a row without
+ * entries is satisfied. Rows of more than 32 entries are summed by whole wavefronts from a list of such rows that the first check of a
+ * matrix builds from its row pointers and keeps in the sp_sparse. SP_EINVAL: a null handle, matrices of different shapes, z too short. */
+int32_t sp_r1cs_check(sp_ctx* ctx, const sp_sparse* A, const sp_sparse* B, const sp_sparse* C, const sp_table* z,
+                      uint64_t* violated, uint64_t* first_row, uint64_t* rows_out, size_t rows_cap);
 
 /* ---- inner-product argument: BulletReductionProof::prove (src/nizk/bullet.rs:32-132) -----------------
  * The folded generators G^(k) are never materialised: G^(k)[i] = sum_p s_k[p] * G[p*n_k + i] with

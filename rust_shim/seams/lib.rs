@@ -1,4 +1,4 @@
-// src/lib.rs — SNARK::prove (:339-420), NIZK::prove (:501-546) and VarsAssignment under `--features gpu`, plus the seeded twins the
+// src/lib.rs — SNARK::prove (:339-420), NIZK::prove (:501-546), VarsAssignment and the device form of Instance::is_sat under `--features gpu`, plus the seeded twins the
 // parity tests need (the only change there is the RandomTape constructor, :356 / :516). Production code keeps OS entropy.
 // C++ rendering: spartan_amd/host/spark.inc (SNARK::prove), prover.cc (NIZK::prove, VarsAssignment).
 //
@@ -16,6 +16,32 @@ impl VarsAssignment {
   /// SNARK::prove / NIZK::prove start from the device copy. `dev: Option<gpu::Table>` is the added field.
   #[cfg(feature = "gpu")]
   pub fn upload(&mut self) { self.dev = Some(gpu::Table::upload(&self.assignment)); }
+}
+
+impl Instance {
+  /// Instance::is_sat (:230-259) on the device, as an ADDITIVE method next to the reference's: the same length checks and zero padding, then
+  /// one sp_r1cs_check over the resident matrices. Returns (satisfied, number of violated constraints, the smallest violated constraint).
+  /// C++ rendering: spartan_amd/host/prover.cc, Instance::is_sat.
+  #[cfg(feature = "gpu")]
+  pub fn is_sat_gpu(&self, vars: &VarsAssignment, inputs: &InputsAssignment) -> Result<(bool, u64, Option<u64>), R1CSError> {
+    let num_vars = self.inst.get_num_vars();
+    if vars.assignment.len() > num_vars || inputs.assignment.len() != self.inst.get_num_inputs() {
+      return Err(R1CSError::InvalidNumberOfInputs);
+    }
+    // z = vars | 0... | 1 | inputs | 0... in a zero-filled table of 2 * num_vars, as R1CSProof::prove_gpu builds it
+    let c = gpu::ctx();
+    let z = gpu::Table::alloc_zeroed(2 * num_vars);
+    match &vars.dev {
+      Some(t) => gpu::ok(unsafe { gpu::sp_table_copy(c, z.0, 0, t.0, 0, t.len()) }),
+      None if !vars.assignment.is_empty() => gpu::ok(unsafe { gpu::sp_table_write(c, z.0, 0, gpu::limbs(&vars.assignment), vars.assignment.len()) }),
+      None => {}
+    }
+    let mut tail = vec![Scalar::one()];
+    tail.extend_from_slice(&inputs.assignment);
+    gpu::ok(unsafe { gpu::sp_table_write(c, z.0, num_vars, gpu::limbs(&tail), tail.len()) });
+    let (violated, first) = gpu::r1cs_check(self.inst.A.dev.as_ref().unwrap(), self.inst.B.dev.as_ref().unwrap(), self.inst.C.dev.as_ref().unwrap(), &z);
+    Ok((violated == 0, violated, if violated == 0 { None } else { Some(first) }))
+  }
 }
 
 impl SNARK {

@@ -15,6 +15,12 @@ struct sp_sparse {
   Fq* csc_val;
   uint32_t *ent_row, *ent_col;  // the entries in the order they were given (SparseMatPolynomial.M, sparse_mlpoly.rs:19-38): SNARK::encode's
   Fq* ent_val;                  // address lists and value vectors are these, zero-padded (sparse_mlpoly.rs:367-427) — no host pass over them
+  // sp_r1cs_check's plan for the long rows of this matrix, built from row_ptr on the first check (check_plan below) and kept: the rows with
+  // more than CHK_LANE_MAX entries in ascending order, cut into chunks of <= CHK_CHUNK entries; chunk k covers entries [chk_beg[k], chk_end[k])
+  // and the chunks of chk_rows[j] are [chk_first[j], chk_first[j + 1])
+  mutable bool chk_built;
+  mutable uint32_t chk_nrows, chk_nchunks;
+  mutable uint32_t *chk_rows, *chk_first, *chk_beg, *chk_end;
 };
 
 // multiply_vec (sparse_mlpoly.rs:454-464)
@@ -25,6 +31,101 @@ __global__ void __launch_bounds__(256) k_spmv(const uint32_t* __restrict__ row_p
   Fq acc = fq_zero();
   for (uint32_t e = row_ptr[r]; e < row_ptr[r + 1]; e++) acc = fq_add(acc, fq_mul(ld_fq(val + e), ld_fq(z + col[e])));
   st_fq(out + r, acc);
+}
+
+// ---- R1CSShape::is_sat (r1cs.rs:240-266): (A z)[r] * (B z)[r] == (C z)[r] for every row, fused — no Az, Bz, Cz tables are written ----
+// A row of up to CHK_LANE_MAX entries is walked by one lane (the synthetic instance: one entry per row and matrix). A lane that walks a row
+// keeps the other 63 lanes of its wavefront waiting, so a wavefront takes as long as its longest row: past 32 entries the 64 lanes do more
+// reading the row side by side (coalesced col / val, 16 entries per lane and chunk) than one lane does alone, chunk launch included. A longer
+// row is therefore cut into chunks of CHK_CHUNK entries that k_r1cs_chunks sums one wavefront each, whatever the row's length; k_r1cs_check
+// adds a row's chunk sums across the lanes of the wavefront that owns the row (one partial per 65536 entries and lane).
+constexpr uint32_t CHK_LANE_MAX = 32, CHK_CHUNK = 1024;
+struct Csr3 {
+  const uint32_t *row_ptr[3], *col[3];
+  const Fq* val[3];
+  const uint32_t *long_rows[3], *long_first[3], *chunk_beg[3], *chunk_end[3];
+  uint32_t n_long[3], n_chunks[3], part_off[3];  // part_off: where a matrix's chunk sums start in `partials`
+};
+__device__ __forceinline__ Fq wave_sum_fq(Fq v) {  // the sum over the 64 lanes, in every lane
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    Fq o;
+#pragma unroll
+    for (int w = 0; w < 4; w++) o.l[w] = __shfl_xor((unsigned long long)v.l[w], m, 64);
+    v = fq_add(v, o);
+  }
+  return v;
+}
+// grid (ceil(max chunks / 4), 3 matrices): one wavefront per chunk, partials[part_off[m] + k] = sum of val * z[col] over chunk k of matrix m
+__global__ void __launch_bounds__(256) k_r1cs_chunks(Csr3 M, const Fq* __restrict__ z, Fq* __restrict__ partials) { SP_FG_PRIO();
+  const int m = blockIdx.y;
+  const unsigned lane = threadIdx.x & 63;
+  const uint32_t k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= M.n_chunks[m]) return;  // the whole wavefront
+  const uint32_t* __restrict__ col = M.col[m];
+  const Fq* __restrict__ val = M.val[m];
+  const uint32_t end = M.chunk_end[m][k];
+  Fq acc = fq_zero();
+  for (uint32_t e = M.chunk_beg[m][k] + lane; e < end; e += 64) acc = fq_add(acc, fq_mul(ld_fq(val + e), ld_fq(z + col[e])));
+  acc = wave_sum_fq(acc);
+  if (lane == 0) st_fq(partials + M.part_off[m] + k, acc);
+}
+// A wavefront owns 64 consecutive rows, a lane one of them. res[0] += violated rows, res[1] = min(res[1], first violated row),
+// bitmap[r / 64] bit r % 64 = row r is violated (every word of ceil(num_rows / 64) is written).
+__global__ void __launch_bounds__(256) k_r1cs_check(Csr3 M, const Fq* __restrict__ z, const Fq* __restrict__ partials, size_t num_rows,
+                                                    unsigned long long* __restrict__ res, unsigned long long* __restrict__ bitmap) { SP_FG_PRIO();
+  const unsigned lane = threadIdx.x & 63;
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t base = r - lane;  // first row of the wavefront
+  if (base >= num_rows) return;
+  const bool live = r < num_rows;
+  uint32_t beg[3], len[3];
+  bool is_long = false;
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    beg[m] = live ? M.row_ptr[m][r] : 0;
+    len[m] = live ? M.row_ptr[m][r + 1] - beg[m] : 0;
+    is_long |= len[m] > CHK_LANE_MAX;
+  }
+  Fq s[3];
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    s[m] = fq_zero();
+    if (!is_long)
+      for (uint32_t e = beg[m]; e < beg[m] + len[m]; e++) s[m] = fq_add(s[m], fq_mul(ld_fq(M.val[m] + e), ld_fq(z + M.col[m][e])));
+  }
+  // rows with a long side: the wavefront takes them one by one (the loop is uniform), every matrix summed across the lanes
+  for (unsigned long long todo = __ballot(is_long); todo; todo &= todo - 1) {
+    const int src = __ffsll(todo) - 1;
+    const uint32_t row = (uint32_t)(base + src);
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+      const uint32_t b = __shfl(beg[m], src, 64), n = __shfl(len[m], src, 64);
+      Fq acc = fq_zero();
+      if (n > CHK_LANE_MAX) {  // its chunk sums: `row` is in the ascending list of this matrix's long rows
+        uint32_t lo = 0, hi = M.n_long[m];
+        while (lo + 1 < hi) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (M.long_rows[m][mid] <= row) lo = mid; else hi = mid;
+        }
+        const uint32_t k1 = M.long_first[m][lo + 1];
+        for (uint32_t k = M.long_first[m][lo] + lane; k < k1; k += 64) acc = fq_add(acc, ld_fq(partials + M.part_off[m] + k));
+      } else if (lane < n) {
+        acc = fq_mul(ld_fq(M.val[m] + b + lane), ld_fq(z + M.col[m][b + lane]));
+      }
+      acc = wave_sum_fq(acc);
+      if ((int)lane == src) s[m] = acc;
+    }
+  }
+  const bool bad = live && !fq_eq(fq_mul(s[0], s[1]), s[2]);  // canonical limbs: equality of values is equality of limbs
+  const unsigned long long mask = __ballot(bad);
+  if (lane == 0) {
+    bitmap[base >> 6] = mask;
+    if (mask) {
+      atomicAdd(res, (unsigned long long)__popcll(mask));
+      atomicMin(res + 1, (unsigned long long)(base + (__ffsll(mask) - 1)));
+    }
+  }
 }
 struct Csc3 {
   const uint32_t* col_ptr[3];
@@ -87,6 +188,29 @@ static int32_t dev_put(sp_ctx* c, T** d, const std::vector<T>& h) {
   size_t bytes = sizeof(T) * (h.size() ? h.size() : 1);
   HIPCHK(hipMalloc((void**)d, bytes));
   if (!h.empty()) HIPCHK(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+  return SP_OK;
+}
+
+// The long rows of a matrix and their chunks, from its row_ptr (device), once per matrix: a matrix without long rows gets no lists.
+static int32_t check_plan(sp_ctx* c, const sp_sparse* m) {
+  if (m->chk_built) return SP_OK;
+  std::vector<uint32_t> ptr(m->num_rows + 1), rows, first, cb, ce;
+  HIPCHK(hipMemcpy(ptr.data(), m->row_ptr, 4 * ptr.size(), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < m->num_rows; r++) {
+    if (ptr[r + 1] - ptr[r] <= CHK_LANE_MAX) continue;
+    rows.push_back((uint32_t)r);
+    first.push_back((uint32_t)cb.size());
+    for (uint64_t b = ptr[r]; b < ptr[r + 1]; b += CHK_CHUNK) { cb.push_back((uint32_t)b); ce.push_back((uint32_t)std::min<uint64_t>(b + CHK_CHUNK, ptr[r + 1])); }
+  }
+  if (!rows.empty()) {
+    first.push_back((uint32_t)cb.size());
+    SPCHK(dev_put(c, &m->chk_rows, rows));
+    SPCHK(dev_put(c, &m->chk_first, first));
+    SPCHK(dev_put(c, &m->chk_beg, cb));
+    SPCHK(dev_put(c, &m->chk_end, ce));
+  }
+  m->chk_nrows = (uint32_t)rows.size(); m->chk_nchunks = (uint32_t)cb.size();
+  m->chk_built = true;
   return SP_OK;
 }
 
@@ -160,7 +284,8 @@ void sp_sparse_free(sp_sparse* m) {
   if (!m) return;
   (void)hipSetDevice(m->ctx->dev);
   (void)hipStreamSynchronize(m->ctx->stream);
-  void* ps[] = {m->row_ptr, m->csr_col, m->csr_row, m->csr_val, m->col_ptr, m->csc_row, m->csc_val, m->ent_row, m->ent_col, m->ent_val};
+  void* ps[] = {m->row_ptr, m->csr_col, m->csr_row, m->csr_val, m->col_ptr, m->csc_row, m->csc_val, m->ent_row, m->ent_col, m->ent_val,
+                m->chk_rows, m->chk_first, m->chk_beg, m->chk_end};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   delete m;
@@ -175,6 +300,55 @@ int32_t sp_sparse_mulvec(sp_ctx* c, const sp_sparse* m, const sp_table* z, sp_ta
                        (const uint32_t*)m->csr_col, (const Fq*)m->csr_val, (const Fq*)z->d, m->num_rows, (*out)->d);
   }
   return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
+}
+int32_t sp_r1cs_check(sp_ctx* c, const sp_sparse* A, const sp_sparse* B, const sp_sparse* C, const sp_table* z, uint64_t* violated, uint64_t* first_row,
+                      uint64_t* rows_out, size_t rows_cap) {
+  if (!c || !A || !B || !C || !z || !violated || !first_row) return SP_EINVAL;
+  const sp_sparse* ms[3] = {A, B, C};
+  const size_t nr = A->num_rows;
+  if (B->num_rows != nr || C->num_rows != nr || B->num_cols != A->num_cols || C->num_cols != A->num_cols || z->len < A->num_cols || c->pend_eval.active)
+    return SP_EINVAL;
+  HIPCHK(hipSetDevice(c->dev));
+  ahead_cancel(c);
+  Csr3 M;
+  memset(&M, 0, sizeof M);
+  uint32_t total = 0, most = 0;
+  double bytes = 4.0 * 3 * (double)(nr + 1);
+  for (int k = 0; k < 3; k++) {
+    SPCHK(check_plan(c, ms[k]));
+    M.row_ptr[k] = ms[k]->row_ptr; M.col[k] = ms[k]->csr_col; M.val[k] = ms[k]->csr_val;
+    M.long_rows[k] = ms[k]->chk_rows; M.long_first[k] = ms[k]->chk_first; M.chunk_beg[k] = ms[k]->chk_beg; M.chunk_end[k] = ms[k]->chk_end;
+    M.n_long[k] = ms[k]->chk_nrows; M.n_chunks[k] = ms[k]->chk_nchunks; M.part_off[k] = total;
+    total += ms[k]->chk_nchunks;
+    most = std::max(most, ms[k]->chk_nchunks);
+    bytes += (double)ms[k]->nnz * (4 + 32 + 32);
+  }
+  // scratch: [0, 16) count and first row, [64, ..) the bitmap, then the chunk sums
+  const size_t nwords = (nr + 63) / 64, off_part = (64 + 8 * nwords + 31) & ~(size_t)31;
+  SPCHK(ensure(&c->scratch, &c->scratch_cap, off_part + 32 * (size_t)total));
+  unsigned long long* res = (unsigned long long*)c->scratch;
+  unsigned long long* bitmap = (unsigned long long*)((uint8_t*)c->scratch + 64);
+  Fq* partials = (Fq*)((uint8_t*)c->scratch + off_part);
+  HIPCHK(hipMemsetAsync(res, 0, 8, c->stream));
+  HIPCHK(hipMemsetAsync(res + 1, 0xff, 8, c->stream));
+  {
+    ProfScope ps(c, PF_SPARSE, bytes);
+    if (total)
+      hipLaunchKernelGGL(k_r1cs_chunks, dim3((most + 3) / 4, 3), dim3(256), 0, c->stream, M, (const Fq*)z->d, partials);
+    hipLaunchKernelGGL(k_r1cs_check, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream, M, (const Fq*)z->d, (const Fq*)partials, nr, res, bitmap);
+  }
+  if (hipGetLastError() != hipSuccess) return SP_EHIP;
+  uint64_t out[2];
+  SPCHK(fetch_out(c, res, out, sizeof out));
+  *violated = out[0]; *first_row = out[1];
+  if (rows_out && rows_cap && out[0]) {  // the lowest failing indices, from the bitmap
+    std::vector<uint64_t> bm(nwords);
+    SPCHK(fetch_out(c, bitmap, bm.data(), 8 * nwords));
+    size_t n = 0;
+    for (size_t w = 0; w < nwords && n < rows_cap; w++)
+      for (uint64_t bits = bm[w]; bits && n < rows_cap; bits &= bits - 1) rows_out[n++] = 64 * w + (uint64_t)__builtin_ctzll(bits);
+  }
+  return SP_OK;
 }
 int32_t sp_sparse_eval_table(sp_ctx* c, const sp_sparse* const* ms, const uint64_t* w, size_t nm, const sp_table* rx, sp_table** out) {
   if (!c || !ms || !w || !rx || !out || nm == 0 || nm > 3) return SP_EINVAL;

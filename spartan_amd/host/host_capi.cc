@@ -309,6 +309,26 @@ void* spz_vars_assignment_new(void* ctx, const uint64_t* vars, size_t nvars) {
   return guard([&]() -> void* { return new VarsAssignment(*(Ctx*)ctx, (const sp::Fq*)vars, nvars); });
 }
 void spz_vars_assignment_free(void* a) { delete (VarsAssignment*)a; }
+// Instance::is_sat (lib.rs:230-259) with the report of the device check: 1 = satisfied, 0 = not, -1 = error (spz_last_error(): "InvalidNumberOfInputs"
+// as R1CSError). `assignment` (a spz_vars_assignment_new handle) or `vars` (host scalars). report[0] = violated constraints, report[1] = the first
+// (UINT64_MAX when none); rows_out (may be NULL) receives the min(report[0], rows_cap) lowest violated constraint numbers.
+int spz_instance_is_sat(void* inst, void* assignment, const uint64_t* vars, size_t nvars, const uint64_t* inputs, size_t ninputs, uint64_t report[2],
+                        uint64_t* rows_out, size_t rows_cap) {
+  try {
+    g_err.clear();
+    const Instance& I = *(Instance*)inst;
+    SatReport rep;
+    const size_t want = rows_out ? rows_cap : 0;
+    const bool sat = assignment ? I.is_sat(*(VarsAssignment*)assignment, limbs_vec(inputs, ninputs), &rep, want)
+                                : I.is_sat((const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs), &rep, want);
+    if (report) { report[0] = rep.violated; report[1] = rep.first_row; }
+    for (size_t i = 0; i < rep.rows.size(); i++) rows_out[i] = rep.rows[i];
+    return sat ? 1 : 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 void* spz_snark_prove_resident(void* ctx, void* inst, void* gens, void* enc, void* assignment, const uint64_t* inputs, size_t ninputs,
                                const char* transcript_label, const uint64_t tape_seed[4], double* times10) {
   return guard([&]() -> void* {

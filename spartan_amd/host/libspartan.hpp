@@ -148,6 +148,10 @@ struct SNARKGens {  // src/lib.rs:276-309
 
 // ---- instance ----
 struct SparseEntry { uint64_t row, col; Fq val; };
+struct VarsAssignment;
+// What Instance::is_sat found: the number of constraints with (A z)[r] * (B z)[r] != (C z)[r], the smallest such r (UINT64_MAX when there is
+// none) and the lowest `max_rows` of them in ascending order — the caller's constraint numbers (Instance::new pads rows at the end only).
+struct SatReport { uint64_t violated = 0, first_row = UINT64_MAX; std::vector<uint64_t> rows; };
 struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the matrices resident on the device
   sp_ctx* c = nullptr;
   size_t num_cons = 0, num_vars = 0, num_inputs = 0;
@@ -175,6 +179,12 @@ struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the m
   // stream keyed by `seed` ("spartan-synthetic-r1cs" || LE64(seed)); returns the satisfying assignment.
   static std::unique_ptr<Instance> produce_synthetic_r1cs(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, uint64_t seed,
                                                           FqVec* vars, FqVec* inputs);
+  // Instance::is_sat (lib.rs:230-259 -> r1cs.rs:240-266) on the device (sp_r1cs_check): one round trip, nothing table-sized crosses PCIe.
+  // Throws Error("InvalidNumberOfInputs") where the reference returns Err: more variables than the padded num_vars, or inputs.size() !=
+  // num_inputs; fewer variables are zero-padded. prove() does not call it: a caller checks, then proves, on the same resident assignment.
+  bool is_sat(const Fq* vars, size_t num_vars_given, const FqVec& inputs, SatReport* report = nullptr, size_t max_rows = 0,
+              const sp_table* vars_resident = nullptr) const;
+  bool is_sat(const VarsAssignment& vars, const FqVec& inputs, SatReport* report = nullptr, size_t max_rows = 0) const;
 };
 // VarsAssignment (lib.rs:56-105, Assignment::new) with the scalars resident in HBM: the reference parses the caller's bytes
 // into Scalars in the constructor, outside prove; here the constructor also uploads them, once, and every proof over the

@@ -1166,6 +1166,32 @@ VarsAssignment::VarsAssignment(Ctx& ctx, const Fq* vars, size_t n_) : c(ctx.h), 
   SPX(sp_table_upload(c, vars[0].l, n_, &t));
   tab = DevTable(c, t);
 }
+// Instance::is_sat (lib.rs:230-259). z = vars | 0... | 1 | inputs | 0... is built on the device the way r1cs_prove builds it.
+bool Instance::is_sat(const Fq* vars, size_t nvars_given, const FqVec& inputs, SatReport* report, size_t max_rows, const sp_table* vars_resident) const {
+  if (nvars_given > num_vars || inputs.size() != num_inputs) throw Error("InvalidNumberOfInputs");  // lib.rs:235-241
+  DevTable z = tab_alloc(c, 2 * num_vars);  // zero-filled: the padding of lib.rs:244-252
+  if (vars_resident) {
+    REQUIRE(sp_table_len(vars_resident) == nvars_given);
+    if (nvars_given) SPX(sp_table_copy(c, z.h, 0, vars_resident, 0, nvars_given));
+  } else if (nvars_given) {
+    REQUIRE(vars != nullptr);
+    SPX(sp_table_write(c, z.h, 0, vars[0].l, nvars_given));
+  }
+  FqVec tail;
+  tail.push_back(fq_one());
+  tail.insert(tail.end(), inputs.begin(), inputs.end());
+  SPX(sp_table_write(c, z.h, num_vars, U(tail), tail.size()));
+  SatReport rep;
+  rep.rows.resize(std::min(max_rows, num_cons));
+  SPX(sp_r1cs_check(c, dA, dB, dC, z.h, &rep.violated, &rep.first_row, rep.rows.empty() ? nullptr : rep.rows.data(), rep.rows.size()));
+  rep.rows.resize((size_t)std::min<uint64_t>(rep.violated, rep.rows.size()));
+  const bool sat = rep.violated == 0;
+  if (report) *report = std::move(rep);
+  return sat;
+}
+bool Instance::is_sat(const VarsAssignment& vars, const FqVec& inputs, SatReport* report, size_t max_rows) const {
+  return is_sat(nullptr, vars.n, inputs, report, max_rows, vars.tab.h);
+}
 NIZK NIZK::prove(Ctx& ctx, const Instance& inst, const Fq* vars, size_t nvars_given, const FqVec& inputs, const NIZKGens& gens, Transcript& t,
                  const Fq* tape_seed, ProveTimes* tm, const sp_table* vars_resident) {  // lib.rs:501-546
   double t0 = now_s();

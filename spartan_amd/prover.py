@@ -107,9 +107,40 @@ class Instance:
         if H.spz_instance_set_digest_header(self.h, ctypes.c_int(1 if old_header else 0)) != 0:
             raise SpartanHipError("set_digest_header: " + H.spz_last_error().decode())
 
+    def check(self, vars_, inputs, max_rows=16):
+        """Instance::is_sat (lib.rs:230-259) on the device, with a report: .violated = the number of constraints the assignment fails,
+        .first_row = the smallest of them (None when satisfied), .rows = the lowest max_rows of them, ascending. vars_: Montgomery limbs
+        (a ctypes uint64 array; fewer than num_vars are zero-padded) or a VarsAssignment. Raises SpartanHipError("InvalidNumberOfInputs")
+        where the reference returns that R1CSError: too many variables, or a number of inputs other than num_inputs."""
+        res = isinstance(vars_, VarsAssignment)
+        rep = (ctypes.c_uint64 * 2)()
+        rows = (ctypes.c_uint64 * max(max_rows, 1))()
+        n_in = self.num_inputs if inputs is self.inputs else len(inputs) // 4   # the instance's own buffer holds one element when num_inputs is 0
+        rc = H.spz_instance_is_sat(self.h, vars_.h if res else None, None if res else vars_, sz(0 if res else len(vars_) // 4), inputs,
+                                   sz(n_in), rep, rows if max_rows > 0 else None, sz(max_rows))
+        if rc < 0:
+            raise SpartanHipError(f"Instance::is_sat failed: {H.spz_last_error().decode()}")
+        violated = int(rep[0])
+        return SatReport(violated, int(rep[1]) if violated else None, [int(r) for r in rows[:min(violated, max_rows)]])
+
+    def is_sat(self, vars_, inputs):
+        return self.check(vars_, inputs, max_rows=0).violated == 0
+
     def free(self):
         if self.h:
             H.spz_instance_free(self.h); self.h = None
+
+
+class SatReport:
+    """what Instance.check found (bool(report): the assignment satisfies the instance)"""
+    def __init__(self, violated, first_row, rows):
+        self.violated, self.first_row, self.rows = violated, first_row, rows
+
+    def __bool__(self):
+        return self.violated == 0
+
+    def __repr__(self):
+        return f"SatReport(violated={self.violated}, first_row={self.first_row}, rows={self.rows})"
 
 
 class SNARKGens:
