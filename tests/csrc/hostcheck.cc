@@ -7,6 +7,7 @@
 
 #include "../../spartan_amd/csrc/msm.hpp"
 #include "../../spartan_amd/csrc/fe10.hpp"
+#include "checkops.hpp"
 
 using namespace sp;
 static Fq L(const uint64_t* p) { Fq x; memcpy(x.l, p, 32); return x; }
@@ -120,6 +121,23 @@ int hc_msm_fixed_geom(const uint8_t* pts_comp, size_t n, const uint64_t* scalars
     }
   }
   pt_compress(a1, out_stream); pt_compress(a2, out_stream2); pt_compress(a3, out_digit);
+  return 1;
+}
+
+// the element-wise wrappers of checkops.hpp (the ones devcheck.hip runs on the device) over n elements of 32 bytes: hc_<op>_n(a, b, out, n)
+#define HC_ENTRY(name, OP, ALT) \
+  void hc_##name##_n(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n) { for (size_t i = 0; i < n; i++) chk::OP::run(a + 32 * i, (b ? b : a) + 32 * i, out + 32 * i); }
+CHK_OPS(HC_ENTRY)
+#undef HC_ENTRY
+// single-element forms the shim lacked
+void hc_fq_dbl(const uint64_t* a, uint64_t* o) { O(fq_dbl(L(a)), o); }
+void hc_fq_sqr(const uint64_t* a, uint64_t* o) { O(fq_sqr(L(a)), o); }
+void hc_fq_to_mont(const uint64_t* a, uint64_t* o) { O(fq_to_mont(L(a)), o); }
+void hc_fp_neg_raw(const uint64_t* a, uint8_t* o) { Fp x; memcpy(x.v, a, 32); fp_to_bytes(fp_neg(x), o); }
+int hc_pt_madd(const uint8_t* a, const uint8_t* b, int neg, uint8_t* out) {
+  Pt p, q;
+  if (!pt_decompress(a, &p) || !pt_decompress(b, &q)) return 0;
+  pt_compress(pt_madd(p, pt_to_niels(q, fp_invert(q.Z)), neg != 0), out);
   return 1;
 }
 }

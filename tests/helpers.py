@@ -35,13 +35,52 @@ def load_oracle():
     return L
 
 
+def _csrc_headers():
+    d = os.path.join(ROOT, "spartan_amd", "csrc")
+    return [os.path.join(d, f) for f in os.listdir(d) if f.endswith(".hpp")] + [os.path.join(ROOT, "tests", "csrc", "checkops.hpp")]
+
+
+def _stale(so, sources):
+    return not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in sources)
+
+
 def load_hostcheck():
     so = os.path.join(ROOT, "tests", "csrc", "libhostcheck.so")
     src = os.path.join(ROOT, "tests", "csrc", "hostcheck.cc")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+    if _stale(so, [src, os.path.join(ROOT, "tests", "csrc", "checkops.hpp")]):
         subprocess.check_call("g++ -O2 -std=c++17 -fPIC -shared -Wno-unknown-pragmas tests/csrc/hostcheck.cc -o tests/csrc/libhostcheck.so",
                               cwd=ROOT, shell=True)
     return ctypes.CDLL(so)
+
+
+DEVCHECK_GENERIC_FLAGS = "-DSP_FIELD_ADD_GENERIC -DSP_FQ_MUL_GENERIC -DSP_FP_MUL_GENERIC"
+
+
+def devcheck_build_cmd(generic=False):
+    """the product's flags (spartan_amd/csrc/Makefile); generic: the compiler's code for the u128 forms instead of the device forms"""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    return "%s --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared %stests/csrc/devcheck.hip -o tests/csrc/libdevcheck%s.so" % (
+        hipcc, DEVCHECK_GENERIC_FLAGS + " " if generic else "", "_generic" if generic else "")
+
+
+def load_devcheck(generic=False):
+    """the device microkernels of tests/csrc/devcheck.hip (one per field / curve operation): libdevcheck.so runs the device forms of
+    field.hpp, libdevcheck_generic.so the generic u128 forms on the same device. Built when missing or older than its sources."""
+    so = os.path.join(ROOT, "tests", "csrc", "libdevcheck%s.so" % ("_generic" if generic else ""))
+    if _stale(so, [os.path.join(ROOT, "tests", "csrc", "devcheck.hip")] + _csrc_headers()):
+        subprocess.check_call(devcheck_build_cmd(generic), cwd=ROOT, shell=True)
+    L = ctypes.CDLL(so)
+    L.dc_flags.restype = ctypes.c_int
+    return L
+
+
+def dc_call(L, op, a, b, n, mode=0, pattern=0):
+    """run dc_<op> over n packed 32-byte elements; returns (hipError_t, output bytes)"""
+    out = ctypes.create_string_buffer(32 * n)
+    f = getattr(L, "dc_" + op)
+    f.restype = ctypes.c_int
+    rc = f(ctypes.c_char_p(a), ctypes.c_char_p(b), out, sz(n), ctypes.c_int(mode), ctypes.c_uint64(pattern))
+    return rc, out.raw
 
 
 # ---- scalar helpers: python int (canonical value) <-> Montgomery limbs
