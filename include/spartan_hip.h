@@ -104,9 +104,9 @@ int sp_msm_window_bits(void);
  * while the set's tables keep >= 12 bits — they win at 2^20, 2^22 and 2^24 — and the LDS-staged form, with its tables built alongside, when
  * device memory was so short that the wide tables came out at 10 or 8 bits (stderr says so). SP_ENOMEM (with a message on stderr) if not even 8-bit
  * tables fit in free device memory.
- * FIXED PUBLIC BASES ONLY: every multi-scalar multiplication of this library (sp_commit_rows*, sp_msm_indexed, the inner-product
- * argument) runs over the points of a sp_gens through its precomputed tables. There is no variable-base device MSM — the prover
- * never needs one (every base on the path is a public generator). */
+ * FIXED PUBLIC BASES: every multi-scalar multiplication of the PROVER (sp_commit_rows*, sp_msm_indexed, the inner-product argument) runs
+ * over the points of a sp_gens through its precomputed tables (every base on the prover's path is a public generator).
+ * The one multiplication over points that are NOT a sp_gens is the verifier's: sp_msm_var (device) and sp_host_msm_var (calling thread) below. */
 /* A caller-supplied list may hold points with known relations between them (repeats, torsion shifts): the inner-product argument over such a
  * set always uses the COMPLETE addition formula in its trees; sets the library derives itself (sp_gens_from_uniform) use the faster dedicated one,
  * whose exceptional pairs cannot occur between sums over independent hash-to-curve points. */
@@ -185,6 +185,16 @@ int32_t sp_host_commit_probe(const uint8_t* compressed /*32*npts*/, size_t npts,
  * arithmetic with which sp_ipa_finish_commit ends an inner-product argument on the calling thread's core (delta = d g_hat + r_delta h of
  * nizk/mod.rs:496-501 from the last round's two row sums, bullet.rs:108). SP_EPOINT for an invalid encoding. */
 int32_t sp_host_msm2_probe(const uint8_t p1[32], const uint64_t k1[4], const uint8_t p2[32], const uint64_t k2[4], uint8_t out[32]);
+/* ---- variable-base multi-scalar multiplication (the verifiers) ----
+ * out = compress( sum_{j<n} S[j] * P[j] ), P[j] given as 32-byte ristretto255 encodings that are NOT an sp_gens:
+ * GroupElement::vartime_multiscalar_mul over points that arrive with a proof (dense_mlpoly.rs:382-384). 1 <= n <= 65536; synchronous, one
+ * round trip. The points are untrusted (repeats, negatives of each other, the identity): every addition is the complete one. Signed 4-bit
+ * windows over (point, window) pairs, wavefront / LDS / cross-block sums, Horner recombination and the encode in one launch chain (msm_var.hip).
+ * SP_EINVAL: n = 0, n > 65536, a null pointer. SP_EPOINT: an encoding is invalid (decoded on the device; out is not written). */
+int32_t sp_msm_var(sp_ctx* ctx, const uint8_t* points /*32*n*/, const uint64_t* S /*4*n, Montgomery*/, size_t n, uint8_t out[32]);
+/* The same sum on the calling thread's core, no context, n <= 64: the 2..2 lg n + 1-term combinations of the verifiers
+ * (sumcheck.rs:127, r1csproof.rs:426,470, bullet.rs:216). SP_EINVAL: n = 0, n > 64, a null pointer. SP_EPOINT as above. */
+int32_t sp_host_msm_var(const uint8_t* points, const uint64_t* S, size_t n, uint8_t out[32]);
 /* Look-ahead for the zero-knowledge sum-checks. Inside their round loop nothing but DotProductProof::prove draws from the
  * random tape (d_vec, r_delta, r_beta: nizk/mod.rs:330-334), so a caller can take the draws of all rounds up front, in the
  * reference's order, and have a helper thread compute everything that depends on the tape alone while the rounds run:

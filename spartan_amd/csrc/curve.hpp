@@ -263,6 +263,31 @@ SP_HD Pt pt_from_uniform_bytes(const uint8_t b[64]) {
   return pt_add(pt_elligator(t1), pt_elligator(t2));
 }
 
+// ---------------------------------------------------------------- variable-base multiplication (msm_var.hip, sp_host_msm_var)
+SP_HD Pt pt_neg(const Pt& p) { return Pt{fp_neg(p.X), p.Y, p.Z, fp_neg(p.T)}; }
+// Signed 4-bit digits of a CANONICAL scalar k < q < 2^253: k = sum_w d[w] 16^w with d[w] in [-8, 8]. The top nibble of k is at most 1,
+// so the last carry fits the 64th window and no 65th is needed.
+constexpr int SP_VAR_WINDOWS = 64, SP_VAR_TABLE = 8;
+SP_HD void fq_signed_digits4(const Fq& k, int8_t d[SP_VAR_WINDOWS]) {
+  int carry = 0;
+  for (int w = 0; w < SP_VAR_WINDOWS; w++) {
+    int v = (int)((k.l[w / 16] >> (4 * (w % 16))) & 15) + carry;
+    carry = v > 8;
+    d[w] = (int8_t)(carry ? v - 16 : v);
+  }
+}
+// T[m - 1] = m P for m = 1 .. 8 (complete additions: P may be the identity or of small order after decoding)
+SP_HD void pt_var_table(const Pt& p, Pt T[SP_VAR_TABLE]) {
+  T[0] = p;
+  T[1] = pt_dbl(p);
+  T[2] = pt_add(T[1], p);
+  T[3] = pt_dbl(T[1]);
+  T[4] = pt_add(T[3], p);
+  T[5] = pt_dbl(T[2]);
+  T[6] = pt_add(T[5], p);
+  T[7] = pt_dbl(T[3]);
+}
+
 // ---------------------------------------------------------------- serial-chain forms (fe10.hpp): LDS tree additions
 // and the ristretto encode executed by a handful of waves on the commit critical path. Same group elements, same bytes.
 struct Pt10 {

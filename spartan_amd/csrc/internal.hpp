@@ -35,6 +35,7 @@ enum ProfFamily {
   PF_IPA,
   PF_SPARK,
   PF_MISC,
+  PF_MSM_VAR,
   PF_COUNT
 };
 extern const char* kProfNames[PF_COUNT];

@@ -526,6 +526,36 @@ int32_t sp_host_msm2_probe(const uint8_t p1[32], const uint64_t k1[4], const uin
   pt_compress(pt_var_msm2(P1, a, P2, b), out);
   return SP_OK;
 }
+// Device-free form of sp_msm_var for the few-term combinations of the verifiers (sumcheck.rs:127, r1csproof.rs:426,470, bullet.rs:216): sum_j S[j] P[j]
+// over n <= 64 encoded points on the calling thread's core. Straus over the same signed 4-bit digits and 1..8 P tables as the device kernel
+// (curve.hpp), complete additions throughout: the points come from a proof. 252 doublings + at most 64 n additions + 7 n for the tables.
+int32_t sp_host_msm_var(const uint8_t* points, const uint64_t* S, size_t n, uint8_t out[32]) {
+  if (!points || !S || !out || n == 0 || n > 64) return SP_EINVAL;
+  std::vector<Pt> T(n * SP_VAR_TABLE);
+  std::vector<int8_t> D(n * SP_VAR_WINDOWS);
+  for (size_t j = 0; j < n; j++) {
+    Pt p;
+    if (!pt_decompress(points + 32 * j, &p)) return SP_EPOINT;
+    pt_var_table(p, &T[j * SP_VAR_TABLE]);
+    Fq k;
+    memcpy(k.l, S + 4 * j, 32);
+    fq_signed_digits4(fq_from_mont(k), &D[j * SP_VAR_WINDOWS]);
+  }
+  Pt acc = pt_identity();
+  bool started = false;
+  for (int w = SP_VAR_WINDOWS - 1; w >= 0; w--) {
+    if (started) acc = pt_dbl(pt_dbl(pt_dbl(pt_dbl(acc))));
+    for (size_t j = 0; j < n; j++) {
+      const int d = D[j * SP_VAR_WINDOWS + w];
+      if (!d) continue;
+      const Pt& e = T[j * SP_VAR_TABLE + (d < 0 ? -d : d) - 1];
+      acc = pt_add(acc, d < 0 ? pt_neg(e) : e);
+      started = true;
+    }
+  }
+  pt_compress(acc, out);
+  return SP_OK;
+}
 int32_t sp_ipa_finish_commit(sp_ipa* ipa, const uint64_t d[4], const uint64_t r[4], uint64_t a_hat[4], uint64_t b_hat[4], uint8_t delta_out[32]) {
   if (!ipa || !d || !r || !a_hat || !b_hat || !delta_out || ipa->n_cur != 1) return SP_EINVAL;
   if (ipa_finish_on_host(ipa, d, r, a_hat, b_hat, delta_out)) return SP_OK;

@@ -374,6 +374,53 @@ void* spz_nizk_prove(void* ctx, void* inst, void* gens, const uint64_t* vars, si
     return h;
   });
 }
+// NIZK::verify (lib.rs:549-587) of untrusted proof bytes: 1 accept, 0 reject, -1 malformed bytes (NIZK::deserialize), -2 error (spz_last_error():
+// "InvalidNumberOfInputs" as Instance::is_sat raises it, or a device failure). Nothing throws across the boundary.
+static int nizk_verify_on(void* ctx, void* inst, void* gens, const uint8_t* proof, size_t proof_len, const uint64_t* inputs, size_t n_inputs, Transcript& t) {
+  NIZK p;
+  if (!NIZK::deserialize(proof, proof_len, &p)) return -1;
+  return p.verify(*(Ctx*)ctx, *(Instance*)inst, limbs_vec(inputs, n_inputs), t, *(NIZKGens*)gens);
+}
+int spz_nizk_verify(void* ctx, void* inst, void* gens, const uint8_t* proof, size_t proof_len, const uint64_t* inputs, size_t n_inputs,
+                    const char* transcript_label) {
+  try {
+    g_err.clear();
+    if (!ctx || !inst || !gens || !proof || !transcript_label || (n_inputs && !inputs)) throw Error("spz_nizk_verify: bad arguments");
+    Transcript t(transcript_label);
+    return nizk_verify_on(ctx, inst, gens, proof, proof_len, inputs, n_inputs, t);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -2;
+  }
+}
+// the same on a caller-owned transcript (spz_nizk_prove_t): continued by the verification and left in the state it ends in
+int spz_nizk_verify_t(void* ctx, void* inst, void* gens, const uint8_t* proof, size_t proof_len, const uint64_t* inputs, size_t n_inputs,
+                      uint8_t transcript_state[203]) {
+  try {
+    g_err.clear();
+    if (!ctx || !inst || !gens || !proof || !transcript_state || (n_inputs && !inputs)) throw Error("spz_nizk_verify_t: bad arguments");
+    Transcript t(Transcript::FromState(), transcript_state);
+    int v = nizk_verify_on(ctx, inst, gens, proof, proof_len, inputs, n_inputs, t);
+    t.export_state(transcript_state);
+    return v;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -2;
+  }
+}
+// test hook (no GPU): parse proof bytes and serialise them again. Returns the number of bytes (written when cap suffices), -1 when malformed.
+long long spz_nizk_parse_probe(const uint8_t* proof, size_t len, uint8_t* out, size_t cap) {
+  try {
+    NIZK p;
+    if (!NIZK::deserialize(proof, len, &p)) return -1;
+    std::vector<uint8_t> b = p.serialize();
+    if (out && cap >= b.size()) memcpy(out, b.data(), b.size());
+    return (long long)b.size();
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 size_t spz_proof_bytes(void* p, uint8_t* out, size_t cap) {
   ProofH* h = (ProofH*)p;
   if (out && cap >= h->bytes.size()) memcpy(out, h->bytes.data(), h->bytes.size());

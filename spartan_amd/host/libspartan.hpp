@@ -2,8 +2,8 @@
 // the C ABI in include/spartan_hip.h. It exists because no Rust toolchain is available here; in the drop-in
 // deployment this layer IS libspartan (Rust) with the `gpu` feature. Names and argument
 // meaning follow the reference: Instance, VarsAssignment/InputsAssignment, SNARKGens, NIZKGens,
-// ComputationCommitment/Decommitment, SNARK::{encode,prove}, NIZK::prove. Verifiers are out of scope
-// (SURVEY.md §2.1); tests verify the emitted bytes with the oracle's restated verifier.
+// ComputationCommitment/Decommitment, SNARK::{encode,prove}, NIZK::{prove,verify} (verifier.cc). SNARK::verify is not implemented
+// (SURVEY.md §2.1); tests verify SNARK bytes with the oracle's restated verifier.
 //
 // All table-sized field/group work of the prover runs on the GPU through sp_* calls; the host keeps what the
 // reference keeps next to its Transcript — Fiat–Shamir, O(log n)-sized scalar bookkeeping, serialization — and the
@@ -332,6 +332,13 @@ struct NIZK {  // lib.rs:488-587
     return prove(ctx, inst, nullptr, vars.n, inputs, gens, transcript, tape_seed, times, vars.tab.h);
   }
   std::vector<uint8_t> serialize() const;
+  // bincode of an UNTRUSTED proof into *out (verifier.cc): false for anything that is not exactly one NIZK — a length that does not fit the
+  // bytes that remain (checked before allocating), a scalar whose limbs are >= q, truncated input, trailing bytes. Never throws.
+  static bool deserialize(const uint8_t* bytes, size_t len, NIZK* out);
+  // NIZK::verify (lib.rs:549-587): 1 accept, 0 reject. The instance's digest is absorbed as NIZK::prove absorbs it; R1CSInstance::evaluate and the
+  // table-sized group operations run on the device (placement: verifier.cc). Throws Error("InvalidNumberOfInputs") for a wrong number of
+  // inputs (lib.rs:569), Error for a device failure; a proof that is merely wrong, or carries undecodable points, is a 0.
+  int verify(Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript& transcript, const NIZKGens& gens) const;
 };
 
 std::vector<uint8_t> serialize_r1cs_proof(const R1CSProof& p);

@@ -16,6 +16,7 @@ for f in ("spz_ctx_new", "spz_instance_new", "spz_instance_synthetic", "spz_snar
 for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode"):
     getattr(H, f).restype = sz
 H.spz_last_error.restype = ctypes.c_char_p
+H.spz_nizk_parse_probe.restype = ctypes.c_longlong
 for f in ("spz_ctx_free", "spz_instance_free", "spz_snark_gens_free", "spz_nizk_gens_free", "spz_encode_free", "spz_proof_free", "spz_vars_assignment_free"):
     getattr(H, f).argtypes = [vp]
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -257,6 +258,32 @@ class NIZK:
         p = _chk(H.spz_nizk_prove_t(ctx.h, inst.h, gens.h, vars_.h if res else None, None if res else vars_, sz(0 if res else len(vars_) // 4),
                                     inputs, sz(inst.num_inputs), transcript_state, tape_seed, tm), "NIZK::prove")
         return _proof_bytes(p)
+
+    @staticmethod
+    def verify_status(ctx, inst, proof_bytes, inputs, gens, transcript_label):
+        """NIZK::verify (lib.rs:549-587) of untrusted proof bytes on the device: 1 accept, 0 reject, -1 malformed bytes. `inputs`: Montgomery limbs
+        (a ctypes uint64 array) or the instance's own. Raises SpartanHipError("InvalidNumberOfInputs") for a wrong number of inputs, as
+        Instance.is_sat does."""
+        n_in = inst.num_inputs if inputs is inst.inputs else len(inputs) // 4
+        rc = H.spz_nizk_verify(ctx.h, inst.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(n_in), transcript_label)
+        if rc < -1:
+            raise SpartanHipError(f"NIZK::verify failed: {H.spz_last_error().decode()}")
+        return int(rc)
+
+    @staticmethod
+    def verify(ctx, inst, proof_bytes, inputs, gens, transcript_label):
+        """True when the proof is accepted; False for a rejected AND for a malformed proof (verify_status tells them apart)"""
+        return NIZK.verify_status(ctx, inst, proof_bytes, inputs, gens, transcript_label) == 1
+
+    @staticmethod
+    def verify_t(ctx, inst, proof_bytes, inputs, gens, transcript_state):
+        """NIZK::verify on a caller-owned transcript: the 203-byte state (see SNARK.prove_t) is continued by the verification and left in the
+        state it ends in — after an accepted proof, the state NIZK.prove_t left on the prover's side. Returns the status of verify_status."""
+        n_in = inst.num_inputs if inputs is inst.inputs else len(inputs) // 4
+        rc = H.spz_nizk_verify_t(ctx.h, inst.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(n_in), transcript_state)
+        if rc < -1:
+            raise SpartanHipError(f"NIZK::verify failed: {H.spz_last_error().decode()}")
+        return int(rc)
 
     @staticmethod
     def prove(ctx, inst, vars_, inputs, gens, transcript_label, tape_seed, times=None):
