@@ -8,6 +8,8 @@ change to the oracle (or to the HIP path, which the GPU tests compare against th
 
 Two groups:
   CASES      small instances; the CPU test suite regenerates them on every run (tests/test_golden.py).
+  STRUCTURED the small structured instances of tests/structured_cases.py (several entries per row, unequal nnz, shifted columns, an empty
+             matrix), under the "structured" key; regenerated on every run like CASES.
   BIG_CASES  the BASELINE.json configurations (SNARK 2^16 / 2^20 / 2^22, NIZK 2^16 / 2^20): minutes of oracle time each,
              generated once with `--big` (OpenMP threads = all cores) and kept under the "big" key; the GPU suite proves
              the same instances through the HIP path and compares length, SHA-256 and SHA-256 of each proof part.
@@ -16,8 +18,10 @@ import ctypes, hashlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from tests.helpers import load_oracle, sz, vp, u64x4, gens_bytes, real_miniz_zlib, oracle_shape_bincode
+from tests import structured_cases
 
 CASES = {"nizk": [(4, 2), (7, 3), (12, 5)], "snark": [(3, 1), (5, 2), (8, 3), (12, 4), (15, 5)]}  # (log2 size, seed)
+STRUCTURED = list(structured_cases.SMALL)  # tests/structured_cases.py: SNARK and NIZK proof and bincode(ComputationCommitment) of each small case
 BIG_CASES = {"nizk": [(16, 6), (20, 0)], "snark": [(16, 6), (20, 0), (22, 0)]}  # seed 0 = bench.py's instance and tape
 
 
@@ -71,13 +75,15 @@ def snark_case(orc, s, seed):
 
 
 def run(orc, cases=CASES):
-    out = {"generators": {}, "nizk": {}, "snark": {}}
+    out = {"generators": {}, "nizk": {}, "snark": {}, "structured": {}}
     for label in (b"gens_r1cs_sat", b"gens_r1cs_eval"):
         out["generators"][label.decode()] = gens_bytes(orc, 3, label).hex()
     for s, seed in cases["nizk"]:
         out["nizk"][f"s{s}_seed{seed}"] = nizk_case(orc, s, seed)
     for s, seed in cases["snark"]:
         out["snark"][f"s{s}_seed{seed}"] = snark_case(orc, s, seed)
+    for name in STRUCTURED:
+        out["structured"][name] = structured_cases.oracle_run(orc, name).entry()
     return out
 
 

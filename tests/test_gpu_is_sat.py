@@ -4,6 +4,7 @@ instance's exported entries. Every comparison is exact."""
 import ctypes, random
 import pytest
 from tests.helpers import *
+from tests.structured_cases import _skewed_instance
 
 pytestmark = pytest.mark.gpu
 
@@ -126,39 +127,6 @@ def test_wrong_witness_exact_report(P, ctx, orc, s):
     i = list(good_inputs); i[4] = (i[4] + 1) % Q              # an input that no constraint reads: still satisfied, here and for the oracle
     assert _failing_rows(nnz, rows, cols, vals_int, _z(good_vars, i, N), N) == [] and inst.is_sat(inst.vars, mont_bulk(i)) is True
     orc.orc_instance_free(oi); inst.free()
-
-
-def _skewed_instance(rng, num_cons, num_vars, num_inputs, n_short, pool):
-    """Row 0: A = every variable with a random coefficient (one (row, col) pair twice), B = the constant 1, C = the variable t = num_vars - 1,
-    which the assignment sets to A's sum. Rows 1..n_short: 1-3 entries per matrix over the variables of `pool`, C's constant term chosen so
-    that the row holds; one of them repeats a (row, col) pair in A. All other rows are empty. Returns entries (A, B, C) and the assignment."""
-    t, const = num_vars - 1, num_vars
-    v = [rng.randrange(Q) for _ in range(num_vars)]
-    inputs = [rng.randrange(Q) for _ in range(num_inputs)]
-    coef = [rng.randrange(1, Q) for _ in range(num_vars)]
-    dup_col, dup_coef = 5, rng.randrange(1, Q)
-    while coef[t] == 1:
-        coef[t] = rng.randrange(2, Q)
-    A = [(0, j, coef[j]) for j in range(num_vars)] + [(0, dup_col, dup_coef)]
-    rng.shuffle(A)                                            # the long row's entries arrive in no particular order
-    rest = (sum(coef[j] * v[j] for j in range(num_vars) if j != t) + dup_coef * v[dup_col]) % Q
-    v[t] = rest * pow((1 - coef[t]) % Q, Q - 2, Q) % Q        # t = rest + coef[t] * t
-    B, C = [(0, const, 1)], [(0, t, 1)]
-    touching = {}
-    for r in range(1, n_short + 1):
-        ea = [(r, rng.choice(pool), rng.randrange(1, Q)) for _ in range(rng.randint(1, 3))]
-        if r == 7:
-            ea.append((r, ea[0][1], rng.randrange(1, Q)))     # the same (row, col) again: the two entries add up
-        eb = [(r, rng.choice(pool + [const, const + 1]), rng.randrange(1, Q)) for _ in range(rng.randint(1, 2))]
-        ec = [(r, rng.choice(pool), rng.randrange(1, Q)) for _ in range(rng.randint(0, 2))]
-        zz = lambda c: v[c] if c < num_vars else ([1] + inputs)[c - num_vars]
-        a = sum(x * zz(c) for _, c, x in ea) % Q
-        b = sum(x * zz(c) for _, c, x in eb) % Q
-        ec.append((r, const, (a * b - sum(x * zz(c) for _, c, x in ec)) % Q))
-        A += ea; B += eb; C += ec
-        for _, c, _x in ea + eb + ec:
-            touching.setdefault(c, set()).add(r)
-    return (A, B, C), v, inputs, touching
 
 
 def test_skewed_instance_with_a_long_row(P, ctx, orc):
