@@ -67,7 +67,7 @@ if fixed:
     print("* A trip costs %.1f us beyond its kernel's body (launch call, dispatch, completion flag over PCIe, the proving thread's wake-up: trip_probe A with an" % fixed[0])
     print("  empty body); %d trips x %.1f us = %.1f ms of the %.1f ms proof is the ceiling of ANY scheme that keeps the arithmetic where it is." % (trips, fixed[0], trips * fixed[0] / 1e3, ms_proof))
 n2 = cnt("sp_sumcheck_bind2_eval_batched", "sp_sumcheck_bind2_eval_tables_batched")
-print("* (built, not the default) Launching the next two-rounds kernel ahead of its challenges (sumcheck.launch_ahead = 1; %d of the %d trips qualify: every two-bind" % (n2, trips))
+print("* (built in round 6, measured, since removed) Launching the next two-rounds kernel ahead of its challenges (sumcheck.launch_ahead = 1; %d of the %d trips qualify: every two-bind" % (n2, trips))
 print("  trip whose predecessor is a trip over the same tables): the probe's B against A is 1.3-6 us per trip depending on the body; in the proof the entry")
 print("  point's time falls by ~2.5 us per trip when it helps (the bell is one PCIe read away, the decision is relayed to the other workgroups through a")
 print("  device word) — 0.3 ms per proof in the first five A/B sessions, nothing in the four later ones: inside the +-0.4 ms run-to-run spread of the proof.")

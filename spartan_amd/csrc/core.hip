@@ -128,7 +128,6 @@ __global__ void k_done(volatile uint32_t* flag, uint32_t seq) { SP_FG_PRIO();
 // Wait until everything queued on the main stream has run. The stream is in-order, so the flag kernel runs after the
 // kernels (and copies) before it have completed, and their results in host memory precede the flag on the way to the host.
 uint32_t sync_post(sp_ctx* c) {
-  ahead_cancel(c);
   uint32_t seq = ++c->done_seq;
   hipLaunchKernelGGL(k_done, dim3(1), dim3(1), 0, c->stream, c->done_flag, seq);
   return seq;
@@ -137,7 +136,7 @@ int32_t sync_wait(sp_ctx* c, uint32_t seq) {
   for (uint64_t spins = 1;; spins++) {
     if (*c->done_flag == seq) { c->sync_epoch++; return SP_OK; }
     if ((spins & 0xFFFFF) == 0) {  // every ~ms: a faulted queue never delivers the flag
-      hipError_t e = hipStreamQuery(c->stream.s);  // the raw handle: the trip after this one may be waiting for its bell behind it
+      hipError_t e = hipStreamQuery(c->stream);
       if (e == hipSuccess) {
         if (*c->done_flag != seq) return SP_EHIP;
         c->sync_epoch++;
@@ -152,7 +151,6 @@ int32_t sync_wait(sp_ctx* c, uint32_t seq) {
 }
 int32_t sync_spin(sp_ctx* c) { return sync_wait(c, sync_post(c)); }
 DoneSig sig_make(sp_ctx* c, size_t total_workgroups) {
-  ahead_cancel(c);
   if (!c->done_counter) return sig_none();
   return DoneSig{c->done_flag, c->done_counter, ++c->done_seq, (uint32_t)total_workgroups, c->ktime};
 }
@@ -1112,8 +1110,7 @@ static int32_t ctx_init(sp_ctx* c, int device_id) {
     // platform: it succeeds, and a 1/8 mask runs an MSM exactly as fast as 8/8 — bench/bg_probe.py.)
     int lo = 0, hi = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIPCHK(hipStreamCreateWithPriority(&c->stream.s, hipStreamNonBlocking, hi));
-    c->stream.owner = c;
+    HIPCHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi));
     HIPCHK(hipStreamCreateWithPriority(&c->stream_side, hipStreamNonBlocking, hi));
     HIPCHK(hipEventCreateWithFlags(&c->side_ev, hipEventDisableTiming));
     HIPCHK(hipStreamCreateWithPriority(&c->stream_bg, hipStreamNonBlocking, lo));
@@ -1130,12 +1127,10 @@ static int32_t ctx_init(sp_ctx* c, int device_id) {
     c->bg_blocks = c->n_cus * (int)c->opt.v[OPT_BG_EIGHTHS] / 8;
   }
   HIPCHK(hipHostMalloc((void**)&c->hmap, HMAP_SIZE, hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&c->done_flag, 128, hipHostMallocDefault));
-  memset((void*)c->done_flag, 0, 128);
-  HIPCHK(hipHostMalloc((void**)&c->bell, sizeof(AheadBell), hipHostMallocDefault));
-  memset(c->bell, 0, sizeof(AheadBell));
+  HIPCHK(hipHostMalloc((void**)&c->done_flag, 64, hipHostMallocDefault));
+  *c->done_flag = 0;
   c->done_seq = 0;
-  HIPCHK(hipMalloc((void**)&c->done_counter, 512));  // word 0: DoneSig::counter | words 4..: row tickets of the fused small commitment | word 64: AheadArgs::decision | words 80..95: AheadArgs::chal
+  HIPCHK(hipMalloc((void**)&c->done_counter, 512));  // word 0: DoneSig::counter | words 4..: row tickets of the fused small commitment
   HIPCHK(hipMemset(c->done_counter, 0, 512));
   HIPCHK(hipMalloc((void**)&c->q_heads, 4 * (size_t)MSMQ_BLOCK_WORDS * MSMQ_BLOCKS));
 #ifdef SP_KTIME
@@ -1159,11 +1154,7 @@ extern "C" {
 void sp_ctx_destroy(sp_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->dev);
-  ahead_cancel(c);
   (void)hipStreamSynchronize(c->stream);
-  if (c->ahead.n_armed && sp_default_options().v[OPT_HOST_CALLSTATS])
-    fprintf(stderr, "[callstats] kernels enqueued ahead of their challenges: %llu, rung %llu, cancelled %llu, gave up %llu\n", (unsigned long long)c->ahead.n_armed,
-            (unsigned long long)c->ahead.n_rung, (unsigned long long)c->ahead.n_cancelled, (unsigned long long)c->ahead.n_gave_up);
   prof_drain(c);
   for (auto e : c->free_events) (void)hipEventDestroy(e);
   for (auto& kv : c->pool)
@@ -1174,7 +1165,6 @@ void sp_ctx_destroy(sp_ctx* c) {
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->hmap) (void)hipHostFree(c->hmap);
   if (c->done_flag) (void)hipHostFree((void*)c->done_flag);
-  if (c->bell) (void)hipHostFree((void*)c->bell);
   if (c->done_counter) (void)hipFree(c->done_counter);
   if (c->prof_epoch) (void)hipEventDestroy(c->prof_epoch);
   if (c->q_heads) (void)hipFree(c->q_heads);
@@ -2080,7 +2070,6 @@ extern "C" {
 void sp_table_free(sp_table* t) {
   if (!t) return;
   (void)hipSetDevice(t->ctx->dev);
-  ahead_cancel(t->ctx);  // a kernel enqueued ahead of its challenges may hold this table's buffers
   if (t->owner) pool_release(t->ctx, t->d, t->d_bytes);
   if (t->alt) pool_release(t->ctx, t->alt, t->alt_bytes);
   delete t;

@@ -309,7 +309,6 @@ int32_t sp_r1cs_check(sp_ctx* c, const sp_sparse* A, const sp_sparse* B, const s
   if (B->num_rows != nr || C->num_rows != nr || B->num_cols != A->num_cols || C->num_cols != A->num_cols || z->len < A->num_cols || c->pend_eval.active)
     return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
-  ahead_cancel(c);
   Csr3 M;
   memset(&M, 0, sizeof M);
   uint32_t total = 0, most = 0;

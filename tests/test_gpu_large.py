@@ -539,51 +539,67 @@ def test_two_rounds_per_launch_match_reference_arithmetic(ctx, ell):
 
 
 @pytest.mark.parametrize("ell,ni", [(13, 5), (12, 20), (9, 24), (6, 3)])
-def test_trips_launched_ahead_of_their_challenges_give_the_same_rounds(ell, ni):
-    """Round 6: while one two-rounds trip of prove_cubic_batched runs, the kernel of the next is already enqueued and waits for its challenges on
-    a bell in host memory (internal.hpp AheadArm; option sumcheck.launch_ahead). An uninterrupted chain of trips — nothing else touches the context
-    between them, as in the prover — must return the same sums, coefficients, final claims and tables whether each kernel is launched with its
-    challenges (0), launched ahead and rung (1), or launched ahead and never rung (2: the test hook — every such kernel gives up after its 20 ms
-    and the trip is repeated the ordinary way). ell = 13 / 12 with 20 instances: the grids whose partial sums need a second kernel."""
-    import time
+def test_weighted_chain_of_two_round_trips_matches_reference_arithmetic(ell, ni):
+    """The weighted form of prove_cubic_batched (sumcheck.rs:287-393, the `coeffs` of 359-369 applied on the device, instances summed) as the prover
+    runs it: sp_sumcheck_eval_coeffs_batched, then an uninterrupted chain of two-bind trips of sp_sumcheck_bind2_eval_batched down to the final
+    claims, in one context with default options; all but the last instance share their C. After every call the weighted evaluations, the
+    mid-round that the returned cubic (M0, M3, T1, T2) predicts, and at the end the heads and four of the single-entry tables are compared with
+    the reference arithmetic in Python. 24 instances: the most that travel in the kernel arguments. (9, 24): the smallest shape whose partial
+    sums (4 blocks x 24 instances x 576 bytes) no longer fit the result page, so that k_reduce_partials18 runs, as it does for (13, 5) and
+    (12, 20); (6, 3): summed on the host. Odd ell: the last call binds once."""
     from spartan_amd import capi
     n = 1 << ell
     rng = random.Random(77000 + ell)
-    A0 = [fast_scalars(rng, n) for _ in range(ni)]; B0 = [fast_scalars(rng, n) for _ in range(ni)]
-    C0 = [fast_scalars(rng, n) for _ in range(2)]
+    A = [fast_scalars(rng, n) for _ in range(ni)]; B = [fast_scalars(rng, n) for _ in range(ni)]
+    C = [fast_scalars(rng, n) for _ in range(2)]
     w = fast_scalars(rng, ni)
     chal = [(rng.getrandbits(251), rng.getrandbits(250)) for _ in range(ell)]
-    results = {}
-    for mode in (0, 1, 2):
-        ctx = capi.Ctx(0)
-        ctx.set_option("testing.unlock", 1); ctx.set_option("sumcheck.launch_ahead", mode)
-        tA, tB, tC = [up(ctx, a) for a in A0], [up(ctx, b) for b in B0], [up(ctx, c) for c in C0]
-        hA = (vp * ni)(*[t.h for t in tA]); hB = (vp * ni)(*[t.h for t in tB])
-        hC = (vp * ni)(*[tC[0].h if k < ni - 1 else tC[1].h for k in range(ni)])   # all but the last instance share their C
-        ev = (ctypes.c_uint64 * 12)(); co = (ctypes.c_uint64 * 48)(); heads = (ctypes.c_uint64 * (4 * (2 * ni + 2)))()
+    half = pow(2, Q - 2, Q)
+    Cs = lambda k: C[0] if k < ni - 1 else C[1]   # all but the last instance share their C
+    comb = lambda: [sum(w[k] * e for k, e in enumerate(col)) % Q for col in zip(*[cubic_evals(A[k], B[k], Cs(k)) for k in range(ni)])]
+
+    def predicted(c12, r):   # E(t; r) from the weighted (M0, M3, T1, T2), as the host driver evaluates it
+        om = (1 - r) % Q
         out = []
-        assert capi.lib.sp_sumcheck_eval_coeffs_batched(ctx.h, hA, hB, hC, sz(ni), mont_bulk(w), ev, co) == 0
-        out.append((bytes(ev), bytes(co)))
-        length, k = n, 0
-        t0 = time.time()
-        while length >= 4:
-            r0, r1 = chal[k]; k += 1
-            length //= 4
-            assert capi.lib.sp_sumcheck_bind2_eval_batched(ctx.h, hA, hB, hC, sz(ni), fq1(r0), fq1(r1), mont_bulk(w), ev if length >= 2 else None,
-                                                           co if length >= 4 else None, heads if length == 1 else None) == 0
-            out.append((bytes(ev) if length >= 2 else b"", bytes(co) if length >= 4 else b"", bytes(heads) if length == 1 else b""))
-        dt = time.time() - t0
-        if length >= 2:  # an odd number of variables: the last round binds once
-            assert capi.lib.sp_sumcheck_bind2_eval_batched(ctx.h, hA, hB, hC, sz(ni), fq1(chal[k][0]), None, mont_bulk(w), None, None, heads) == 0
-            out.append(bytes(heads))
-        out.append(bytes(tA[0].download(1)) + bytes(tB[ni - 1].download(1)) + bytes(tC[0].download(1)) + bytes(tC[1].download(1)))
-        results[mode] = out
-        if mode == 1:
-            assert dt < 0.018, "a trip launched ahead waited for its 20 ms time-out: %.1f ms for %d trips" % (dt * 1e3, k)
-        for t in tA + tB + tC:
-            t.free()
-        ctx.close()
-    assert results[1] == results[0] and results[2] == results[0]
+        for t_ in range(3):
+            M0, M3, T1, T2 = c12[4 * t_:4 * t_ + 4]
+            M1 = ((T1 - T2) * half - M3) % Q; M2 = ((T1 + T2) * half - M0) % Q
+            out.append((M0 * om ** 3 + M1 * om ** 2 * r + M2 * om * r ** 2 + M3 * r ** 3) % Q)
+        return out
+    ctx = capi.Ctx(0)
+    tA, tB, tC = [up(ctx, a) for a in A], [up(ctx, b) for b in B], [up(ctx, c) for c in C]
+    hA = (vp * ni)(*[t.h for t in tA]); hB = (vp * ni)(*[t.h for t in tB])
+    hC = (vp * ni)(*[tC[0].h if k < ni - 1 else tC[1].h for k in range(ni)])
+    ev = (ctypes.c_uint64 * 12)(); co = (ctypes.c_uint64 * 48)(); heads = (ctypes.c_uint64 * (4 * (2 * ni + 2)))()
+    wm = mont_bulk(w)
+    assert capi.lib.sp_sumcheck_eval_coeffs_batched(ctx.h, hA, hB, hC, sz(ni), wm, ev, co) == 0
+    assert from_mont_bulk(ev, 3) == comb()
+    length, k = n, 0
+    while length >= 4:
+        c12 = from_mont_bulk(co, 12)
+        r0, r1 = chal[k]; k += 1
+        A = [bind(a, r0) for a in A]; B = [bind(b, r0) for b in B]; C = [bind(c, r0) for c in C]
+        assert predicted(c12, r0) == comb(), length          # the cubic predicts the round after the bind at r0
+        A = [bind(a, r1) for a in A]; B = [bind(b, r1) for b in B]; C = [bind(c, r1) for c in C]
+        length //= 4
+        assert capi.lib.sp_sumcheck_bind2_eval_batched(ctx.h, hA, hB, hC, sz(ni), fq1(r0), fq1(r1), wm, ev if length >= 2 else None,
+                                                       co if length >= 4 else None, heads if length == 1 else None) == 0
+        assert len(tA[0]) == length and len(tB[ni - 1]) == length and len(tC[0]) == length and len(tC[1]) == length
+        if length >= 2:
+            assert from_mont_bulk(ev, 3) == comb(), length
+    if length >= 2:  # an odd number of variables: the last round binds once
+        r0 = chal[k][0]
+        A = [bind(a, r0) for a in A]; B = [bind(b, r0) for b in B]; C = [bind(c, r0) for c in C]
+        assert capi.lib.sp_sumcheck_bind2_eval_batched(ctx.h, hA, hB, hC, sz(ni), fq1(r0), None, wm, None, None, heads) == 0
+    want = []
+    for i in range(ni):
+        want += [A[i][0], B[i][0]]
+    assert from_mont_bulk(heads, 2 * ni + 2) == want + [C[0][0], C[1][0]]
+    got = [from_mont_bulk(t.download(1), 1) for t in (tA[0], tB[ni - 1], tC[0], tC[1])]
+    assert got == [A[0], B[ni - 1], C[0], C[1]]
+    for t in tA + tB + tC:
+        t.free()
+    ctx.close()
 
 
 @pytest.mark.parametrize("ell,nbind", [(5, 2), (4, 2), (3, 2), (4, 1), (3, 1), (2, 1), (3, 0), (2, 0), (1, 0), (6, 2)])

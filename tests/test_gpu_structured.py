@@ -164,7 +164,7 @@ def test_ops_heavy_17_matches_oracle(P, ctx, orc, sides):
 # the settings whose code paths depend on table lengths: here the ops circuits are 2^17 long while the mem circuits (2^12) are on the
 # short-table and host-tail paths — with the synthetic instance of test_every_ab_switch_gives_the_same_proof it is the other way round
 LENGTH_SETTINGS = [{}, {"spark.eq_factor": 0}, {"spark.hash_fuse": 0}, {"spark.prod_layer2": 0},
-                   {"sumcheck.double_round_max_len": 0, "sumcheck.host_tail": 0}, {"sumcheck.launch_ahead": 2}, {"msm.form": 3},
+                   {"sumcheck.double_round_max_len": 0, "sumcheck.host_tail": 0}, {"msm.form": 3},
                    {"msm.lds_bits": 10, "msm.form": 1}]
 
 
