@@ -1,6 +1,6 @@
 // Micro-benchmark: the GATHER ceiling of the fixed-base row MSM (VERDICT r3 #2 / "missing" #6).
 //
-// The row MSM (spartan_amd/csrc/core.hip: k_msm_rows) performs, per mixed addition, one gather of a 96-byte affine Niels entry
+// The row MSM (spartan_amd/csrc/msm_rows.hip: k_msm_rows) performs, per mixed addition, one gather of a 96-byte affine Niels entry
 // from a window table of 27 GB (1025 points, 15-bit windows) or 61 GB (4098 points, 14-bit windows). A wavefront's 64 lanes are 64
 // ROWS of the same column, so the 64 gathers of a step fall into ONE (point, window) sub-table (tent entries: 1.5 MiB at 15 bits,
 // 0.75 MiB at 14) at uniformly random entries. This program issues exactly that access pattern with NO arithmetic behind it and

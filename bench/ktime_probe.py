@@ -1,6 +1,6 @@
 """Where does the time of a launch-sized kernel go? Runs the two latency-bound kernels that dominate the proof's GPU time —
 k_cubic_bind2_eval (the two-rounds-per-trip batched sum-check kernel, spark.hip) and k_ipa_round (one inner-product round,
-core.hip) — from the DIAGNOSTIC build of the library (make -C spartan_amd/csrc ktime: -DSP_KTIME adds wall-clock stamps of
+commit.hip) — from the DIAGNOSTIC build of the library (make -C spartan_amd/csrc ktime: -DSP_KTIME adds wall-clock stamps of
 the first workgroup at the phase boundaries) and prints, per phase, the time between stamps next to the host-side time of
 the whole call. 100 MHz device wall clock: 10 ns resolution.
 Run on the GPU box from the repo root:  python bench/ktime_probe.py   (sets the library option debug.ktime through SPARTAN_OPTIONS)"""

@@ -1,4 +1,4 @@
-"""A/B of the row MSM's forms on the launch shapes of a 2^s proof: the wide-window gathered forms (core.hip) against the LDS-staged
+"""A/B of the row MSM's forms on the launch shapes of a 2^s proof: the wide-window gathered forms (msm_rows.hip) against the LDS-staged
 small-window form (msm_lds.hip), same process, same generator set (built with both table kinds: option msm.lds_bits), the form chosen per
 launch by option msm.form. Prints ms per launch (best of 6) and G mixed additions/s; the two forms' commitments must be equal (each is
 also checked against the oracle by tests/msm_forms_worker.py).

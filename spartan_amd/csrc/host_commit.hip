@@ -27,7 +27,7 @@ struct StreamTables {
   std::map<uint32_t, std::unique_ptr<Niels[]>> tab;
 };
 std::mutex g_reg_mu;
-std::map<const void*, std::shared_ptr<StreamTables>> g_reg;  // keyed by the generator set's cache entry (core.hip)
+std::map<const void*, std::shared_ptr<StreamTables>> g_reg;  // keyed by the generator set's cache entry (gens.hip)
 
 // window table of one point: entry (w, m) = m * 2^(c w) * P for m = 1..2^(c-1), affine Niels form (msm_tidx layout, pt = 0)
 std::unique_ptr<Niels[]> build_table(const uint8_t comp[32]) {

@@ -74,7 +74,7 @@ struct sp_ctx {
   hipStream_t stream_low = nullptr;  // a second low-priority stream: short streaming jobs (sp_sparse_evaluate_begin) that must not queue behind a background MSM
   bool device_encode;     // SPARTAN_DEVICE_ENCODE: small commitments are encoded by the device too (100 us instead of 3 us each)
   int bg_blocks;          // workgroups of a background MSM (one per CU, fewer than CUs); 0 = plain launches
-  int bg_inflight = 0;    // background commits queued and not yet collected: while one runs, foreground commits keep the strip form (core.hip, msm_plan)
+  int bg_inflight = 0;    // background commits queued and not yet collected: while one runs, foreground commits keep the strip form (commit.hip, msm_plan)
   size_t bg_lds;          // dynamic LDS each of them claims (a whole CU's)
   unsigned* q_heads = nullptr;  // queue form of the row MSM (msm_queue.hip): a ring of MSMQ_BLOCKS counter blocks, one per launch in flight
   unsigned q_next = 0;
@@ -97,7 +97,7 @@ struct sp_ctx {
   uint32_t done_seq;
   uint32_t* done_counter = nullptr;  // DoneSig::counter
   long long* ktime = nullptr;        // DoneSig::kt (SP_KTIME builds with SPARTAN_KTIME set)
-  uint8_t *vm_pinned = nullptr, *vm_dstage = nullptr;  // sp_vecmat_dev's own staging pair for L: the call does not wait (core.hip: vm_stage)
+  uint8_t *vm_pinned = nullptr, *vm_dstage = nullptr;  // sp_vecmat_dev's own staging pair for L: the call does not wait (ctx.hip: vm_stage)
   size_t vm_cap = 0;
   hipEvent_t vm_ev = nullptr;
   struct { bool active; int kind; size_t nblk; bool on_host; uint32_t seq; } pend_eval = {false, 0, 0, false, 0};  // sp_sumcheck_bind_eval_start .. _collect
@@ -122,7 +122,7 @@ struct sp_ctx {
 struct sp_gens {
   sp_ctx* ctx;
   size_t n;
-  Niels* table;  // [n][nwin][tent]; owned by the process-wide table cache (core.hip), shared between contexts
+  Niels* table;  // [n][nwin][tent]; owned by the process-wide table cache (gens.hip), shared between contexts
   MsmGeom geom;  // window geometry these tables were built with
   bool prefer_lds = false;  // the set's wide tables came out narrow (<= 10 bits: HBM was short): its row commits take the LDS-staged form by default
   bool derived = false;  // the points came out of the library's own hash-to-curve (sp_gens_from_uniform: MultiCommitGens::new), not from a caller's list
@@ -144,7 +144,7 @@ struct sp_table {
   Fq* alt;         // second pool buffer for out-of-place binds of tables shared between kernel instances
   size_t alt_bytes;
 };
-// the 32-byte encodings of a generator set's points (kept by the process-wide table cache, core.hip); *n = number of points
+// the 32-byte encodings of a generator set's points (kept by the process-wide table cache, gens.hip); *n = number of points
 extern "C" const uint8_t* gens_compressed_bytes(const sp_gens* g, size_t* n);
 void host_commit_forget(const void* cache_entry);  // host_commit.hip: drop the host-side window tables of a freed set
 int32_t table_ensure_alt(sp_table* t, size_t elems);
@@ -249,9 +249,25 @@ uint32_t sync_post(sp_ctx* c);               // queue the completion flag behind
 int32_t sync_wait(sp_ctx* c, uint32_t seq);  // spin until that flag has arrived
 // Enqueue (no wait) the lookups + tree of a commitment with <= 256 (column, window) pairs per row and rows <= 8 on `st`:
 // scalars S[rows][cols] and generator indices are staged in the host-mapped input page, the row sums (extended points)
-// land at sums_out (device-visible). core.hip.
+// land at sums_out (device-visible). commit.hip.
 extern "C" int32_t msm_small_enqueue(sp_ctx* c, hipStream_t st, const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows,
                                      uint8_t* sums_out);
+// one inner-product round in one launch (k_ipa_round, commit.hip; driven by ipa.hip)
+struct IpaRoundArgs {
+  const Fq *a, *b, *s;         // vectors before the pending fold (a, b: 2 n_cur entries when fold; s: n0 / (2 n_cur) entries), else current
+  Fq *a_new, *b_new, *s_new;   // the vectors of this round, written when fold != 0
+  size_t n_cur, n0, g_off;
+  int fold;
+  Fq u, u_inv;
+  Fq u2, u2_inv;               // u^2, u^-2: the lookups' scalar a'[i] s'[p] in two multiplications (k_ipa_round)
+  Pt10* part;                  // [2][nblk]
+  uint32_t* counters;          // [2], zero between launches
+  Pt* sums_out;                // host page: the two row sums
+  Fq* dots_out;                // host page: [nd][8] partial quarter dot products
+  unsigned nblk, nd;
+};
+// enqueue the round on the main stream; unified != 0: the tree with the complete addition formula. *sig_out: what to wait for (sig_wait)
+int32_t ipa_round_launch(sp_ctx* c, const sp_gens* g, IpaRoundArgs* A, DoneSig* sig_out, int unified);
 // host-mapped page layout: [0, HMAP_GEN) inputs of calls that wait for their kernels, [HMAP_GEN, HMAP_IN) a ring of
 // EQ_SLOTS slots for the challenge vectors of sp_eq_expand (which does not wait: the table is consumed by later launches
 // on the same stream), [HMAP_IN, HMAP_SIZE) kernel results
@@ -264,11 +280,20 @@ static inline Fq* partials_dst(sp_ctx* c, size_t nblk, int K) { return 32 * nblk
 int32_t fetch_small(sp_ctx* c, void* hdst, size_t bytes);
 int32_t sync_spin(sp_ctx* c);  // wait for everything queued on the context stream                 // stream sync + copy out of the result area
 int32_t reduce_and_fetch(sp_ctx* c, Fq* partials, size_t nblk, int K, uint64_t* out);
-// fixed-base MSM core: Z on device (row stride in elements), optional idx / blinds (device); out on host, synchronous
+constexpr size_t SP_HOST_ENCODE_ROWS = 8;  // commitments of up to this many rows are encoded by the host core (commit.hip, k_msm_reduce)
+// fixed-base MSM core (commit.hip): Z on device (row stride in elements), optional idx / blinds (device); out on host, synchronous
 extern "C" int32_t msm_launch(sp_ctx* c, const sp_gens* g, const Fq* dZ, size_t z_stride, size_t rows, size_t cols, size_t g_off,
                               const uint32_t* didx, const Fq* dblinds, size_t h_idx, uint8_t* out_host, size_t idx_row_stride = 0,
                               Pt* points_out = nullptr /* rows <= 8: the row sums as extended points instead of encodings */);
 // idx_row_stride: 0 = every row uses idx[0..cols); otherwise row r uses idx[r*idx_row_stride ..] (latency path only)
+
+// gathered wide-window forms of the row MSM (msm_rows.hip): enqueue of the lookups, partial[row][P] extended points (the reduction is the
+// caller's). WINDOWS: one lookup per thread, P = (cols + blind) x windows; STRIP: P strips of `strip` columns (on a background stream the
+// persistent launch); FLAT: the balanced form, P runs per row, cut for msm_flat_slots() resident workgroups
+enum MsmRowsForm { MSM_ROWS_WINDOWS = 0, MSM_ROWS_STRIP, MSM_ROWS_FLAT };
+size_t msm_flat_slots();
+void msm_rows_enqueue(sp_ctx* c, hipStream_t st, const sp_gens* g, const Fq* dZ, size_t z_stride, size_t rows, size_t cols, size_t g_off,
+                      const uint32_t* didx, const Fq* dblinds, size_t h_idx, Pt* partial, int form, size_t strip, size_t P);
 
 // LDS-staged small-window row MSM (msm_lds.hip): runs per row-block for `wg_slots` resident workgroups; enqueue of the lookups
 // (partial[row][nb] extended points; the reduction is the caller's, as for the other forms). grid_limit != 0: persistent form on that many workgroups

@@ -17,7 +17,7 @@ struct sp_ipa {
   uint32_t* idx_lr;           // device: [2][n0/2+2] per-row generator lists of the current round
   uint32_t* counters;         // device: [2] row tickets of k_ipa_round (zero between launches)
   size_t bytes;
-  // one-launch rounds (k_ipa_round, core.hip): c_L, c_R of the first round (k_ipa_init) and the eight quarter dot products the
+  // one-launch rounds (k_ipa_round, commit.hip): c_L, c_R of the first round (k_ipa_init) and the eight quarter dot products the
   // last round left behind, from which the next c_L, c_R follow once the fold challenge is recorded
   Fq c0[2], dots[8];
   bool have_c0, have_dots;
@@ -33,21 +33,6 @@ struct sp_ipa {
   Fq fin_a[2], fin_b[2];
   Pt fin_raw[2];
 };
-// core.hip
-struct IpaRoundArgs {
-  const Fq *a, *b, *s;
-  Fq *a_new, *b_new, *s_new;
-  size_t n_cur, n0, g_off;
-  int fold;
-  Fq u, u_inv;
-  Fq u2, u2_inv;               // u^2, u^-2: the lookups' scalar a'[i] s'[p] in two multiplications (k_ipa_round)
-  Pt10* part;
-  uint32_t* counters;
-  Pt* sums_out;
-  Fq* dots_out;
-  unsigned nblk, nd;
-};
-extern "C" int32_t ipa_round_launch(sp_ctx* c, const sp_gens* g, IpaRoundArgs* A, DoneSig* sig_out, int unified);
 static unsigned ipa_c0_blocks(size_t n) { return (unsigned)((n / 2 + 511) / 512); }  // k_ipa_init: one workgroup per 512 index pairs
 static bool ipa_fused(const sp_ctx* c) { return c->opt.v[OPT_IPA_FUSED] != 0; }  // A/B switch (0): three launches + flag kernel per round (the round-2 path)
 
@@ -356,7 +341,7 @@ static int32_t ipa_round_fused(sp_ipa* ipa, const uint64_t blind_L[4], const uin
   SPCHK(hrc);
   const Pt* sums = (const Pt*)hres(c);
   if (fp_is_zero(sums[0].Z) || fp_is_zero(sums[1].Z)) {
-    // no valid point has Z = 0: an addition of the two-multiplication tree met one of its exceptional pairs (core.hip, pt10_tree_quad_ded:
+    // no valid point has Z = 0: an addition of the two-multiplication tree met one of its exceptional pairs (tree.hpp, pt10_tree_quad_ded:
     // a generator list that repeats a point). The round is run again with the unified formula: same inputs, same outputs otherwise.
     if (!c->opt.v[OPT_IPA_RERUN_EXCEPTIONAL]) return SP_EHIP;  // test-only: shows that a test input reached this path
     DoneSig sig2;

@@ -23,7 +23,7 @@ constexpr size_t MSM_PT_ENTRIES = (size_t)MSM_NWIN * MSM_TENT;
 static_assert(MSM_WBITS >= 4 && MSM_WBITS <= 15, "window width");
 
 // The window width is a property of a generator set (sp_gens), chosen when its tables are built: the widest c whose tables
-// fit the HBM budget (core.hip, choose_wbits) — 15 bits (17 additions per scalar) for the generators of a 2^20 instance,
+// fit the HBM budget (gens.hip, choose_wbits) — 15 bits (17 additions per scalar) for the generators of a 2^20 instance,
 // 13 for a 2^22 one, less for larger sets. The constants above are the default geometry (and the one the host-side
 // arithmetic tests use).
 //

@@ -1,7 +1,7 @@
 // spartan_amd: the LDS-staged small-window form of the fixed-base row MSM (BASELINE.json north_star: "scalars and generator
 // windows staged in LDS ... built on gfx950 wavefront ballot/shuffle primitives").
 //
-// Replaces the same reference code as the wide-window forms of core.hip — the rows of DensePolynomial::commit_inner
+// Replaces the same reference code as the wide-window forms of msm_rows.hip — the rows of DensePolynomial::commit_inner
 // (src/dense_mlpoly.rs:164-177), i.e. [Scalar]::commit = vartime_multiscalar_mul over MultiCommitGens + blind * h
 // (src/commitments.rs:80-92, src/group.rs:98-117) — with the opposite trade: the wide form spends HBM (15-bit windows, 118 GB of
 // tables at 2^20, one random 128-byte gather per mixed addition) to do 17-19 additions per scalar; this form keeps 10-bit signed
@@ -17,11 +17,11 @@
 //   * HBM sees a sequential stream: rows/1024 x cols x 26 x 48 KB per commit (1.3 GB for the 2^20 witness, ~1.3 TB/s while the
 //     kernel runs) instead of 107-126 B of random gather per addition at 88-93 % L2 miss.
 //
-// The unit of work is the tile, and a row-block's cols x nwin tiles are cut into nb equal runs (as in the balanced form of core.hip),
+// The unit of work is the tile, and a row-block's cols x nwin tiles are cut into nb equal runs (as in the balanced form of msm_rows.hip),
 // so a launch is exactly as many workgroups as the chip (or the background share of it) holds and all finish together; a run may start
 // in the middle of a scalar (the signed recoding's carry into its first window is rebuilt from the lower windows).
 // Scalars leave Montgomery form once per column (one Montgomery reduction per 26 additions); the next column's scalar is requested
-// one column ahead. Partial sums go to partial[row][run]; the cross-run reduction and the encodes are the existing kernels of core.hip
+// one column ahead. Partial sums go to partial[row][run]; the cross-run reduction and the encodes are the existing kernels of commit.hip
 // (DPP point-addition trees, k_msm_reduce / k_pt_encode).
 #include "internal.hpp"
 

@@ -4,7 +4,7 @@
 // [Scalar]::commit = vartime_multiscalar_mul over MultiCommitGens + blind * h (src/commitments.rs:80-92, src/group.rs:98-117), and
 // Derefs::commit (src/sparse_mlpoly.rs:64-67) — over the same wide-window tables (15/14-bit signed windows, one 128-byte line per entry).
 //
-// What the earlier forms measured: the strip form (core.hip) keeps its table entries in flight in REGISTERS (48 of
+// What the earlier forms measured: the strip form (msm_rows.hip) keeps its table entries in flight in REGISTERS (48 of
 // its 164 VGPRs) and still waits on memory 42-47 % of its wave cycles; the ring form (msm_lds.hip) moved the gathers to LDS-DMA issued by
 // loader wavefronts and reached 0.75-0.82 of the mixed-addition ceiling, but its unit of scheduling is a 1024-thread workgroup in
 // lock-step (one barrier per tile, ~1 ms of indivisible work per CU) — faster per launch, no faster in the proof. Here:
@@ -27,7 +27,7 @@
 //     (ballot), the stream jumps to the next column without issuing the remaining gathers (short scalars: SNARK::encode's addresses
 //     and timestamps, src/sparse_mlpoly.rs:483-503).
 //
-// Partial sums go to partial[row][run]; the cross-run reduction and the encodes are the existing kernels of core.hip.
+// Partial sums go to partial[row][run]; the cross-run reduction and the encodes are the existing kernels of commit.hip.
 #include "internal.hpp"
 
 struct MsmQArgs {

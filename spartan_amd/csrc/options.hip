@@ -71,7 +71,7 @@ SpOptions sp_default_options() {  // a copy, taken under the lock: sp_ctx_set_op
   defaults_init_locked();
   return g_defaults;
 }
-void ctx_options_changed(sp_ctx* c, int which);  // core.hip: derived state (background workgroups, ...)
+void ctx_options_changed(sp_ctx* c, int which);  // ctx.hip: derived state (background workgroups, ...)
 
 extern "C" {
 int32_t sp_ctx_set_option(sp_ctx* c, const char* key, const char* value) {

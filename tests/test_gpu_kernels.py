@@ -35,7 +35,7 @@ def test_gens_from_uniform_matches_oracle(ctx, orc):
 
 
 def test_generator_tables_are_shared_between_contexts(orc):
-    """window tables are built once per (device, generator bytes) and reference-counted across contexts (core.hip gens_build)"""
+    """window tables are built once per (device, generator bytes) and reference-counted across contexts (gens.hip gens_build)"""
     import hashlib, time
     from spartan_amd import capi
     from tests.test_oracle_pins import BASEPOINT
@@ -91,7 +91,7 @@ def gens301(ctx, orc):
     g.free()
 
 
-# every launch plan of msm_launch (core.hip): lookups+tree in one launch / + second reduce (rows <= 8, host encode);
+# every launch plan of msm_launch (commit.hip): lookups+tree in one launch / + second reduce (rows <= 8, host encode);
 # windowed one-pass and two-pass trees with per-block and one-lane-per-row encodes; row-strip kernel with and without the
 # XCD-aware tile order
 @pytest.mark.parametrize("rows,cols,blind", [(1, 300, True), (8, 300, False), (16, 128, True), (100, 128, False), (256, 128, True),
@@ -110,7 +110,7 @@ def test_commit_rows_launch_plans_match_oracle(ctx, orc, gens301, rows, cols, bl
 
 @pytest.mark.parametrize("wbits", [5, 6, 8, 10, 12, 13, 14, 15, -17, -18, -19, -20, -21, -22, -24, -26, -32])
 def test_commit_rows_at_every_window_width(ctx, orc, wbits, monkeypatch):
-    """the window geometry is a property of the generator set, chosen at upload (core.hip choose_geom): every uniform width (option
+    """the window geometry is a property of the generator set, chosen at upload (gens.hip choose_geom): every uniform width (option
     msm.wbits) and every number of MIXED-width windows (option msm.windows, the negative parameters: 17 = 1 x 14 + 16 x 15 bits, 18 = 16 x
     14 + 2 x 15, ... 32 = 2 x 7 + 30 x 8: msm.hpp) gives the same commitments through every launch plan (one-launch small, windowed trees,
     row strips, the queue form, the indexed lookups of the inner-product argument)"""
@@ -150,7 +150,7 @@ def test_commit_rows_at_every_window_width(ctx, orc, wbits, monkeypatch):
 
 
 def test_narrow_wide_tables_switch_the_set_to_the_lds_staged_form(ctx, orc):
-    """The default per generator set (core.hip gens_build; profiles/r5_ab_msm_forms.txt): a set whose gathered tables come out at <= 10 bits — HBM
+    """The default per generator set (gens.hip gens_build; profiles/r5_ab_msm_forms.txt): a set whose gathered tables come out at <= 10 bits — HBM
     was short (here: a 1 GB table budget) — also gets the packed 10-bit tables and its row commitments of >= 512 rows run the LDS-staged form
     (msm_lds.hip); msm.form = 3 keeps the gathered forms. Same commitments either way, equal to the oracle's. A width FORCED with msm.wbits
     gets exactly the tables it asks for and no second set."""
@@ -446,6 +446,74 @@ def test_background_commit_overlaps_and_matches(ctx, orc, gens40):
     assert orc.orc_commit_rows(g[32 * 2:32 * (2 + cols)], sz(cols), g[32 * 39:], mont_array(Z[:4 * cols]), sz(4), sz(cols), None, want) == 0
     assert got[:128] == bytes(want)
     t.free(); ta.free(); tb.free()
+
+
+def test_commit_job_entry_points_match_the_synchronous_commit(ctx, orc, gens301):
+    """sp_commit_rows_dev_begin / _dev_start / _upload_start + sp_job_wait against the oracle and against sp_commit_rows_dev on the same
+    table, at the smallest shapes that reach each launch form of the plan (commit.hip, msm_plan; lookup form: rows x (cols + blind) x
+    windows <= 2^19, which the test confirms for the windows the set got):
+      (9, 16)     the lookup form (k_msm_windows + per-row encode) through all three; upload_start takes copy-then-commit
+      (200, 300)  the strip form: past 2^19, under 256 rows and no multiple of 256 (dev_begin: the persistent background launch;
+                  upload_start: copy-then-commit, the rows are no multiple of 4 x 256)
+      (256, 300)  the queue form; through dev_begin in the co-resident role, and a dev_start queued while that background job is
+                  uncollected meets it in flight (the co-resident role on the main stream); upload_start: copy-then-commit
+      (1024, 64)  upload_start in the default four chunks: the balanced form, one 256-row block per chunk, one reduction over all rows
+                  and the one-lane-per-row encode; dev_start and dev_begin: the queue form
+    dev_start and upload_start with and without blinds (dev_begin takes none). A job collected into a sink leaves the context usable."""
+    from spartan_amd import capi
+    L = capi.lib
+    nwin = gens301.windows()
+    assert ctx.get_option("msm.form") == 0 and ctx.get_option("upload.chunks") == 4 and ctx.get_option("upload.overlap") == 1
+    assert 9 * 17 * nwin <= 1 << 19 and min(200 * 300, 256 * 300, 1024 * 64) * nwin > 1 << 19     # the lookup form / the throughput forms
+    g = gens301.compressed
+    rng = random.Random(4711)
+
+    def wait(job, rows):
+        out = (ctypes.c_uint8 * (32 * rows))()
+        assert L.sp_job_wait(job, out) == 0
+        return bytes(out)
+
+    def dev_begin(t, rows, cols):
+        job = vp()
+        assert L.sp_commit_rows_dev_begin(ctx.h, gens301.h, sz(0), t.h, sz(0), sz(rows), sz(cols), ctypes.byref(job)) == 0
+        return job
+
+    def dev_start(t, rows, cols, bl):
+        job = vp()
+        assert L.sp_commit_rows_dev_start(ctx.h, gens301.h, sz(0), sz(300), t.h, sz(0), sz(rows), sz(cols), bl, ctypes.byref(job)) == 0
+        return job
+
+    def upload_start(src, rows, cols, bl):
+        t = capi.Table.alloc(ctx, rows * cols)
+        job = vp()
+        assert L.sp_commit_rows_upload_start(ctx.h, gens301.h, sz(0), sz(300), t.h, sz(0), src, sz(rows), sz(cols), bl, ctypes.byref(job)) == 0
+        got = wait(job, rows)
+        assert bytes(t.download()) == bytes(src)      # the rows are left in the table
+        t.free()
+        return got
+
+    for rows, cols in [(9, 16), (200, 300), (256, 300), (1024, 64)]:
+        Z = mont_array(rand_scalars(rng, rows * cols, "uniform"))
+        blinds = mont_array(rand_scalars(rng, rows, "uniform"))
+        want = {}
+        for bl in (None, blinds):     # the references, once per shape
+            w = (ctypes.c_uint8 * (32 * rows))()
+            assert orc.orc_commit_rows(g[:32 * cols], sz(cols), g[32 * 300:32 * 301], Z, sz(rows), sz(cols), bl, w) == 0
+            want[bl is not None] = bytes(w)
+        t = capi.Table.upload(ctx, Z, rows * cols)
+        for bl in (None, blinds):
+            assert gens301.commit_rows(t, rows, cols, bl, g_off=0, h_idx=300) == want[bl is not None], (rows, cols, "dev")
+        bg = dev_begin(t, rows, cols)
+        fg = dev_start(t, rows, cols, blinds)          # queued while the background job is uncollected
+        assert wait(fg, rows) == want[True], (rows, cols, "dev_start next to a background job")
+        assert wait(bg, rows) == want[False], (rows, cols, "dev_begin")
+        for bl in (None, blinds):
+            assert wait(dev_start(t, rows, cols, bl), rows) == want[bl is not None], (rows, cols, "dev_start")
+            assert upload_start(Z, rows, cols, bl) == want[bl is not None], (rows, cols, "upload_start")
+        # jobs collected into a sink: the synchronous commit that follows on the same context still matches
+        wait(dev_begin(t, rows, cols), rows); wait(dev_start(t, rows, cols, blinds), rows)
+        assert gens301.commit_rows(t, rows, cols, blinds, g_off=0, h_idx=300) == want[True], (rows, cols, "after the jobs")
+        t.free()
 
 
 def test_dot3_many_matches_reference_arithmetic(ctx):

@@ -366,7 +366,7 @@ def _ipa_against_folded_generators(ctx, orc, n, comp, a, b, rng):
 
 
 def test_inner_product_argument_n4096_matches_folded_generators(ctx, orc):
-    """n = 4096: the opening size of a 2^20 proof (two trees of ~8 levels per row and round, core.hip k_ipa_round)."""
+    """n = 4096: the opening size of a 2^20 proof (two trees of ~8 levels per row and round, commit.hip k_ipa_round)."""
     n = 4096
     rng = random.Random(4096)
     comp = gens_bytes(orc, n + 1, b"gens_ipa_test")   # G[0..n), Q = P[n], H = P[n+1]
@@ -375,7 +375,7 @@ def test_inner_product_argument_n4096_matches_folded_generators(ctx, orc):
 
 @pytest.mark.parametrize("case", ["repeated_generators_equal_scalars", "repeated_generators_opposite_scalars", "zero_vector", "sparse_vector", "plain_small"])
 def test_inner_product_argument_exceptional_sums(ctx, orc, case):
-    """The tree of k_ipa_round adds with the dedicated (two-multiplication) formula, which is not complete (core.hip,
+    """The tree of k_ipa_round adds with the dedicated (two-multiplication) formula, which is not complete (tree.hpp,
     pt10_tree_quad_ded): the neutral element is kept away from it by marks, P = Q collapses to the all-zero quadruple and the host
     re-runs the round with the unified formula. The cases that reach those paths, against the reference's folded-generator algorithm:
     a generator list that repeats points under equal scalars (two sub-trees with limb-identical sums: the re-run), under opposite
