@@ -892,6 +892,7 @@ constexpr size_t TAIL_OFF = 12288, TAIL_MAX_INST = 21;  // the <= 8-entry tables
 struct Bind2Shape {
   size_t n2, nblk;
   bool host, tail;
+  bool spill;  // reduced by kernel and 18 sums x ninst exceed the result area (ninst > 56): they stay in the scratch buffer, behind the partials
 };
 static Bind2Shape bind2_shape(size_t len, int nbind, size_t ninst, bool want_tables) {
   Bind2Shape s;
@@ -900,6 +901,7 @@ static Bind2Shape bind2_shape(size_t len, int nbind, size_t ninst, bool want_tab
   s.nblk = (ng + 7) / 8;
   s.host = 32 * 18 * s.nblk * ninst <= HOST_SUM_BYTES;
   s.tail = want_tables && s.n2 >= 2 && s.n2 <= 8 && ninst <= TAIL_MAX_INST && s.host && s.nblk == 1;
+  s.spill = !s.host && 32 * 18 * ninst > HMAP_SIZE - HMAP_IN;
   return s;
 }
 // enqueue the kernel(s) of one trip on the main stream
@@ -915,7 +917,8 @@ static void bind2_enqueue(sp_ctx* c, const Bind2Inline& IN, bool inl, const Fq* 
   }
   if (!sh.host) {
     ProfScope ps(c, PF_REDUCE, 32.0 * 18 * (double)(sh.nblk * ninst));
-    hipLaunchKernelGGL(k_reduce_partials18, dim3((unsigned)ninst), dim3(256), 0, c->stream, (const Fq*)partials, sh.nblk, (Fq*)hres(c), sig);
+    hipLaunchKernelGGL(k_reduce_partials18, dim3((unsigned)ninst), dim3(256), 0, c->stream, (const Fq*)partials, sh.nblk,
+                       sh.spill ? partials + 18 * sh.nblk * ninst : (Fq*)hres(c), sig);
   }
 }
 // shared by the entry points below: one trip of k_cubic_bind2_eval, the 18 sums per instance brought to the host
@@ -959,18 +962,21 @@ static int32_t bind2_launch(sp_ctx* c, sp_table* const* A, sp_table* const* B, s
   const Bind2Shape sh = bind2_shape(len, nbind, ninst, out_tables != nullptr);
   const Fq z = fq_zero();
   SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * 18 * (sh.nblk + 1) * ninst));
-  const DoneSig sig = sig_make(c, sh.host ? sh.nblk * ninst : ninst);  // raised by the last kernel of the trip
+  const DoneSig sig = sh.spill ? sig_none() : sig_make(c, sh.host ? sh.nblk * ninst : ninst);  // raised by the last kernel of the trip
   bind2_enqueue(c, IN, inl, dweights, len, nbind, r0 ? limbs(r0) : z, r1 ? limbs(r1) : z, ninst, sh, sig);
   // the tables as this trip leaves them (host bookkeeping: the kernels are stream-ordered)
   if (do_bind) {
     for (size_t k = 0; k < ninst; k++) { A[k]->len = n2; B[k]->len = n2; }
     for (sp_table* t : distinctC) table_swap_to_alt(t, n2);
   }
-  SPCHK(sig_wait(c, sig));
   std::vector<Fq> sums(18 * ninst);
-  if (!sh.host) {
+  if (sh.spill) {  // more than the result area holds: from the slot behind the partials (scratch has nblk + 1 per instance)
+    SPCHK(fetch_out(c, (const Fq*)c->scratch + 18 * sh.nblk * ninst, sums.data(), 32 * 18 * ninst));
+  } else if (!sh.host) {
+    SPCHK(sig_wait(c, sig));
     memcpy(sums.data(), hres(c), 32 * 18 * ninst);
   } else {
+    SPCHK(sig_wait(c, sig));
     const Fq* p = (const Fq*)hres(c);
     for (size_t i = 0; i < ninst; i++)
       for (int k = 0; k < 18; k++) {

@@ -1,5 +1,7 @@
 """Direct parity tests of the C-ABI entry points at the sizes where the THROUGHPUT launch plans are selected (the
-small-shape tests in test_gpu_kernels.py reach only the latency forms): >= 2^17 elements for the F_q streaming kernels
+small-shape tests in test_gpu_kernels.py reach only the latency forms; the small shapes of the SPARK family - spark.hip's batched
+sum-check, product trees, hash layers and reductions on field edge values, at every boundary of their dispatch - are in
+test_gpu_spark_edges.py): >= 2^17 elements for the F_q streaming kernels
 (k_eq_outer, k_cubic_*_batched, k_sc_bind_eval, k_dot_many, k_dot3, k_spmv, k_eval_table, k_sparse_eval, k_hash_layer),
 n = 4096 for the inner-product argument, and the full 1024 x 1024 witness-sized commit on every row (k_msm_rows with the
 XCD tile order, and the persistent half-chip k_msm_rows_bg).
@@ -642,8 +644,6 @@ def test_short_tables_are_handed_over_with_the_round(ctx, ell, nbind):
     else:
         assert tables[0] == 0xFFFFFFFFFFFFFFFF
     for t in tA + tB + [tCpar] + tCseq:
-        t.free()
-    for t in tA + tB + tCseq + [tCpar]:
         t.free()
 
 
