@@ -221,14 +221,17 @@ int32_t sp_table_copy(sp_ctx* ctx, sp_table* dst, size_t dst_off, const sp_table
 size_t sp_table_len(const sp_table* t); /* current (bound) length */
 void sp_table_free(sp_table* t);
 
-/* EqPolynomial::evals (dense_mlpoly.rs:68-84): chi_b(r) for all b in {0,1}^ell, r[0] <-> MSB. */
+/* EqPolynomial::evals (dense_mlpoly.rs:68-84): chi_b(r) for all b in {0,1}^ell, r[0] <-> MSB. 1 <= ell <= 32 (a long table is the outer
+ * product of two short ones of at most 16 variables each); any other ell is SP_EINVAL, returned before anything is allocated. */
 int32_t sp_eq_expand(sp_ctx* ctx, const uint64_t* r /*4*ell*/, size_t ell, sp_table** out);
 /* Sum-check round evaluations over the current length of the tables (t = 0, 2[, 3]):
  *   kind 0: A*B          -> out[2]  (sumcheck.rs:460-469, comb of r1csproof.rs:122-123)
  *   kind 1: A*B*C        -> out[3]  (sumcheck.rs:203-228 / 290-357)
  *   kind 2: A*(B*C - D)  -> out[3]  (sumcheck.rs:624-652, comb of r1csproof.rs:87-91)        */
 int32_t sp_sumcheck_eval(sp_ctx* ctx, int kind, sp_table* const* tabs, size_t ntabs, uint64_t* out_evals);
-/* DensePolynomial::bound_poly_var_top (dense_mlpoly.rs:215-223) on every table: Z[i] += r*(Z[i+n]-Z[i]). */
+/* DensePolynomial::bound_poly_var_top (dense_mlpoly.rs:215-223) on every table: Z[i] += r*(Z[i+n]-Z[i]). The tables have one length, a
+ * power of two >= 2, and each is listed once; the whole list is checked before anything is launched, so a call that returns SP_EINVAL
+ * has changed no table. */
 int32_t sp_table_bind_top(sp_ctx* ctx, sp_table* const* tabs, size_t ntabs, const uint64_t r[4]);
 /* The last round of a sum-check: tables of length 2 are bound at r (length 1) and their remaining entry is returned,
  * out_heads[4k..4k+4) for table k — one launch and one wait for any number of tables (each listed once). */

@@ -39,8 +39,9 @@ constexpr size_t EQ_SMALL_ELL = 13;
 // One thread per entry, but not one chain of ell multiplications per thread (a lone wavefront needs 1-2 us per dependent
 // F_q multiplication: 13 of them were ~19 us per table, on the critical path of every product-circuit layer). The factors
 // are grouped: the low 8 index bits split 4 + 4 into two 16-entry tables built by 32 threads (3 multiplications deep),
-// the block's high bits (<= 5) are multiplied out by one more thread, then hi*ta (16 threads) and one multiplication per
-// entry: at most 6 deep. The product of the same factors in another order is the same field element.
+// the block's high bits (<= 5 for a table of its own, <= 8 for the 16-variable half of a long table) are multiplied out by
+// one more thread, then hi*ta (16 threads) and one multiplication per entry: at most 6 deep for a table of its own. The
+// product of the same factors in another order is the same field element.
 // The three product chains (the two 16-entry tables and the block's high bits) run in three different wavefronts: as branches of ONE
 // wavefront they were executed one after the other (10 dependent multiplications instead of 4: 14 -> ~8 us per table, 70+ tables per
 // proof). The challenge vector travels in the kernel arguments (r_host == null) instead of being read from the host-mapped page.
@@ -359,11 +360,14 @@ static void launch_eq_small(sp_ctx* c, const Fq* dr, const uint64_t* r_host, siz
   hipLaunchKernelGGL(k_eq_expand_small, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, inl ? (const Fq*)nullptr : dr, in, ell, out);
 }
 int32_t sp_eq_expand(sp_ctx* c, const uint64_t* r, size_t ell, sp_table** out) {
-  if (!c || !r || !out || ell == 0 || ell > 40) return SP_EINVAL;
+  // ell > 32: a long table's upper half has hi_ell = ell - ell/2 variables, and hi_ell <= 16 is what k_eq_expand_small's r[16] holds
+  // (ell = 33 would copy 17 scalars into it); refused here, before a ring slot is taken or anything is allocated. No test reaches
+  // ell >= 27, where a half has 14..16 variables, fills r[13..15] and is always read from the staged slot: tables of 4 GiB and more
+  if (!c || !r || !out || ell == 0 || ell > 32) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
   // the challenge vector goes into the next slot of a small ring and the call returns without waiting; a slot is reused
   // only after a completed wait on the stream (sync_epoch moved on), which guarantees its kernel has read it
-  static_assert(EQ_SLOTS == 8 && 32 * 40 <= EQ_SLOT_BYTES, "eq ring layout");
+  static_assert(EQ_SLOTS == 8 && 32 * 32 <= EQ_SLOT_BYTES, "eq ring layout");
   unsigned slot = c->eq_next;
   c->eq_next = (slot + 1) % EQ_SLOTS;
   if (c->eq_slot_epoch[slot] == c->sync_epoch + 1) SPCHK(sync_spin(c));
@@ -427,19 +431,22 @@ int32_t sp_sumcheck_eval(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntab
 }
 int32_t sp_table_bind_top(sp_ctx* c, sp_table* const* tabs, size_t ntabs, const uint64_t r[4]) {
   if (!c || !tabs || !r || ntabs == 0) return SP_EINVAL;
+  // the whole list is checked before the first launch: a refused call leaves every table as it was
+  size_t len = tabs[0] ? tabs[0]->len : 0;
+  if (len < 2 || !is_pow2(len)) return SP_EINVAL;
+  for (size_t k = 0; k < ntabs; k++) {
+    if (!tabs[k] || tabs[k]->len != len) return SP_EINVAL;
+    for (size_t m = 0; m < k; m++)
+      if (tabs[m] == tabs[k]) return SP_EINVAL;  // a table listed twice would be bound twice (as in bind_top_list)
+  }
   HIPCHK(hipSetDevice(c->dev));
   Fq rr;
   memcpy(rr.l, r, 32);
+  size_t half = len / 2;
   for (size_t k0 = 0; k0 < ntabs; k0 += 4) {
     size_t nk = ntabs - k0 < 4 ? ntabs - k0 : 4;
     Tabs4 T = {{nullptr, nullptr, nullptr, nullptr}};
-    size_t len = tabs[k0] ? tabs[k0]->len : 0;
-    for (size_t k = 0; k < nk; k++) {
-      if (!tabs[k0 + k] || tabs[k0 + k]->len != len) return SP_EINVAL;
-      T.p[k] = tabs[k0 + k]->d;
-    }
-    if (len < 2 || !is_pow2(len)) return SP_EINVAL;
-    size_t half = len / 2;
+    for (size_t k = 0; k < nk; k++) T.p[k] = tabs[k0 + k]->d;
     {
       ProfScope ps(c, PF_SC_BIND, 48.0 * (double)len * (double)nk);
       hipLaunchKernelGGL(k_bind_top, dim3((unsigned)grid_for(half)), dim3(256), 0, c->stream, T, (int)nk, half, rr);

@@ -118,15 +118,15 @@ def _ints(arr, n=None):
     return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(n)]
 
 
-def _same(sec, got, want, what):
-    """exact comparison of every value, each below q"""
+def _same(sec, got, want, what, counts=None):
+    """exact comparison of every value, each below q; counts: another module's tally (tests/test_gpu_fq_edges.py)"""
     assert len(got) == len(want), (what, len(got), len(want))
     bad = [i for i in range(len(want)) if got[i] != want[i] or got[i] >= Q]
     if bad:
         i = bad[0]
         pytest.fail("%s: %d of %d values differ, first at %d\n    want %#066x\n    got  %#066x%s" % (
             what, len(bad), len(want), i, want[i], got[i], "  (not reduced: >= q)" if got[i] >= Q else ""))
-    COUNTS[sec] += len(want)
+    (COUNTS if counts is None else counts)[sec] += len(want)
 
 
 def _same_table(sec, t, want, what, off=0):
