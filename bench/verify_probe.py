@@ -1,4 +1,4 @@
-"""What NIZK::verify costs on the device (spartan_amd/host/verifier.cc) next to the oracle's restated verifier on the host cores of the same
+"""What NIZK::verify and SNARK::verify cost on the device (spartan_amd/host/verifier.cc) next to the oracle's restated verifier on the host cores of the same
 box. One process, its own time limit, stops at the first step that fails. Per size (2^16, 2^20, 2^22 constraints, synthetic instances):
   (a) NIZK.verify of the HIP prover's proof, warm (digest set, generator tables built, one verification done): median of 20 calls timed with
       the host clock — the call ends in a wait for the device, so the wall time is the verification;
@@ -6,7 +6,11 @@ box. One process, its own time limit, stops at the first step that fails. Per si
       round trips of one verification (sp_ctx_trips);
   (c) the oracle's orc_nizk_verify_bytes on the same bytes, 16 host threads, median of 3.
 The reference publishes 414.5 ms for NIZK::verify at 2^20 on its own machine (BASELINE.md): context, not a comparison on this box.
-usage: python bench/verify_probe.py [--out profiles/nizk_verify.txt] [--sizes 16,20,22]"""
+--what snark: the same three for SNARK.verify against a Commitment loaded from bincode bytes (two of its four C_LZ go through sp_msm_var, two
+through the resident point sets of the commitment, sp_msm_points) and the oracle's orc_snark_verify_bytes.
+--what msm: sp_msm_points against sp_msm_var on identical points and scalars (n = 2048, 4096), the calls interleaved in one process, 20 samples
+each after 3 warm pairs: median and spread (min .. max) per call, the table build (sp_points_upload) beside them.
+usage: python bench/verify_probe.py [--what nizk|snark|msm] [--out profiles/nizk_verify.txt] [--sizes 16,20,22]"""
 import argparse, ctypes, faulthandler, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,13 +54,120 @@ def family(raw, name):
     return {names[i].decode(): (ms[i], int(n[i])) for i in range(k)}.get(name, (0.0, 0))
 
 
+def comm_parts(cb):
+    """the six numbers and the two share vectors of bincode(ComputationCommitment), as orc_snark_verify_bytes takes them"""
+    h = [int.from_bytes(cb[8 * i:8 * i + 8], "little") for i in range(6)]
+    n_ops = int.from_bytes(cb[48:56], "little")
+    o = 56 + 32 * n_ops
+    n_mem = int.from_bytes(cb[o:o + 8], "little")
+    return h, cb[56:o], cb[o + 8:o + 8 + 32 * n_mem]
+
+
+def snark(args, orc):
+    label = b"snark_example"
+    lines = ["SNARK::verify on the device against the oracle's verifier on the host (bench/verify_probe.py --what snark; host CPU: %s)" % cpu_model(),
+             "(a): median of %d warm calls, host clock; msm_var / msm_points: HIP events around their launch chains, runs of their own; (c): median of 3, 16 threads" % REPS,
+             ""]
+    ctx = P.Ctx(0)
+    raw = ctx.raw()
+    for s in [int(x) for x in args.sizes.split(",")]:
+        N, ni, seed = 1 << s, 10, s
+        inst = P.Instance.produce_synthetic_r1cs(ctx, N, N, ni, seed=seed)
+        gens = P.SNARKGens(ctx, N, N, ni, N)
+        enc = P.SNARK.encode(ctx, inst, gens)
+        proof = P.SNARK.prove(ctx, inst, enc, inst.vars, inst.inputs, gens, label, P.seed_scalar(b"tape", seed))
+        cb = enc.serialize_commitment()
+        t0 = time.perf_counter(); comm = P.Commitment.load(ctx, cb); load_ms = (time.perf_counter() - t0) * 1e3
+        verify = lambda: P.SNARK.verify_status(ctx, comm, proof, inst.inputs, gens, label)
+        if verify() != 1:
+            raise SystemExit("2^%d: the device verifier rejected the prover's proof" % s)
+        med, lo, hi = median_ms(verify, WARM, REPS)
+        t0 = L.sp_ctx_trips(raw); verify(); trips = L.sp_ctx_trips(raw) - t0
+        L.sp_prof_enable(raw, ctypes.c_int(1)); L.sp_prof_reset(raw)
+        for _ in range(5):
+            verify()
+        mv_ms, mv_n = family(raw, "msm_var")
+        mp_ms, mp_n = family(raw, "msm_points")
+        L.sp_prof_enable(raw, ctypes.c_int(0))
+        h, ops, mem = comm_parts(cb)
+        og = vp(orc.orc_snark_gens_new(sz(N), sz(N), sz(ni), sz(N)))
+        overify = lambda: orc.orc_snark_verify_bytes(proof, sz(len(proof)), og, sz(h[0]), sz(h[1]), sz(h[2]), sz(h[4]), sz(h[5]), ops, sz(len(ops) // 32), mem,
+                                                     sz(len(mem) // 32), inst.inputs, label)
+        if overify() != 1:
+            raise SystemExit("2^%d: the oracle rejected the prover's proof" % s)
+        omed, olo, ohi = median_ms(overify, 0, 3)
+        orc.orc_snark_gens_free(og)
+        lines += ["synthetic 2^%d: proof %d bytes, commitment %d + %d shares (loaded once in %.1f ms), %d round trips per verification" % (
+                      s, len(proof), len(ops) // 32, len(mem) // 32, load_ms, trips),
+                  "  (a) SNARK.verify, device                 median %9.3f ms   (min %.3f, max %.3f)" % (med, lo, hi),
+                  "  (b) msm_var launch chain                 mean   %9.3f ms   (of %d); msm_points launch chain mean %.3f ms (of %d)" % (
+                      mv_ms / max(mv_n, 1), mv_n, mp_ms / max(mp_n, 1), mp_n),
+                  "  (c) oracle orc_snark_verify_bytes        median %9.3f ms   (min %.3f, max %.3f)" % (omed, olo, ohi),
+                  "  (c) / (a) = %.1f" % (omed / med)]
+        print("\n".join(lines[-5:]), flush=True)
+        comm.free(); enc.free(); gens.free(); inst.free()
+    ctx.close()
+    return lines
+
+
+def msm(args, orc):
+    import random
+    from tests import msm_var_cases as M
+    from tests.helpers import mont_bulk, fast_scalars
+    lines = ["sp_msm_points (resident point set) against sp_msm_var on identical points and scalars (bench/verify_probe.py --what msm)",
+             "calls interleaved in one process, %d warm pairs, then %d samples each on the host clock (a call ends in its wait for the device)" % (WARM, REPS),
+             ""]
+    ctx = capi.Ctx(0)
+    out = (ctypes.c_uint8 * 32)()
+    for n in (2048, 4096):
+        pts = b"".join(M.points(orc, n))
+        S = mont_bulk(fast_scalars(random.Random(n), n))
+        h = vp()
+        t0 = time.perf_counter()
+        rc = L.sp_points_upload(ctx.h, pts, sz(n), ctypes.byref(h))
+        build_ms = (time.perf_counter() - t0) * 1e3
+        if rc != 0:
+            raise SystemExit("sp_points_upload: %d" % rc)
+        tv, tp, rv, rp = [], [], None, None
+        for i in range(WARM + REPS):
+            t0 = time.perf_counter(); rc1 = L.sp_msm_var(ctx.h, pts, S, sz(n), out); t1 = time.perf_counter(); rv = bytes(out)
+            rc2 = L.sp_msm_points(ctx.h, h, S, sz(n), out); t2 = time.perf_counter(); rp = bytes(out)
+            if rc1 != 0 or rc2 != 0 or rv != rp:
+                raise SystemExit("n = %d: the two multiplications disagree (%d, %d)" % (n, rc1, rc2))
+            if i >= WARM:
+                tv.append((t1 - t0) * 1e3); tp.append((t2 - t1) * 1e3)
+        L.sp_points_free(h)
+        tv.sort(); tp.sort()
+        mv, mp = tv[len(tv) // 2], tp[len(tp) // 2]
+        spread = max(tv[-1] - tv[0], tp[-1] - tp[0])
+        lines += ["n = %d: table build (sp_points_upload, %d MiB) %.2f ms, once" % (n, n * 64 // 1024, build_ms),
+                  "  sp_msm_var     median %8.3f ms   (min %.3f, max %.3f)" % (mv, tv[0], tv[-1]),
+                  "  sp_msm_points  median %8.3f ms   (min %.3f, max %.3f)" % (mp, tp[0], tp[-1]),
+                  "  difference of the medians %.3f ms, widest spread of the %d samples %.3f ms: %s" % (
+                      mv - mp, REPS, spread, "a gain beyond the spread" if mv - mp > spread else "NO gain beyond the spread")]
+        print("\n".join(lines[-4:]), flush=True)
+    ctx.close()
+    return lines
+
+
+def finish(args, lines):
+    text = "\n".join(lines) + "\n"
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="16,20,22")
+    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm"])
     args = ap.parse_args()
     orc = load_oracle()
     orc.orc_set_threads(ctypes.c_int(16))
+    if args.what != "nizk":
+        return finish(args, snark(args, orc) if args.what == "snark" else msm(args, orc))
     lines = ["NIZK::verify on the device against the oracle's verifier on the host (bench/verify_probe.py; host CPU: %s)" % cpu_model(),
              "(a): median of %d warm calls, host clock; msm_var: HIP events around its launch chain, runs of their own; (c): median of 3, 16 threads" % REPS,
              ""]

@@ -106,7 +106,8 @@ int sp_msm_window_bits(void);
  * tables fit in free device memory.
  * FIXED PUBLIC BASES: every multi-scalar multiplication of the PROVER (sp_commit_rows*, sp_msm_indexed, the inner-product argument) runs
  * over the points of a sp_gens through its precomputed tables (every base on the prover's path is a public generator).
- * The one multiplication over points that are NOT a sp_gens is the verifier's: sp_msm_var (device) and sp_host_msm_var (calling thread) below. */
+ * The multiplications over points that are NOT a sp_gens are the verifiers': sp_msm_var (device) and sp_host_msm_var (calling thread) over points
+ * that arrive with a proof, sp_msm_points (device) over a resident set of points that were given once (sp_points), all below. */
 /* A caller-supplied list may hold points with known relations between them (repeats, torsion shifts): the inner-product argument over such a
  * set always uses the COMPLETE addition formula in its trees; sets the library derives itself (sp_gens_from_uniform) use the faster dedicated one,
  * whose exceptional pairs cannot occur between sums over independent hash-to-curve points. */
@@ -195,6 +196,19 @@ int32_t sp_msm_var(sp_ctx* ctx, const uint8_t* points /*32*n*/, const uint64_t* 
 /* The same sum on the calling thread's core, no context, n <= 64: the 2..2 lg n + 1-term combinations of the verifiers
  * (sumcheck.rs:127, r1csproof.rs:426,470, bullet.rs:216). SP_EINVAL: n = 0, n > 64, a null pointer. SP_EPOINT as above. */
 int32_t sp_host_msm_var(const uint8_t* points, const uint64_t* S, size_t n, uint8_t out[32]);
+/* ---- resident point sets (SNARK::verify: the two commitments of a ComputationCommitment, fixed for the lifetime of a circuit) ----
+ * A sp_points is n points that are NOT generators of the library but do not change between calls. They are decoded once, at upload, and the
+ * set keeps the multiples 1..8 of 16^w P for all 64 signed 4-bit windows of every point: n x 64 x 8 extended points, 64 KiB of HBM a point.
+ * Like the points of sp_msm_var they are untrusted — the identity, repeats and negatives of each other are legal — and every addition is the
+ * complete one. 1 <= n <= 65536. SP_EPOINT (and no handle) when an encoding is invalid: checked here, once, and never again. */
+typedef struct sp_points sp_points;
+int32_t sp_points_upload(sp_ctx* ctx, const uint8_t* compressed /*32*n*/, size_t n, sp_points** out);
+void sp_points_free(sp_points* p);
+size_t sp_points_count(const sp_points* p);
+/* out = compress( sum_{j<n} S[j] * P[j] ) over the set: the sum of sp_msm_var as a flat sum of table entries — no decode, no table build, no
+ * Horner doublings (msm_var.hip). Synchronous, one launch chain, one round trip. SP_EINVAL: n is not the set's size, the set lives on
+ * another device than ctx, a null pointer. */
+int32_t sp_msm_points(sp_ctx* ctx, const sp_points* pts, const uint64_t* S /*4*n, Montgomery*/, size_t n, uint8_t out[32]);
 /* Look-ahead for the zero-knowledge sum-checks. Inside their round loop nothing but DotProductProof::prove draws from the
  * random tape (d_vec, r_delta, r_beta: nizk/mod.rs:330-334), so a caller can take the draws of all rounds up front, in the
  * reference's order, and have a helper thread compute everything that depends on the tape alone while the rounds run:

@@ -36,6 +36,7 @@ enum ProfFamily {
   PF_SPARK,
   PF_MISC,
   PF_MSM_VAR,
+  PF_MSM_POINTS,
   PF_COUNT
 };
 extern const char* kProfNames[PF_COUNT];

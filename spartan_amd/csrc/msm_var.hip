@@ -31,6 +31,18 @@ __device__ __forceinline__ Pt pt_shfl_down(const Pt& p, int delta) {
   return r;
 }
 
+// The sum of one term per lane over a block of MV_BLOCK lanes, shared by the window kernels of sp_msm_var and sp_msm_points: 6 wavefront
+// shuffle levels, then the 4 wavefront sums through LDS; lane 0 writes the block's sum. EVERY lane of the block must call it (no early exit
+// before it): lane 0 of each wavefront ends with the sum of its 64 terms.
+__device__ __forceinline__ void msmv_block_sum(Pt p, Pt* sm /*[MV_BLOCK / 64], shared*/, Pt* __restrict__ out) {
+  const int t = threadIdx.x;
+#pragma unroll 1
+  for (int delta = 32; delta > 0; delta >>= 1) p = pt_add(p, pt_shfl_down(p, delta));
+  if ((t & 63) == 0) sm[t >> 6] = p;
+  __syncthreads();
+  if (t == 0) *out = pt_add(pt_add(sm[0], sm[1]), pt_add(sm[2], sm[3]));
+}
+
 __global__ void __launch_bounds__(64) k_msmv_prepare(const uint8_t* __restrict__ enc, const Fq* __restrict__ S, size_t n, Pt* __restrict__ table,
                                                      int8_t* __restrict__ digits /*[64][n]*/, int* __restrict__ bad) { SP_FG_PRIO();
   const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -64,12 +76,7 @@ __global__ void __launch_bounds__(MV_BLOCK) k_msmv_windows(const Pt* __restrict_
       if (d < 0) p = pt_neg(p);
     }
   }
-  // every lane of the block is alive here (no early exit above): lane 0 of each wavefront ends with the sum of its 64 terms
-#pragma unroll 1
-  for (int delta = 32; delta > 0; delta >>= 1) p = pt_add(p, pt_shfl_down(p, delta));
-  if ((t & 63) == 0) sm[t >> 6] = p;
-  __syncthreads();
-  if (t == 0) partial[w * gridDim.x + blockIdx.x] = pt_add(pt_add(sm[0], sm[1]), pt_add(sm[2], sm[3]));
+  msmv_block_sum(p, sm, &partial[w * gridDim.x + blockIdx.x]);
 }
 
 __global__ void __launch_bounds__(256) k_msmv_finish(const Pt* __restrict__ partial, size_t nblocks, const int* __restrict__ bad, uint8_t* __restrict__ out /*32 + 4*/,
@@ -95,6 +102,78 @@ __global__ void __launch_bounds__(256) k_msmv_finish(const Pt* __restrict__ part
     pt10_compress(r10, c);
     for (int k = 0; k < 32; k++) out[k] = c[k];
     *reinterpret_cast<int*>(out + 32) = *bad;
+  }
+  signal_done(sig);
+}
+// ---- resident point sets (sp_points, sp_msm_points): the same sum over points that do NOT change between calls — the two commitments of a
+// ComputationCommitment, fixed for the lifetime of a circuit. The set is decoded once and keeps, per point, the multiples 1..8 of 16^w P for
+// all 64 windows (64 KiB a point), so a multiplication is a flat sum of table entries: no decode, no table build, no Horner doublings.
+//   k_points_build   one lane per point, at upload: decode (flag word as above), then per window the table of the running base and base <- 16 base;
+//   k_msmp_digits    one lane per scalar: out of Montgomery form, 64 signed digits, the [64][n] layout of k_msmv_prepare;
+//   k_msmp_windows   k_msmv_windows with the lane's term fetched from window w's slice of the resident table;
+//   k_msmp_finish    one block: 256 lanes stride over all 64 x nblocks partial sums (they carry their weight 16^w already), 6 shuffle levels,
+//                    the 4 wavefront sums through LDS, the encode on one lane; the result goes to the host page.
+// Point operations on the critical path: 8 + ceil(64 nblocks / 256) + 8 + the encode. One round trip.
+__global__ void __launch_bounds__(64) k_points_build(const uint8_t* __restrict__ enc, size_t n, Pt* __restrict__ table /*[64][n][8]*/, int* __restrict__ bad) {
+  const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (j >= n) return;
+  uint8_t b[32];
+  for (int k = 0; k < 32; k++) b[k] = enc[32 * j + k];
+  Pt base;
+  if (!pt_decompress(b, &base)) {
+    atomicExch(bad, 1);
+    base = pt_identity();
+  }
+#pragma unroll 1
+  for (size_t w = 0; w < SP_VAR_WINDOWS; w++) {
+    Pt T[SP_VAR_TABLE];
+    pt_var_table(base, T);
+    for (int m = 0; m < SP_VAR_TABLE; m++) table[(w * n + j) * SP_VAR_TABLE + m] = T[m];
+    base = pt_dbl(T[SP_VAR_TABLE - 1]);  // 16 base = 2 (8 base)
+  }
+}
+
+__global__ void __launch_bounds__(MV_BLOCK) k_msmp_digits(const Fq* __restrict__ S, size_t n, int8_t* __restrict__ digits /*[64][n]*/) { SP_FG_PRIO();
+  const size_t j = (size_t)blockIdx.x * MV_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  int8_t d[SP_VAR_WINDOWS];
+  fq_signed_digits4(fq_from_mont(ld_fq(S + j)), d);
+  for (int w = 0; w < SP_VAR_WINDOWS; w++) digits[(size_t)w * n + j] = d[w];
+}
+
+// grid (nblocks, 64 windows): partial[w * nblocks + blk] = sum over the block's 256 points of digit_w(S[j]) * 16^w P[j]
+__global__ void __launch_bounds__(MV_BLOCK) k_msmp_windows(const Pt* __restrict__ table, const int8_t* __restrict__ digits, size_t n,
+                                                           Pt* __restrict__ partial) { SP_FG_PRIO();
+  __shared__ Pt sm[MV_BLOCK / 64];
+  const int t = threadIdx.x;
+  const size_t w = blockIdx.y, j = (size_t)blockIdx.x * MV_BLOCK + t;
+  Pt p = pt_identity();
+  if (j < n) {
+    const int d = digits[w * n + j];
+    if (d != 0) {
+      p = table[(w * n + j) * SP_VAR_TABLE + ((d < 0 ? -d : d) - 1)];
+      if (d < 0) p = pt_neg(p);
+    }
+  }
+  msmv_block_sum(p, sm, &partial[w * gridDim.x + blockIdx.x]);
+}
+
+__global__ void __launch_bounds__(256) k_msmp_finish(const Pt* __restrict__ partial, size_t nparts, uint8_t* __restrict__ out /*32*/, DoneSig sig) { SP_FG_PRIO();
+  __shared__ Pt sm[4];
+  const int t = threadIdx.x;
+  Pt acc = pt_identity();
+  for (size_t i = t; i < nparts; i += 256) acc = pt_add(acc, partial[i]);
+#pragma unroll 1
+  for (int delta = 32; delta > 0; delta >>= 1) acc = pt_add(acc, pt_shfl_down(acc, delta));
+  if ((t & 63) == 0) sm[t >> 6] = acc;
+  __syncthreads();
+  if (t == 0) {
+    Pt r = pt_add(pt_add(sm[0], sm[1]), pt_add(sm[2], sm[3]));
+    uint8_t c[32];
+    Pt10 r10 = pt10_load(r);
+    fe10_pin(r10.X); fe10_pin(r10.Y); fe10_pin(r10.Z); fe10_pin(r10.T);
+    pt10_compress(r10, c);
+    for (int k = 0; k < 32; k++) out[k] = c[k];
   }
   signal_done(sig);
 }
@@ -143,6 +222,81 @@ extern "C" int32_t sp_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* 
   int flag;
   memcpy(&flag, res + 32, 4);
   if (flag) return SP_EPOINT;
+  memcpy(out, res, 32);
+  return SP_OK;
+}
+
+struct sp_points {
+  int dev;
+  size_t n;
+  Pt* table;  // [64 windows][n][8]: table[(w * n + j) * 8 + m - 1] = m 16^w P[j]
+};
+
+extern "C" int32_t sp_points_upload(sp_ctx* c, const uint8_t* compressed, size_t n, sp_points** out) {
+  if (!c || !compressed || !out || n == 0 || n > MV_MAX_N) return SP_EINVAL;
+  *out = nullptr;
+  HIPCHK(hipSetDevice(c->dev));
+  SPCHK(ensure_dstage(c, 32 * n));
+  SPCHK(stage_in(c, 0, compressed, 32 * n));
+  const size_t table_bytes = n * SP_VAR_WINDOWS * SP_VAR_TABLE * sizeof(Pt);
+  uint8_t* buf = nullptr;  // the table, then the flag word
+  HIPCHK(hipMalloc((void**)&buf, table_bytes + 256));
+  int* bad = (int*)(buf + table_bytes);
+  int flag = 0;
+  int32_t rc = hipMemsetAsync(bad, 0, 4, c->stream) == hipSuccess ? SP_OK : SP_EHIP;
+  if (rc == SP_OK)
+    hipLaunchKernelGGL(k_points_build, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t*)c->dstage, n, (Pt*)buf, bad);
+  if (rc == SP_OK) rc = fetch_out(c, bad, &flag, 4);
+  if (rc == SP_OK && hipGetLastError() != hipSuccess) rc = SP_EHIP;
+  if (rc == SP_OK && flag) rc = SP_EPOINT;
+  sp_points* p = rc == SP_OK ? new (std::nothrow) sp_points{c->dev, n, (Pt*)buf} : nullptr;
+  if (!p) {
+    (void)hipFree(buf);
+    return rc == SP_OK ? SP_ENOMEM : rc;
+  }
+  *out = p;
+  return SP_OK;
+}
+extern "C" void sp_points_free(sp_points* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->dev);
+  (void)hipFree(p->table);  // waits for whatever still reads the table
+  delete p;
+}
+extern "C" size_t sp_points_count(const sp_points* p) { return p ? p->n : 0; }
+
+extern "C" int32_t sp_msm_points(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, uint8_t out[32]) {
+  if (!c || !pts || !S || !out || n == 0 || n != pts->n || pts->dev != c->dev) return SP_EINVAL;
+  HIPCHK(hipSetDevice(c->dev));
+  const size_t nblocks = (n + MV_BLOCK - 1) / MV_BLOCK, nparts = (size_t)SP_VAR_WINDOWS * nblocks;
+  // device buffer: [partial 64 x nblocks Pt][digits 64 n]
+  const size_t off_dig = nparts * sizeof(Pt), total = off_dig + (size_t)SP_VAR_WINDOWS * n;
+  const Fq* d_S;
+  if (32 * n <= HMAP_GEN) {
+    d_S = (const Fq*)stage_small(c, 0, S, 32 * n);
+  } else {
+    SPCHK(ensure_dstage(c, 32 * n));
+    SPCHK(stage_in(c, 0, S, 32 * n));
+    d_S = (const Fq*)c->dstage;
+  }
+  void* buf = nullptr;
+  SPCHK(pool_alloc(c, total, &buf));
+  Pt* partial = (Pt*)buf;
+  int8_t* digits = (int8_t*)((uint8_t*)buf + off_dig);
+  uint8_t* res = hres(c);
+  DoneSig sig = sig_make(c, 1);
+  {
+    const double ops = (double)SP_VAR_WINDOWS * (double)(nblocks * MV_BLOCK) + (double)nparts;
+    ProfScope ps(c, PF_MSM_POINTS, 32.0 * (double)n + 32.0, nullptr, ops);
+    hipLaunchKernelGGL(k_msmp_digits, dim3((unsigned)nblocks), dim3(MV_BLOCK), 0, c->stream, d_S, n, digits);
+    hipLaunchKernelGGL(k_msmp_windows, dim3((unsigned)nblocks, SP_VAR_WINDOWS), dim3(MV_BLOCK), 0, c->stream, (const Pt*)pts->table, (const int8_t*)digits, n,
+                       partial);
+    hipLaunchKernelGGL(k_msmp_finish, dim3(1), dim3(256), 0, c->stream, (const Pt*)partial, nparts, res, sig);
+  }
+  int32_t rc = sig_wait(c, sig);
+  pool_release(c, buf, total);
+  if (rc != SP_OK) return rc;
+  if (hipGetLastError() != hipSuccess) return SP_EHIP;
   memcpy(out, res, 32);
   return SP_OK;
 }

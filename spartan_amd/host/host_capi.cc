@@ -1,6 +1,7 @@
 // spartan_amd host driver: C entry points over libspartan.hpp for ctypes (tests/, bench.py). Exceptions are
 // turned into NULL / error strings here; nothing throws across the boundary.
 #include <cstring>
+#include <memory>
 #include <string>
 
 #include "libspartan.hpp"
@@ -12,6 +13,11 @@ namespace {
 thread_local std::string g_err;
 struct EncH { ComputationCommitment comm; ComputationDecommitment decomm; };
 struct ProofH { std::vector<uint8_t> bytes; };
+struct CommH {  // what spz_commitment_load hands out: the commitment and its two share vectors as resident point sets
+  ComputationCommitment comm;
+  sp_points *ops = nullptr, *mem = nullptr;
+  ~CommH() { sp_points_free(ops); sp_points_free(mem); }
+};
 FqVec limbs_vec(const uint64_t* p, size_t n) { FqVec v(n); if (n) memcpy(v[0].l, p, 32 * n); return v; }
 void fill_times(const ProveTimes& t, double* o) {
   if (!o) return;
@@ -414,6 +420,85 @@ long long spz_nizk_parse_probe(const uint8_t* proof, size_t len, uint8_t* out, s
     NIZK p;
     if (!NIZK::deserialize(proof, len, &p)) return -1;
     std::vector<uint8_t> b = p.serialize();
+    if (out && cap >= b.size()) memcpy(out, b.data(), b.size());
+    return (long long)b.size();
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+// ComputationCommitment::deserialize of untrusted bytes (what spz_commitment_bincode writes): the verifier's handle of a circuit, with both share
+// vectors uploaded as resident point sets (64 KiB of HBM a share). NULL with spz_last_error() for bytes that are not one commitment, or
+// that hold a share that does not decode.
+void* spz_commitment_load(void* ctx, const uint8_t* bytes, size_t len) {
+  return guard([&]() -> void* {
+    if (!ctx || !bytes) throw Error("spz_commitment_load: bad arguments");
+    std::unique_ptr<CommH> h(new CommH);
+    if (!ComputationCommitment::deserialize(bytes, len, &h->comm)) throw Error("spz_commitment_load: malformed commitment bytes");
+    auto upload = [&](const PolyCommitment& pc, sp_points** out) {  // an undecodable share is found here, once (SP_EPOINT)
+      int32_t rc = sp_points_upload(((Ctx*)ctx)->h, pc.C[0].data(), pc.C.size(), out);
+      if (rc != SP_OK) throw Error(std::string("spz_commitment_load: sp_points_upload failed: ") + sp_strerror(rc));
+    };
+    upload(h->comm.comm.comm_comb_ops, &h->ops);
+    upload(h->comm.comm.comm_comb_mem, &h->mem);
+    return h.release();
+  });
+}
+void spz_commitment_free(void* comm) { delete (CommH*)comm; }
+// SNARK::verify (lib.rs:423-466) of untrusted proof bytes against a loaded commitment: 1 accept, 0 reject, -1 malformed bytes (SNARK::deserialize),
+// -2 error (spz_last_error(): "InvalidNumberOfInputs", or a device failure). Nothing throws across the boundary.
+static int snark_verify_on(void* ctx, void* comm, void* gens, const uint8_t* proof, size_t proof_len, const uint64_t* inputs, size_t n_inputs, Transcript& t) {
+  SNARK p;
+  if (!SNARK::deserialize(proof, proof_len, &p)) return -1;
+  const CommH& h = *(CommH*)comm;
+  return p.verify(*(Ctx*)ctx, h.comm, limbs_vec(inputs, n_inputs), t, *(SNARKGens*)gens, ResidentCommitment{h.ops, h.mem});
+}
+int spz_snark_verify(void* ctx, void* comm, void* gens, const uint8_t* proof, size_t proof_len, const uint64_t* inputs, size_t n_inputs,
+                     const char* transcript_label) {
+  try {
+    g_err.clear();
+    if (!ctx || !comm || !gens || !proof || !transcript_label || (n_inputs && !inputs)) throw Error("spz_snark_verify: bad arguments");
+    Transcript t(transcript_label);
+    return snark_verify_on(ctx, comm, gens, proof, proof_len, inputs, n_inputs, t);
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -2;
+  }
+}
+// the same on a caller-owned transcript (spz_snark_prove_t): continued by the verification and left in the state it ends in
+int spz_snark_verify_t(void* ctx, void* comm, void* gens, const uint8_t* proof, size_t proof_len, const uint64_t* inputs, size_t n_inputs,
+                       uint8_t transcript_state[203]) {
+  try {
+    g_err.clear();
+    if (!ctx || !comm || !gens || !proof || !transcript_state || (n_inputs && !inputs)) throw Error("spz_snark_verify_t: bad arguments");
+    Transcript t(Transcript::FromState(), transcript_state);
+    int v = snark_verify_on(ctx, comm, gens, proof, proof_len, inputs, n_inputs, t);
+    t.export_state(transcript_state);
+    return v;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -2;
+  }
+}
+// no GPU, no context: SNARK::deserialize, then SNARK::serialize. Returns the number of bytes (written when cap suffices), -1 when malformed.
+long long spz_snark_reserialize(const uint8_t* proof, size_t len, uint8_t* out, size_t cap) {
+  try {
+    SNARK p;
+    if (!SNARK::deserialize(proof, len, &p)) return -1;
+    std::vector<uint8_t> b = p.serialize();
+    if (out && cap >= b.size()) memcpy(out, b.data(), b.size());
+    return (long long)b.size();
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+// the same for ComputationCommitment::deserialize / serialize
+long long spz_commitment_reserialize(const uint8_t* bytes, size_t len, uint8_t* out, size_t cap) {
+  try {
+    ComputationCommitment c;
+    if (!ComputationCommitment::deserialize(bytes, len, &c)) return -1;
+    std::vector<uint8_t> b = c.serialize();
     if (out && cap >= b.size()) memcpy(out, b.data(), b.size());
     return (long long)b.size();
   } catch (const std::exception& e) {

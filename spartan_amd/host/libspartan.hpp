@@ -2,8 +2,7 @@
 // the C ABI in include/spartan_hip.h. It exists because no Rust toolchain is available here; in the drop-in
 // deployment this layer IS libspartan (Rust) with the `gpu` feature. Names and argument
 // meaning follow the reference: Instance, VarsAssignment/InputsAssignment, SNARKGens, NIZKGens,
-// ComputationCommitment/Decommitment, SNARK::{encode,prove}, NIZK::{prove,verify} (verifier.cc). SNARK::verify is not implemented
-// (SURVEY.md §2.1); tests verify SNARK bytes with the oracle's restated verifier.
+// ComputationCommitment/Decommitment, SNARK::{encode,prove,verify}, NIZK::{prove,verify} (the verifiers: verifier.cc).
 //
 // All table-sized field/group work of the prover runs on the GPU through sp_* calls; the host keeps what the
 // reference keeps next to its Transcript — Fiat–Shamir, O(log n)-sized scalar bookkeeping, serialization — and the
@@ -279,6 +278,15 @@ struct ComputationCommitment {  // lib.rs:44-48 -> r1cs.rs:50-56
   size_t num_cons, num_vars, num_inputs;
   SparseMatPolyCommitment comm;
   std::vector<uint8_t> serialize() const;  // bincode (r1cs.rs:50-56, sparse_mlpoly.rs:320-327, dense_mlpoly.rs:42-45)
+  // the bytes serialize() writes, UNTRUSTED, into *out (verifier.cc): what a verifier holds of a circuit — it never has the decommitment. False
+  // for truncated input, trailing bytes, a length that does not fit the bytes that remain, batch_size != 3, a share vector that is empty, not a
+  // power of two or longer than 65536, or one whose size is not what encode gives for num_ops / num_mem_cells. Never throws.
+  static bool deserialize(const uint8_t* bytes, size_t len, ComputationCommitment* out);
+};
+// The two share vectors of a ComputationCommitment as resident point sets of the device (sp_points: decoded once, window tables in HBM), for
+// the verifier of many proofs over one circuit (spz_commitment_load makes them). SNARK::verify wants both: there is one path.
+struct ResidentCommitment {
+  const sp_points *ops = nullptr, *mem = nullptr;  // comm.comm_comb_ops.C, comm.comm_comb_mem.C
 };
 struct ComputationDecommitment {  // lib.rs:50-54 -> r1cs.rs:67-70
   MultiSparseMatPolynomialAsDense dense;
@@ -317,6 +325,15 @@ struct SNARK {  // lib.rs:311-467
     return prove(ctx, inst, comm, decomm, nullptr, vars.n, inputs, gens, transcript, tape_seed, times, vars.tab.h);
   }
   std::vector<uint8_t> serialize() const;  // bincode 1.3 default encoding
+  // bincode of an UNTRUSTED proof into *out (verifier.cc), under the rules of NIZK::deserialize: every Vec length — the nested Vec<Vec<Scalar>> of
+  // compressed_polys and the Vec<LayerProofBatched> included — is checked against the bytes that remain before anything is allocated. Never throws.
+  static bool deserialize(const uint8_t* bytes, size_t len, SNARK* out);
+  // SNARK::verify (lib.rs:423-466) against a computation commitment: 1 accept, 0 reject. R1CSProof::verify takes the proof's inst_evals, the
+  // sparse-polynomial evaluation proof binds them to the commitment; the four C_LZ multi-scalar multiplications run on the device (placement:
+  // verifier.cc). Throws Error("InvalidNumberOfInputs") for a wrong number of inputs (lib.rs:437), Error for a device failure; a proof that is
+  // merely wrong, has a vector of the wrong length, or carries undecodable points, is a 0.
+  int verify(Ctx& ctx, const ComputationCommitment& comm, const FqVec& inputs, Transcript& transcript, const SNARKGens& gens,
+             const ResidentCommitment& resident) const;
 };
 struct NIZK {  // lib.rs:488-587
   R1CSProof r1cs_sat_proof;

@@ -11,13 +11,15 @@ ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
 H = ctypes.CDLL(HOST_PATH)
 for f in ("spz_ctx_new", "spz_instance_new", "spz_instance_synthetic", "spz_snark_gens_new", "spz_nizk_gens_new", "spz_snark_encode",
           "spz_snark_prove", "spz_nizk_prove", "spz_ctx_raw", "spz_vars_assignment_new", "spz_snark_prove_resident", "spz_nizk_prove_resident",
-          "spz_snark_prove_t", "spz_nizk_prove_t"):
+          "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load"):
     getattr(H, f).restype = vp
 for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode"):
     getattr(H, f).restype = sz
 H.spz_last_error.restype = ctypes.c_char_p
-H.spz_nizk_parse_probe.restype = ctypes.c_longlong
-for f in ("spz_ctx_free", "spz_instance_free", "spz_snark_gens_free", "spz_nizk_gens_free", "spz_encode_free", "spz_proof_free", "spz_vars_assignment_free"):
+for f in ("spz_nizk_parse_probe", "spz_snark_reserialize", "spz_commitment_reserialize"):
+    getattr(H, f).restype = ctypes.c_longlong
+for f in ("spz_ctx_free", "spz_instance_free", "spz_snark_gens_free", "spz_nizk_gens_free", "spz_encode_free", "spz_proof_free", "spz_vars_assignment_free",
+          "spz_commitment_free"):
     getattr(H, f).argtypes = [vp]
 u64p = ctypes.POINTER(ctypes.c_uint64)
 TIME_NAMES = ["polycommit", "prove_sc_phase_one", "prove_sc_phase_two", "polyeval", "R1CSProof::prove", "eval_sparse_polys",
@@ -249,6 +251,46 @@ class SNARK:
         return _proof_bytes(p)
 
 
+    @staticmethod
+    def verify_status(ctx, comm, proof_bytes, inputs, gens, transcript_label):
+        """SNARK::verify (lib.rs:423-466) of untrusted proof bytes against a Commitment, on the device: 1 accept, 0 reject, -1 malformed bytes.
+        `inputs`: Montgomery limbs (a ctypes uint64 array). Raises SpartanHipError("InvalidNumberOfInputs") when their number is not the
+        commitment's num_inputs, as NIZK.verify_status does."""
+        rc = H.spz_snark_verify(ctx.h, comm.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(len(inputs) // 4), transcript_label)
+        if rc < -1:
+            raise SpartanHipError(f"SNARK::verify failed: {H.spz_last_error().decode()}")
+        return int(rc)
+
+    @staticmethod
+    def verify(ctx, comm, proof_bytes, inputs, gens, transcript_label):
+        """True when the proof is accepted; False for a rejected AND for a malformed proof (verify_status tells them apart)"""
+        return SNARK.verify_status(ctx, comm, proof_bytes, inputs, gens, transcript_label) == 1
+
+    @staticmethod
+    def verify_t(ctx, comm, proof_bytes, inputs, gens, transcript_state):
+        """SNARK::verify on a caller-owned transcript: the 203-byte state (see prove_t) is continued by the verification and left in the state
+        it ends in — after an accepted proof, the state SNARK.prove_t left on the prover's side. Returns the status of verify_status."""
+        rc = H.spz_snark_verify_t(ctx.h, comm.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(len(inputs) // 4), transcript_state)
+        if rc < -1:
+            raise SpartanHipError(f"SNARK::verify failed: {H.spz_last_error().decode()}")
+        return int(rc)
+
+
+class Commitment:
+    """the verifier's handle of a circuit: a ComputationCommitment parsed from its (untrusted) bincode bytes"""
+    def __init__(self, h):
+        self.h = h
+
+    @staticmethod
+    def load(ctx, comm_bytes):
+        """raises SpartanHipError for bytes that are not one commitment (ComputationCommitment::deserialize, libspartan.hpp)"""
+        return Commitment(_chk(H.spz_commitment_load(ctx.h, bytes(comm_bytes), sz(len(comm_bytes))), "Commitment.load"))
+
+    def free(self):
+        if self.h:
+            H.spz_commitment_free(self.h); self.h = None
+
+
 class NIZK:
     @staticmethod
     def prove_t(ctx, inst, vars_, inputs, gens, transcript_state, tape_seed):
@@ -323,6 +365,10 @@ class Encoded:
         n = H.spz_commitment_bincode(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
         H.spz_commitment_bincode(self.h, b, sz(n))
         return bytes(b)
+
+    def commitment(self, ctx):
+        """the Commitment a verifier would load from serialize_commitment()"""
+        return Commitment.load(ctx, self.serialize_commitment())
 
     def serialize_decommitment(self):
         n = H.spz_decommitment_bincode(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
