@@ -558,7 +558,12 @@ int32_t msm_launch(sp_ctx* c, const sp_gens* g, const Fq* dZ, size_t z_stride, s
         hipLaunchKernelGGL((k_msm_reduce<true, false>), dim3((unsigned)rows), dim3(256), 0, c->stream, (const void*)part, nblk, sums_dst, (const unsigned*)nullptr);
       }
     } else {
-      if (idx_row_stride) return SP_EINVAL;  // per-row index lists exist on the lookup+tree path only
+      if (idx_row_stride) {  // per-row index lists exist on the lookup+tree path only: longer rows go out one at a time, each with its own list
+        for (size_t r = 0; r < rows; r++)  // (an inner-product round of more than 2^19 lookups that is not fusable: n0 = 32768, or 16384 at narrow windows)
+          SPCHK(msm_launch(c, g, dZ + r * z_stride, z_stride, 1, cols, g_off, didx + r * idx_row_stride, dblinds ? dblinds + r : nullptr, h_idx,
+                           out_host ? out_host + 32 * r : nullptr, 0, points_out ? points_out + r : nullptr));
+        return SP_OK;
+      }
       const unsigned* qcounts = msm_enqueue_sums(c, c->stream, m, g, dZ, z_stride, rows, cols, g_off, didx, dblinds, h_idx, (uint8_t*)c->scratch);
       msm_enqueue_reduce(c, c->stream, m, rows, (uint8_t*)c->scratch, sums_dst, false, nullptr, qcounts);
     }

@@ -286,7 +286,8 @@ constexpr size_t SP_HOST_ENCODE_ROWS = 8;  // commitments of up to this many row
 extern "C" int32_t msm_launch(sp_ctx* c, const sp_gens* g, const Fq* dZ, size_t z_stride, size_t rows, size_t cols, size_t g_off,
                               const uint32_t* didx, const Fq* dblinds, size_t h_idx, uint8_t* out_host, size_t idx_row_stride = 0,
                               Pt* points_out = nullptr /* rows <= 8: the row sums as extended points instead of encodings */);
-// idx_row_stride: 0 = every row uses idx[0..cols); otherwise row r uses idx[r*idx_row_stride ..] (latency path only)
+// idx_row_stride: 0 = every row uses idx[0..cols); otherwise row r uses idx[r*idx_row_stride ..] (rows <= 8; rows of more lookups than the
+// lookup+tree path takes go out one launch each)
 
 // gathered wide-window forms of the row MSM (msm_rows.hip): enqueue of the lookups, partial[row][P] extended points (the reduction is the
 // caller's). WINDOWS: one lookup per thread, P = (cols + blind) x windows; STRIP: P strips of `strip` columns (on a background stream the

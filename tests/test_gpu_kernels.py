@@ -113,7 +113,8 @@ def test_commit_rows_at_every_window_width(ctx, orc, wbits, monkeypatch):
     """the window geometry is a property of the generator set, chosen at upload (gens.hip choose_geom): every uniform width (option
     msm.wbits) and every number of MIXED-width windows (option msm.windows, the negative parameters: 17 = 1 x 14 + 16 x 15 bits, 18 = 16 x
     14 + 2 x 15, ... 32 = 2 x 7 + 30 x 8: msm.hpp) gives the same commitments through every launch plan (one-launch small, windowed trees,
-    row strips, the queue form, the indexed lookups of the inner-product argument)"""
+    row strips, the queue form, the indexed lookups of sp_msm_indexed; the digit path of the inner-product argument's own kernel, k_ipa_round, is
+    in tests/test_gpu_ipa_edges.py)"""
     from spartan_amd import capi
     if wbits > 0:
         ctx.set_option("msm.wbits", wbits)   # read when a generator set is built

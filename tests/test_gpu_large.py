@@ -3,7 +3,8 @@ small-shape tests in test_gpu_kernels.py reach only the latency forms; the small
 sum-check, product trees, hash layers and reductions on field edge values, at every boundary of their dispatch - are in
 test_gpu_spark_edges.py): >= 2^17 elements for the F_q streaming kernels
 (k_eq_outer, k_cubic_*_batched, k_sc_bind_eval, k_dot_many, k_dot3, k_spmv, k_eval_table, k_sparse_eval, k_hash_layer),
-n = 4096 for the inner-product argument, and the full 1024 x 1024 witness-sized commit on every row (k_msm_rows with the
+n = 4096 for the inner-product argument (its other sizes, edge values, window geometries and call orders are in test_gpu_ipa_edges.py, on the
+model of tests/ipa_reference.py, from which the folded-generator reference used here comes), and the full 1024 x 1024 witness-sized commit on every row (k_msm_rows with the
 XCD tile order, and the persistent half-chip k_msm_rows_bg).
 
 Ground truth: the oracle where it exports the operation (orc_eq_evals, orc_sumcheck_eval, orc_bound_top, orc_commit_rows,
@@ -316,51 +317,41 @@ def test_vecmat_and_evaluate_large_match_oracle(ctx, orc):
 
 
 def _ipa_against_folded_generators(ctx, orc, n, comp, a, b, rng):
-    """BulletReductionProof::prove (nizk/bullet.rs:32-132) as the reference computes it — G folded every round,
-    L = <a_L, G_R> + c_L Q + blind_L H over the FOLDED generators — through the oracle's point arithmetic only
-    (orc_pt_msm), against sp_ipa_*, which never folds G (fixed-base rows over the original generators).
+    """sp_ipa_*, which never folds G (fixed-base rows over the original generators), against BulletReductionProof::prove as the reference
+    computes it (tests/ipa_reference.py, folded_reference: G folded every round, every point through orc_pt_msm). The blinds, challenges and
+    d, r come from rng in the order this helper always drew them (ipa_reference.make_script).
     comp: n + 2 compressed points, G[0..n), Q = P[n], H = P[n+1]."""
     from spartan_amd import capi
+    from tests import ipa_reference as I
     g = capi.Gens(ctx, compressed=comp)
     P = [comp[32 * i:32 * i + 32] for i in range(n + 2)]
     a, b = list(a), list(b)
-    qs = rng.getrandbits(250)
+    script = I.make_script(n, rng)
+    want = I.folded_reference(orc, P, a, b, script)
+    qs = script["q_scale"]
     ipa = vp()
     assert capi.lib.sp_ipa_begin(ctx.h, g.h, sz(0), sz(n), sz(n), sz(n + 1), fq1(qs), mont_bulk(a), mont_bulk(b), ctypes.byref(ipa)) == 0
     out = (ctypes.c_uint8 * 32)()
-
-    def msm(scalars, points):
-        assert orc.orc_pt_msm(mont_bulk(scalars), b"".join(points), sz(len(points)), out) == 1
-        return bytes(out)
-    Qp = msm([qs], [P[n]])   # gens_1.scale(r) (nizk/mod.rs:479-480)
-    G = P[:n]
-    cur = n
-    while cur > 1:
-        h = cur // 2
-        bl, br = rng.getrandbits(250), rng.getrandbits(249)
-        cL = sum(a[i] * b[h + i] for i in range(h)) % Q
-        cR = sum(a[h + i] * b[i] for i in range(h)) % Q
-        wantL = msm(a[:h] + [cL, bl], G[h:] + [Qp, P[n + 1]])     # bullet.rs:83-89
-        wantR = msm(a[h:] + [cR, br], G[:h] + [Qp, P[n + 1]])     # :91-97
-        L = (ctypes.c_uint8 * 32)(); Rr = (ctypes.c_uint8 * 32)()
-        assert capi.lib.sp_ipa_round_lr(ipa, fq1(bl), fq1(br), L, Rr) == 0
-        assert bytes(L) == wantL and bytes(Rr) == wantR, cur
-        u = rng.getrandbits(251) | 1
-        ui = pow(u, Q - 2, Q)
-        assert capi.lib.sp_ipa_round_fold(ipa, fq1(u), fq1(ui)) == 0
-        a = [(a[i] * u + ui * a[h + i]) % Q for i in range(h)]     # :105-106
-        b = [(b[i] * ui + u * b[h + i]) % Q for i in range(h)]
-        G = [msm([ui, u], [G[i], G[h + i]]) for i in range(h)]     # :108
-        cur = h
+    cur, k = n, 0
+    for st in script["steps"]:
+        if st[0] == "round":
+            L = (ctypes.c_uint8 * 32)(); Rr = (ctypes.c_uint8 * 32)()
+            assert capi.lib.sp_ipa_round_lr(ipa, fq1(st[1]), fq1(st[2]), L, Rr) == 0
+            assert bytes(L) == want["L"][k] and bytes(Rr) == want["R"][k], cur
+            k += 1
+        else:
+            assert capi.lib.sp_ipa_round_fold(ipa, fq1(st[1]), fq1(st[2])) == 0
+            cur //= 2
+    a, b = [want["a_hat"]], [want["b_hat"]]
     ah = (ctypes.c_uint64 * 4)(); bh = (ctypes.c_uint64 * 4)(); gh = (ctypes.c_uint8 * 32)()
-    d, r = rng.getrandbits(250), rng.getrandbits(250)
-    want_delta = msm([d, r], [G[0], P[n + 1]])                     # nizk/mod.rs:496-501
+    d, r = script["d"], script["r"]
+    want_delta = want["delta"]                                     # nizk/mod.rs:496-501
     # the end of the argument in one call: on the calling thread's core from the last round's row sums (ipa.hip, ipa_finish_on_host) ...
     assert capi.lib.sp_ipa_finish_commit(ipa, fq1(d), fq1(r), ah, bh, out) == 0
     assert from_mont_bulk(ah, 1) == a and from_mont_bulk(bh, 1) == b and bytes(out) == want_delta
     # ... and on the device (the fold applied, g_hat as a fixed-base row over all n generators)
     assert capi.lib.sp_ipa_finish(ipa, ah, bh, gh) == 0
-    assert from_mont_bulk(ah, 1) == a and from_mont_bulk(bh, 1) == b and bytes(gh) == G[0]
+    assert from_mont_bulk(ah, 1) == a and from_mont_bulk(bh, 1) == b and bytes(gh) == want["g_hat"]
     assert capi.lib.sp_ipa_commit_ghat(ipa, fq1(d), fq1(r), out) == 0
     assert bytes(out) == want_delta
     capi.lib.sp_ipa_free(ipa)
