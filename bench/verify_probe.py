@@ -10,7 +10,10 @@ The reference publishes 414.5 ms for NIZK::verify at 2^20 on its own machine (BA
 through the resident point sets of the commitment, sp_msm_points) and the oracle's orc_snark_verify_bytes.
 --what msm: sp_msm_points against sp_msm_var on identical points and scalars (n = 2048, 4096), the calls interleaved in one process, 20 samples
 each after 3 warm pairs: median and spread (min .. max) per call, the table build (sp_points_upload) beside them.
-usage: python bench/verify_probe.py [--what nizk|snark|msm] [--out profiles/nizk_verify.txt] [--sizes 16,20,22]"""
+--what snark_many --batch 1,4,16,64: SNARK.verify_many of K proofs of one circuit (lock step: spartan_amd/host/batch_gate.hpp) against K sequential
+SNARK.verify calls on the same proofs, the two interleaved sample by sample in one process: ms per batch and per proof, round trips, and the
+device time of the two variable-base MSM families per launch chain.
+usage: python bench/verify_probe.py [--what nizk|snark|msm|snark_many] [--out profiles/nizk_verify.txt] [--sizes 16,20,22] [--batch 1,4,16,64]"""
 import argparse, ctypes, faulthandler, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,6 +113,62 @@ def snark(args, orc):
     return lines
 
 
+def snark_many(args, orc):
+    label = b"snark_example"
+    DISTINCT = 4
+    lines = ["SNARK::verify_many (K proofs of one circuit in lock step) against K sequential SNARK::verify calls (bench/verify_probe.py --what snark_many; "
+             "host CPU: %s, %d CPUs for this process)" % (cpu_model(), len(os.sched_getaffinity(0))),
+             "per K: %d warm pairs, then %d samples of (one verify_many, K verify calls) interleaved on the host clock, medians; a batch holds %d distinct "
+             "proofs (tape seeds) in rotation; msm_var / msm_points: HIP events around their launch chains, runs of their own" % (WARM, REPS, DISTINCT),
+             ""]
+    ctx = P.Ctx(0)
+    raw = ctx.raw()
+    med = lambda ts: sorted(ts)[len(ts) // 2]
+    for s in [int(x) for x in args.sizes.split(",")]:
+        N, ni, seed = 1 << s, 10, s
+        inst = P.Instance.produce_synthetic_r1cs(ctx, N, N, ni, seed=seed)
+        gens = P.SNARKGens(ctx, N, N, ni, N)
+        enc = P.SNARK.encode(ctx, inst, gens)
+        distinct = [P.SNARK.prove(ctx, inst, enc, inst.vars, inst.inputs, gens, label, P.seed_scalar(b"tape", seed + 100 * i)) for i in range(DISTINCT)]
+        comm = P.Commitment.load(ctx, enc.serialize_commitment())
+        single = lambda p: P.SNARK.verify_status(ctx, comm, p, inst.inputs, gens, label)
+        lines.append("synthetic 2^%d: proof %d bytes" % (s, len(distinct[0])))
+        print(lines[-1], flush=True)
+        for K in [int(x) for x in args.batch.split(",")]:
+            batch = [distinct[i % DISTINCT] for i in range(K)]
+            many = lambda: P.SNARK.verify_many(ctx, comm, batch, inst.inputs, gens, label)
+            seq = lambda: [single(p) for p in batch]
+            if many() != [1] * K or seq() != [1] * K:
+                raise SystemExit("2^%d, K = %d: a proof of the prover was not accepted" % (s, K))
+            tm, ts = [], []
+            for i in range(WARM + REPS):
+                t0 = time.perf_counter(); many(); t1 = time.perf_counter(); seq(); t2 = time.perf_counter()
+                if i >= WARM:
+                    tm.append((t1 - t0) * 1e3); ts.append((t2 - t1) * 1e3)
+            t0 = L.sp_ctx_trips(raw); many(); trips_m = L.sp_ctx_trips(raw) - t0
+            t0 = L.sp_ctx_trips(raw); seq(); trips_s = L.sp_ctx_trips(raw) - t0
+            fam = {}
+            for name, fn in (("many", many), ("seq", seq)):
+                L.sp_prof_enable(raw, ctypes.c_int(1)); L.sp_prof_reset(raw)
+                for _ in range(3):
+                    fn()
+                fam[name] = (family(raw, "msm_var"), family(raw, "msm_points"))
+                L.sp_prof_enable(raw, ctypes.c_int(0))
+            chain = lambda f: "%.3f ms (of %d)" % (f[0] / max(f[1], 1), f[1])
+            mm, sm = med(tm), med(ts)
+            lines += ["  K = %2d  verify_many   median %9.3f ms a batch = %8.3f ms a proof   (min %.3f, max %.3f), %d round trips a batch" % (
+                          K, mm, mm / K, min(tm), max(tm), trips_m),
+                      "          K x verify    median %9.3f ms         = %8.3f ms a proof   (min %.3f, max %.3f), %d round trips" % (
+                          sm, sm / K, min(ts), max(ts), trips_s),
+                      "          launch chains: verify_many msm_var %s, msm_points %s; verify msm_var %s, msm_points %s" % (
+                          chain(fam["many"][0]), chain(fam["many"][1]), chain(fam["seq"][0]), chain(fam["seq"][1])),
+                      "          sequential / batched = %.2f per proof%s" % (sm / mm, "" if sm >= mm else "   (the batch is SLOWER per proof)")]
+            print("\n".join(lines[-4:]), flush=True)
+        comm.free(); enc.free(); gens.free(); inst.free()
+    ctx.close()
+    return lines
+
+
 def msm(args, orc):
     import random
     from tests import msm_var_cases as M
@@ -162,12 +221,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="16,20,22")
-    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm"])
+    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm", "snark_many"])
+    ap.add_argument("--batch", default="1,4,16,64", help="--what snark_many: the batch sizes K")
     args = ap.parse_args()
     orc = load_oracle()
     orc.orc_set_threads(ctypes.c_int(16))
     if args.what != "nizk":
-        return finish(args, snark(args, orc) if args.what == "snark" else msm(args, orc))
+        return finish(args, {"snark": snark, "msm": msm, "snark_many": snark_many}[args.what](args, orc))
     lines = ["NIZK::verify on the device against the oracle's verifier on the host (bench/verify_probe.py; host CPU: %s)" % cpu_model(),
              "(a): median of %d warm calls, host clock; msm_var: HIP events around its launch chain, runs of their own; (c): median of 3, 16 threads" % REPS,
              ""]

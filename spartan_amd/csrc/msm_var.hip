@@ -14,35 +14,9 @@
 // Point operations on the critical path: 7 + 8 (6 shuffle levels + 2 LDS) + ceil(nblocks / 4) + 2 + 63 * 5 + the encode, i.e. ~335 for
 // n <= 1024 of which 252 are the doublings no schedule avoids; in all 7 n + 64 n + 315 operations. One round trip.
 #include "internal.hpp"
+#include "msm_var.hpp"
 
 namespace {
-constexpr size_t MV_MAX_N = 65536;
-constexpr int MV_BLOCK = 256;
-
-__device__ __forceinline__ Pt pt_shfl_down(const Pt& p, int delta) {
-  Pt r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    r.X.v[i] = __shfl_down((unsigned long long)p.X.v[i], delta, 64);
-    r.Y.v[i] = __shfl_down((unsigned long long)p.Y.v[i], delta, 64);
-    r.Z.v[i] = __shfl_down((unsigned long long)p.Z.v[i], delta, 64);
-    r.T.v[i] = __shfl_down((unsigned long long)p.T.v[i], delta, 64);
-  }
-  return r;
-}
-
-// The sum of one term per lane over a block of MV_BLOCK lanes, shared by the window kernels of sp_msm_var and sp_msm_points: 6 wavefront
-// shuffle levels, then the 4 wavefront sums through LDS; lane 0 writes the block's sum. EVERY lane of the block must call it (no early exit
-// before it): lane 0 of each wavefront ends with the sum of its 64 terms.
-__device__ __forceinline__ void msmv_block_sum(Pt p, Pt* sm /*[MV_BLOCK / 64], shared*/, Pt* __restrict__ out) {
-  const int t = threadIdx.x;
-#pragma unroll 1
-  for (int delta = 32; delta > 0; delta >>= 1) p = pt_add(p, pt_shfl_down(p, delta));
-  if ((t & 63) == 0) sm[t >> 6] = p;
-  __syncthreads();
-  if (t == 0) *out = pt_add(pt_add(sm[0], sm[1]), pt_add(sm[2], sm[3]));
-}
-
 __global__ void __launch_bounds__(64) k_msmv_prepare(const uint8_t* __restrict__ enc, const Fq* __restrict__ S, size_t n, Pt* __restrict__ table,
                                                      int8_t* __restrict__ digits /*[64][n]*/, int* __restrict__ bad) { SP_FG_PRIO();
   const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -225,12 +199,6 @@ extern "C" int32_t sp_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* 
   memcpy(out, res, 32);
   return SP_OK;
 }
-
-struct sp_points {
-  int dev;
-  size_t n;
-  Pt* table;  // [64 windows][n][8]: table[(w * n + j) * 8 + m - 1] = m 16^w P[j]
-};
 
 extern "C" int32_t sp_points_upload(sp_ctx* c, const uint8_t* compressed, size_t n, sp_points** out) {
   if (!c || !compressed || !out || n == 0 || n > MV_MAX_N) return SP_EINVAL;

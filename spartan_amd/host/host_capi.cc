@@ -480,6 +480,36 @@ int spz_snark_verify_t(void* ctx, void* comm, void* gens, const uint8_t* proof, 
     return -2;
   }
 }
+// SNARK::verify_many: K untrusted proofs of one circuit against a loaded commitment, in lock step on the device (libspartan.hpp). Fills
+// status_out[k] with 1 accept, 0 reject, -1 malformed bytes and returns 0. Returns -2 with spz_last_error() for an error of the CALL — bad
+// arguments, n_inputs that is not the commitment's ("InvalidNumberOfInputs", before anything runs), a device failure, whose text is carried
+// over from the worker thread it happened on; status_out is then all -2: nothing is reported as accepted. K = 0 is legal and does nothing.
+int spz_snark_verify_many(void* ctx, void* comm, void* gens, const uint8_t* const* proofs, const size_t* proof_lens, const uint64_t* const* inputs,
+                          size_t n_inputs, size_t K, const char* transcript_label, int* status_out) {
+  try {
+    g_err.clear();
+    if (!ctx || !comm || !gens || !transcript_label || (K && (!proofs || !proof_lens || !status_out || (n_inputs && !inputs))))
+      throw Error("spz_snark_verify_many: bad arguments");
+    for (size_t k = 0; k < K; k++) status_out[k] = -2;
+    std::vector<std::pair<const uint8_t*, size_t>> pv(K);
+    std::vector<FqVec> in(K);
+    std::vector<const FqVec*> inp(K);
+    for (size_t k = 0; k < K; k++) {
+      if (!proofs[k] || (n_inputs && !inputs[k])) throw Error("spz_snark_verify_many: bad arguments");
+      pv[k] = std::make_pair(proofs[k], proof_lens[k]);
+      in[k] = limbs_vec(n_inputs ? inputs[k] : nullptr, n_inputs);
+      inp[k] = &in[k];
+    }
+    const CommH& h = *(CommH*)comm;
+    if (K && n_inputs != h.comm.num_inputs) throw Error("InvalidNumberOfInputs");
+    std::vector<int> v = SNARK::verify_many(*(Ctx*)ctx, h.comm, pv, inp, transcript_label, *(SNARKGens*)gens, ResidentCommitment{h.ops, h.mem});
+    for (size_t k = 0; k < K; k++) status_out[k] = v[k];
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -2;
+  }
+}
 // no GPU, no context: SNARK::deserialize, then SNARK::serialize. Returns the number of bytes (written when cap suffices), -1 when malformed.
 long long spz_snark_reserialize(const uint8_t* proof, size_t len, uint8_t* out, size_t cap) {
   try {

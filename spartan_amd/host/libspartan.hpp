@@ -15,6 +15,7 @@
 #include <stdexcept>
 #include <string>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "../../include/spartan_hip.h"
@@ -334,6 +335,16 @@ struct SNARK {  // lib.rs:311-467
   // merely wrong, has a vector of the wrong length, or carries undecodable points, is a 0.
   int verify(Ctx& ctx, const ComputationCommitment& comm, const FqVec& inputs, Transcript& transcript, const SNARKGens& gens,
              const ResidentCommitment& resident) const;
+  // K UNTRUSTED proofs (bytes, length) of one circuit, each verified by verify() itself under a transcript of its own made from
+  // `transcript_label`, one host thread a proof, in lock step: the threads meet at the three blocking device calls of a verification
+  // (batch_gate.hpp) and the requests of one shape go out as ONE call (sp_msm_var_many, sp_msm_points_many, sp_commit_rows with rows = K) — 8
+  // round trips for a batch of up to 64 proofs instead of 8 each. No combined equation: every proof gets the verdict verify() gives it, 1 accept,
+  // 0 reject, -1 malformed bytes (these never start a thread); a proof that is rejected leaves the lock step without holding the others up.
+  // Lists longer than 64 are cut into batches of 64. inputs[k] belongs to proofs[k]. Throws Error("InvalidNumberOfInputs") before anything
+  // runs when one of them has another size than the commitment's; Error for a device failure (then no verdict is given at all).
+  static std::vector<int> verify_many(Ctx& ctx, const ComputationCommitment& comm, const std::vector<std::pair<const uint8_t*, size_t>>& proofs,
+                                      const std::vector<const FqVec*>& inputs, const char* transcript_label, const SNARKGens& gens,
+                                      const ResidentCommitment& resident);
 };
 struct NIZK {  // lib.rs:488-587
   R1CSProof r1cs_sat_proof;

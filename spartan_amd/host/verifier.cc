@@ -12,15 +12,20 @@
 //   the SPARK sum-checks            calling thread: field arithmetic over the proof's scalars and the transcript, no groups (SumcheckInstanceProof,
 //                                   ProductCircuitEvalProofBatched, ProductLayerProof, HashLayerProof::verify_helper)
 //   point equalities                comparisons of 32-byte encodings
+// SNARK::verify_many (at the end of the file) runs K of these verifications on K threads; their C_LZ and G_hat calls then meet at a gate
+// (batch_gate.hpp) and go out once per batch: sp_msm_var_many, sp_msm_points_many, sp_commit_rows with K rows.
 // Verdicts: 1 accept, 0 reject, -1 malformed bytes. The input is untrusted: where the reference panics on attacker-controlled data
 // (decompress().unwrap() at dense_mlpoly.rs:382, r1csproof.rs:409, nizk/mod.rs:239; the length asserts of sumcheck.rs:38,44,97-98, nizk/mod.rs:381,
 // 536-537, product_tree.rs:395,417-418,425, sparse_mlpoly.rs:167,861-883,910,922-930,1238-1268,1379-1381,1531 and the slice indices next to
 // them; assert_eq!(rx, claimed_rx) at lib.rs:580-581) this returns 0. r1cs_verify takes the three evaluations from its caller, as
 // R1CSProof::verify does (r1csproof.rs:351-359): NIZK::verify computes them, SNARK::verify hands over the proof's.
 #include "libspartan.hpp"
+#include "batch_gate.hpp"
 #include "fq_inv.hpp"
 
+#include <algorithm>
 #include <functional>
+#include <thread>
 
 namespace spz {
 using namespace sp;
@@ -82,6 +87,48 @@ CP commit_gens(const sp_gens* g, const std::vector<uint32_t>& idx, const FqVec& 
   CP out;
   spx(sp_host_commit_small(g, idx.data(), idx.size(), U(s), 1, nullptr, out.data()), "sp_host_commit_small");
   return out;
+}
+
+// ---- the three blocking device calls of a verification. A verification run by SNARK::verify_many has a gate (batch_gate.hpp) on its thread:
+// the call is then POSTED there and answered by the batch's leader, who issues one device call for all the requests of the same shape. Without
+// a gate (every single-proof verifier) the call goes straight to the device. Requests that may share a call have equal keys:
+//   (var, n)                     sp_msm_var over n points of the proof        -> sp_msm_var_many
+//   (points, set, n)             sp_msm_points over a resident set            -> sp_msm_points_many
+//   (rows, gens, g_off, h, n)    sp_commit_rows of one unblinded row          -> sp_commit_rows with rows = the group's size
+struct DevKey {
+  enum Kind { VAR, POINTS, ROWS } kind;
+  const void* obj;  // the sp_points or the sp_gens; null for VAR
+  size_t g_off, h, n;
+  bool operator<(const DevKey& o) const {
+    if (kind != o.kind) return kind < o.kind;
+    if (obj != o.obj) return std::less<const void*>()(obj, o.obj);
+    if (g_off != o.g_off) return g_off < o.g_off;
+    if (h != o.h) return h < o.h;
+    return n < o.n;
+  }
+};
+struct DevReq { const uint8_t* points; const uint64_t* S; };  // n encodings (VAR only) and n scalars, alive while the member waits
+struct DevAns { int32_t rc = SP_OK; CP out{}; };
+typedef BatchGate<DevKey, DevReq, DevAns> VerifyGate;
+struct GateSeat { VerifyGate* gate = nullptr; size_t member = 0; };
+thread_local GateSeat tl_seat;  // set by a worker thread of verify_many for its lifetime; null on every other thread
+
+void dev_answer(const DevKey& key, const DevReq& req, uint8_t out[32], const char* what) {
+  DevAns a = tl_seat.gate->post(tl_seat.member, key, req);
+  spx(a.rc, what);
+  memcpy(out, a.out.data(), 32);
+}
+void dev_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t n, uint8_t out[32]) {
+  if (!tl_seat.gate) spx(sp_msm_var(c, points, S, n, out), "sp_msm_var");
+  else dev_answer(DevKey{DevKey::VAR, nullptr, 0, 0, n}, DevReq{points, S}, out, "sp_msm_var_many");
+}
+void dev_msm_points(sp_ctx* c, const sp_points* set, const uint64_t* S, size_t n, uint8_t out[32]) {
+  if (!tl_seat.gate) spx(sp_msm_points(c, set, S, n, out), "sp_msm_points");  // SP_EINVAL for another size cannot happen: the caller required it
+  else dev_answer(DevKey{DevKey::POINTS, set, 0, 0, n}, DevReq{nullptr, S}, out, "sp_msm_points_many");
+}
+void dev_commit_row(sp_ctx* c, const sp_gens* g, size_t g_off, size_t h, const uint64_t* S, size_t n, uint8_t out[32]) {
+  if (!tl_seat.gate) spx(sp_commit_rows(c, g, g_off, h, S, 1, n, nullptr, out), "sp_commit_rows");
+  else dev_answer(DevKey{DevKey::ROWS, g, g_off, h, n}, DevReq{nullptr, S}, out, "sp_commit_rows");
 }
 
 // ---- nizk/mod.rs ----
@@ -163,7 +210,7 @@ void bullet_verify(sp_ctx* c, const BulletReductionProof& p, size_t n, const FqV
     s[i] = s[i - ((size_t)1 << lg_i)] * u_sq[(lg_n - 1) - lg_i];
   }
   // G_hat = <s, G> (:213): fixed bases, the device's window tables
-  spx(sp_commit_rows(c, gn.g, gn.G[0], gn.h, U(s), 1, n, nullptr, g_hat->data()), "sp_commit_rows");
+  dev_commit_row(c, gn.g, gn.G[0], gn.h, U(s), n, g_hat->data());
   *a_hat = dot(a, s);                                          // :214
   Terms g;                                                     // :216-222
   for (size_t i = 0; i < lg_n; i++) g.add(p.L_vec[i], u_sq[i]);
@@ -201,8 +248,8 @@ void polyeval_verify(sp_ctx* c, const PolyEvalProof& p, const PolyCommitmentGens
   FqVec L = eq_evals(r, left), R = eq_evals(r + left, ell - left);
   CP C_LZ;  // :382-384, over the commitment shares the proof carries
   static_assert(sizeof(CP) == 32, "CP is 32 packed bytes");
-  if (resident) spx(sp_msm_points(c, resident, U(L), L.size(), C_LZ.data()), "sp_msm_points");  // SP_EINVAL for another size cannot happen: required above
-  else spx(sp_msm_var(c, comm.C[0].data(), U(L), L.size(), C_LZ.data()), "sp_msm_var");
+  if (resident) dev_msm_points(c, resident, U(L), L.size(), C_LZ.data());
+  else dev_msm_var(c, comm.C[0].data(), U(L), L.size(), C_LZ.data());
   dotproductlog_verify(c, p.proof, R.size(), gens.gens, gb, t, R, C_LZ, C_Zr);
 }
 // ZKSumcheckInstanceProof::verify (sumcheck.rs:84-179)
@@ -707,6 +754,111 @@ int SNARK::verify(Ctx& ctx, const ComputationCommitment& comm, const FqVec& inpu
     return 0;
   }
   return 1;
+}
+
+// ---- SNARK::verify_many: K proofs of one circuit, each verified by SNARK::verify itself on a thread of its own, in lock step through a gate.
+namespace {
+constexpr size_t kVerifyBatch = 64;              // proofs (threads) in lock step; a longer list is cut into batches of this size
+
+// The batch leader's side of the gate: one device call for a group of requests with equal keys. Runs on one thread at a time, and it is the
+// only code of a batch that touches the context. A device failure is thrown: every member of the rendezvous gets it.
+void serve_group(sp_ctx* c, const DevKey& key, const std::vector<const DevReq*>& reqs, std::vector<DevAns>& answers) {
+  const size_t G = reqs.size(), n = key.n;
+  answers.assign(G, DevAns());
+  std::vector<uint64_t> S;
+  std::vector<uint8_t> pts, out;
+  std::vector<int32_t> status;
+  auto failed = [](const char* what, int32_t rc) { return Error(std::string(what) + " failed: " + sp_strerror(rc) + " (" + std::to_string(rc) + ")"); };
+  // the group in calls of at most `step` members: the whole group unless n K passes the library's cap (n >= 2^14 at 64 proofs)
+  size_t step = n && SP_MSM_MANY_MAX_TERMS / n ? SP_MSM_MANY_MAX_TERMS / n : 1;
+  if (step > SP_MSM_MANY_MAX_K) step = SP_MSM_MANY_MAX_K;
+  if (key.kind == DevKey::ROWS) step = G;
+  for (size_t k0 = 0; k0 < G; k0 += step) {
+    const size_t k = std::min(step, G - k0);
+    S.resize(4 * n * k);
+    out.assign(32 * k, 0);
+    for (size_t i = 0; i < k; i++) memcpy(S.data() + 4 * n * i, reqs[k0 + i]->S, 32 * n);
+    if (key.kind == DevKey::VAR) {
+      pts.resize(32 * n * k);
+      status.assign(k, SP_OK);
+      for (size_t i = 0; i < k; i++) memcpy(pts.data() + 32 * n * i, reqs[k0 + i]->points, 32 * n);
+      int32_t rc = sp_msm_var_many(c, pts.data(), S.data(), n, k, out.data(), status.data());
+      if (rc != SP_OK) throw failed("sp_msm_var_many", rc);
+      for (size_t i = 0; i < k; i++) answers[k0 + i].rc = status[i];  // SP_EPOINT: a Reject for that proof alone
+    } else if (key.kind == DevKey::POINTS) {
+      int32_t rc = sp_msm_points_many(c, (const sp_points*)key.obj, S.data(), n, k, out.data());
+      if (rc != SP_OK) throw failed("sp_msm_points_many", rc);
+    } else {
+      int32_t rc = sp_commit_rows(c, (const sp_gens*)key.obj, key.g_off, key.h, S.data(), k, n, nullptr, out.data());
+      if (rc != SP_OK) throw failed("sp_commit_rows", rc);
+    }
+    for (size_t i = 0; i < k; i++) memcpy(answers[k0 + i].out.data(), out.data() + 32 * i, 32);
+  }
+}
+
+// one batch of at most kVerifyBatch parsed proofs: verdict[i] for proofs[i]
+void verify_batch(Ctx& ctx, const ComputationCommitment& comm, const SNARK* const* proofs, const FqVec* const* inputs, size_t K, const char* label,
+                  const SNARKGens& gens, const ResidentCommitment& res, int* verdict) {
+  sp_ctx* c = ctx.h;
+  VerifyGate gate(K, [c](const DevKey& key, const std::vector<size_t>&, const std::vector<const DevReq*>& reqs, std::vector<DevAns>& answers) {
+    serve_group(c, key, reqs, answers);
+  });
+  std::mutex err_mu;
+  std::string err;  // the first error of a worker, carried to the caller's thread
+  bool have_err = false;
+  auto note = [&](const char* what) {
+    std::lock_guard<std::mutex> lk(err_mu);
+    if (!have_err) { have_err = true; err = what; }
+  };
+  auto work = [&](size_t m) {
+    tl_seat = GateSeat{&gate, m};
+    GateMember<VerifyGate> seat(gate, m);  // leaves on return and on exception: a proof rejected early never holds the others up
+    try {
+      Transcript t(label);
+      verdict[m] = proofs[m]->verify(ctx, comm, *inputs[m], t, gens, res);
+    } catch (const std::exception& e) {
+      note(e.what());
+    } catch (...) {
+      note("SNARK::verify_many: unknown exception in a verification");
+    }
+    tl_seat = GateSeat();
+  };
+  std::vector<std::thread> threads;
+  size_t started = 0;
+  try {
+    for (; started < K; started++) threads.emplace_back(work, started);
+  } catch (const std::exception& e) {
+    note((std::string("SNARK::verify_many: cannot start a thread: ") + e.what()).c_str());
+    for (size_t m = started; m < K; m++) gate.leave(m);  // the others must not wait for members that never come
+  }
+  for (auto& th : threads) th.join();
+  if (have_err) throw Error(err);  // on purpose the call's error: verify_many then returns no verdict at all, those of earlier batches of 64 included
+}
+}  // namespace
+
+std::vector<int> SNARK::verify_many(Ctx& ctx, const ComputationCommitment& comm, const std::vector<std::pair<const uint8_t*, size_t>>& proofs,
+                                    const std::vector<const FqVec*>& inputs, const char* transcript_label, const SNARKGens& gens,
+                                    const ResidentCommitment& res) {
+  const size_t K = proofs.size();
+  if (inputs.size() != K || !transcript_label) throw Error("SNARK::verify_many: bad arguments");
+  if (!res.ops || !res.mem) throw Error("SNARK::verify_many: the commitment's resident point sets are missing");
+  for (const FqVec* in : inputs)  // lib.rs:437, before any thread starts: the caller's error, not a proof's
+    if (!in || in->size() != comm.num_inputs) throw Error("InvalidNumberOfInputs");
+  std::vector<int> verdict(K, -1);
+  for (size_t b0 = 0; b0 < K; b0 += kVerifyBatch) {
+    const size_t kb = std::min(kVerifyBatch, K - b0);
+    std::vector<SNARK> parsed(kb);
+    std::vector<const SNARK*> pp;
+    std::vector<const FqVec*> in;
+    std::vector<size_t> where;
+    for (size_t i = 0; i < kb; i++)  // malformed bytes are a -1 here and never enter the gate
+      if (SNARK::deserialize(proofs[b0 + i].first, proofs[b0 + i].second, &parsed[i])) { pp.push_back(&parsed[i]); in.push_back(inputs[b0 + i]); where.push_back(b0 + i); }
+    if (pp.empty()) continue;
+    std::vector<int> v(pp.size(), 0);
+    verify_batch(ctx, comm, pp.data(), in.data(), pp.size(), transcript_label, gens, res, v.data());
+    for (size_t i = 0; i < pp.size(); i++) verdict[where[i]] = v[i];
+  }
+  return verdict;
 }
 
 }  // namespace spz
