@@ -692,6 +692,7 @@ int32_t sp_commit_rows_upload_start(sp_ctx* c, const sp_gens* g, size_t g_off, s
   MsmScratch lay;
   SPCHK(job_open(c, c->stream, m, rows, &j, &lay));
   const size_t rch = rows / nch;
+  const unsigned* qcounts = nullptr;
   // copies on the side stream, back to back; the additions of a chunk on the main stream, behind that chunk's copy
   hipEvent_t ready = nullptr;
   hipError_t e = hipEventCreateWithFlags(&ready, hipEventDisableTiming);
@@ -707,11 +708,14 @@ int32_t sp_commit_rows_upload_start(sp_ctx* c, const sp_gens* g, size_t g_off, s
     if (e == hipSuccess) e = hipEventRecord(copied, c->stream_side);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, copied, 0);
     if (copied) (void)hipEventDestroy(copied);
-    if (e == hipSuccess)  // (the queue form's slot counts of a chunk are not handed on: the reduction over all rows gets none)
-      (void)msm_enqueue_sums(c, c->stream, m, g, Z->d + z_off + r0 * cols, cols, rch, cols, g_off, nullptr, dbl ? dbl + r0 : nullptr, h_idx,
-                             j->scratch + r0 * m.P * sizeof(Pt));
+    if (e == hipSuccess)
+      qcounts = msm_enqueue_sums(c, c->stream, m, g, Z->d + z_off + r0 * cols, cols, rch, cols, g_off, nullptr, dbl ? dbl + r0 : nullptr, h_idx,
+                                 j->scratch + r0 * m.P * sizeof(Pt));
   }
-  if (e == hipSuccess) msm_enqueue_reduce(c, c->stream, m, rows, j->scratch, j->scratch + lay.out_off, true, j->scratch + lay.sums_off, nullptr);
+  // The queue form is planned only for an upload issued as ONE chunk (launch_rows == rows, upload.chunks = 1): its slot counts then cover every
+  // row, and the reduction must have them — a slot no wavefront attached to holds no sum. (Without them every row of such a commit came out wrong.)
+  // The other forms return none.
+  if (e == hipSuccess) msm_enqueue_reduce(c, c->stream, m, rows, j->scratch, j->scratch + lay.out_off, true, j->scratch + lay.sums_off, nch == 1 ? qcounts : nullptr);
   (void)hipEventRecord(j->done, c->stream);
   if (e != hipSuccess || hipGetLastError() != hipSuccess) {
     (void)hipStreamSynchronize(c->stream);

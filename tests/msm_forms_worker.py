@@ -1,5 +1,5 @@
 """Worker of tests/test_gpu_kernels.py::test_row_msm_forms_match_oracle: the row MSM's launch form is chosen once per process
-(msm.form = 0, the default: the queue form of msm_queue.hip for launches of >= 256 rows; msm.form = 3: the strip form and the balanced form with two entries in flight, chosen per launch; msm.form = 1 with msm.lds_bits = 10: the LDS-staged small-window form — all through SPARTAN_OPTIONS), so every form runs in a process of its own. Shapes that only these plans select, each against the oracle's orc_commit_rows:
+(msm.form = 0, the default: the queue form of msm_queue.hip for launches of >= 256 rows; msm.form = 3: the strip form and the balanced form with two entries in flight, chosen per launch; msm.form = 1 with msm.lds_bits = 10: the LDS-staged small-window form — all through SPARTAN_OPTIONS), so every form runs in a process of its own. Hand-picked shapes on random-ish scalar kinds, each against the oracle's orc_commit_rows (the thresholds of the launch plan on both sides, the form that ran and the edge-value pools are tests/test_gpu_commit_edges.py's):
 blinds (an extra column that starts or ends a run in the middle of a scalar), rows of zeros, short scalars (the early exit of the strip form
 and the ballot skip of the balanced form: SNARK::encode's addresses and timestamps, src/sparse_mlpoly.rs:483-503), scalars with only high
 bits set (carries into the top window), a run boundary inside the signed recoding's carry chain, and the background kernel."""

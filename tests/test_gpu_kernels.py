@@ -91,9 +91,9 @@ def gens301(ctx, orc):
     g.free()
 
 
-# every launch plan of msm_launch (commit.hip): lookups+tree in one launch / + second reduce (rows <= 8, host encode);
-# windowed one-pass and two-pass trees with per-block and one-lane-per-row encodes; row-strip kernel with and without the
-# XCD-aware tile order
+# seven shapes of msm_launch (commit.hip) on uniform scalars: lookups+tree in one launch / + second reduce (rows <= 8, host encode);
+# windowed trees with per-block and one-lane-per-row encodes; throughput-sized commits. Which plan a shape takes, and both sides of every
+# threshold of the plan, are tests/test_gpu_commit_edges.py's (checked against the source by tests/test_commit_reference.py)
 @pytest.mark.parametrize("rows,cols,blind", [(1, 300, True), (8, 300, False), (16, 128, True), (100, 128, False), (256, 128, True),
                                              (70, 300, True), (512, 64, False)])
 def test_commit_rows_launch_plans_match_oracle(ctx, orc, gens301, rows, cols, blind):
@@ -112,8 +112,9 @@ def test_commit_rows_launch_plans_match_oracle(ctx, orc, gens301, rows, cols, bl
 def test_commit_rows_at_every_window_width(ctx, orc, wbits, monkeypatch):
     """the window geometry is a property of the generator set, chosen at upload (gens.hip choose_geom): every uniform width (option
     msm.wbits) and every number of MIXED-width windows (option msm.windows, the negative parameters: 17 = 1 x 14 + 16 x 15 bits, 18 = 16 x
-    14 + 2 x 15, ... 32 = 2 x 7 + 30 x 8: msm.hpp) gives the same commitments through every launch plan (one-launch small, windowed trees,
-    row strips, the queue form, the indexed lookups of sp_msm_indexed; the digit path of the inner-product argument's own kernel, k_ipa_round, is
+    14 + 2 x 15, ... 32 = 2 x 7 + 30 x 8: msm.hpp) gives the same commitments on a few shapes of each kind (one-launch small, windowed trees,
+    row strips, the queue form, the indexed lookups of sp_msm_indexed; the boundaries of the launch plan and the digit pool at every
+    geometry through the forms that start inside a scalar are in tests/test_gpu_commit_edges.py; the digit path of the inner-product argument's own kernel, k_ipa_round, is
     in tests/test_gpu_ipa_edges.py)"""
     from spartan_amd import capi
     if wbits > 0:
@@ -542,7 +543,9 @@ def test_dot3_many_matches_reference_arithmetic(ctx):
                                         ({}, 27), ({"msm__form": 2, "msm__q_waves": 8, "msm__q_bg_waves": 4, "msm__q_units": 4, "msm__wbits": 12, "bg__eighths": 6}, 27),
                                         ({"msm__q_waves": 4, "msm__q_bg_waves": 12, "msm__q_units": 100, "msm__wbits": 15}, 27)])
 def test_row_msm_forms_match_oracle(opts, count):
-    """Every launch form of the fixed-base row MSM (DensePolynomial::commit_inner, src/dense_mlpoly.rs:164-177) against the oracle: the strip
+    """The launch forms of the fixed-base row MSM (DensePolynomial::commit_inner, src/dense_mlpoly.rs:164-177) against the oracle on hand-picked
+    shapes and random-ish scalar kinds (the thresholds between the forms, with the form that ran observed, and the edge-value pools:
+    tests/test_gpu_commit_edges.py): the strip
     form with its short-scalar early exit (many row-blocks, the persistent background launch), the balanced (column, window) form with two
     entries in flight, another window width and background share, and the LDS-staged small-window form (msm_lds.hip: 10-bit sub-tables
     double-buffered in LDS; 8-, 7- and 6-bit ones — every width the option accepts since ADVICE r5) with shapes of its own — row-blocks that are not a multiple of a
