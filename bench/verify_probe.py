@@ -13,7 +13,10 @@ each after 3 warm pairs: median and spread (min .. max) per call, the table buil
 --what snark_many --batch 1,4,16,64: SNARK.verify_many of K proofs of one circuit (lock step: spartan_amd/host/batch_gate.hpp) against K sequential
 SNARK.verify calls on the same proofs, the two interleaved sample by sample in one process: ms per batch and per proof, round trips, and the
 device time of the two variable-base MSM families per launch chain.
-usage: python bench/verify_probe.py [--what nizk|snark|msm|snark_many] [--out profiles/nizk_verify.txt] [--sizes 16,20,22] [--batch 1,4,16,64]"""
+--what nizk_many --batch 1,4,16,64: the same for NIZK.verify_many against K sequential NIZK.verify calls, with the device time of the batched
+evaluation (one `sparse` record a batch: sp_sparse_evaluate_many_begin) beside K times the single call's, and the keep-or-drop rule of DESIGN.md
+section 3 applied at K = 16: the per-proof medians must differ by more than the spread (max - min) of the samples.
+usage: python bench/verify_probe.py [--what nizk|snark|msm|snark_many|nizk_many] [--out profiles/nizk_verify.txt] [--sizes 16,20,22] [--batch 1,4,16,64]"""
 import argparse, ctypes, faulthandler, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -169,6 +172,68 @@ def snark_many(args, orc):
     return lines
 
 
+def nizk_many(args, orc):
+    DISTINCT = 4
+    lines = ["NIZK::verify_many (K proofs of one instance in lock step) against K sequential NIZK::verify calls (bench/verify_probe.py --what nizk_many; "
+             "host CPU: %s, %d CPUs for this process)" % (cpu_model(), len(os.sched_getaffinity(0))),
+             "per K: %d warm pairs, then %d samples of (one verify_many, K verify calls) interleaved on the host clock, medians; a batch holds %d distinct "
+             "proofs (tape seeds) in rotation; sparse / eq_expand: HIP events around their launches, runs of their own (3 each)" % (WARM, REPS, DISTINCT),
+             "rule (DESIGN.md section 3): the batch is kept if at K = 16 its per-proof median lies below the sequential one by more than the spread (max - min) of the samples",
+             ""]
+    ctx = P.Ctx(0)
+    raw = ctx.raw()
+    med = lambda ts: sorted(ts)[len(ts) // 2]
+    for s in [int(x) for x in args.sizes.split(",")]:
+        N, ni, seed = 1 << s, 10, s
+        inst = P.Instance.produce_synthetic_r1cs(ctx, N, N, ni, seed=seed)
+        inst.set_digest(b"digest-%d" % s)
+        gens = P.NIZKGens(ctx, N, N, ni)
+        distinct = [P.NIZK.prove(ctx, inst, inst.vars, inst.inputs, gens, LABEL, P.seed_scalar(b"tape", seed + 100 * i)) for i in range(DISTINCT)]
+        single = lambda p: P.NIZK.verify_status(ctx, inst, p, inst.inputs, gens, LABEL)
+        lines.append("synthetic 2^%d: proof %d bytes" % (s, len(distinct[0])))
+        print(lines[-1], flush=True)
+        for K in [int(x) for x in args.batch.split(",")]:
+            batch = [distinct[i % DISTINCT] for i in range(K)]
+            many = lambda: P.NIZK.verify_many(ctx, inst, batch, inst.inputs, gens, LABEL)
+            seq = lambda: [single(p) for p in batch]
+            if many() != [1] * K or seq() != [1] * K:
+                raise SystemExit("2^%d, K = %d: a proof of the prover was not accepted" % (s, K))
+            tm, ts = [], []
+            for i in range(WARM + REPS):
+                t0 = time.perf_counter(); many(); t1 = time.perf_counter(); seq(); t2 = time.perf_counter()
+                if i >= WARM:
+                    tm.append((t1 - t0) * 1e3); ts.append((t2 - t1) * 1e3)
+            t0 = L.sp_ctx_trips(raw); many(); trips_m = L.sp_ctx_trips(raw) - t0
+            t0 = L.sp_ctx_trips(raw); seq(); trips_s = L.sp_ctx_trips(raw) - t0
+            fam = {}
+            for name, fn in (("many", many), ("seq", seq)):
+                L.sp_prof_enable(raw, ctypes.c_int(1)); L.sp_prof_reset(raw)
+                for _ in range(3):
+                    fn()
+                fam[name] = (family(raw, "sparse"), family(raw, "eq_expand"))
+                L.sp_prof_enable(raw, ctypes.c_int(0))
+            mm, sm = med(tm), med(ts)
+            (bs_ms, bs_n), (be_ms, be_n) = fam["many"]
+            (ss_ms, ss_n), (se_ms, se_n) = fam["seq"]
+            one_sparse, one_eq = ss_ms / max(ss_n, 1), se_ms / max(se_n, 1)
+            lines += ["  K = %2d  verify_many   median %9.3f ms a batch = %8.3f ms a proof   (min %.3f, max %.3f), %d round trips a batch" % (
+                          K, mm, mm / K, min(tm), max(tm), trips_m),
+                      "          K x verify    median %9.3f ms         = %8.3f ms a proof   (min %.3f, max %.3f), %d round trips" % (
+                          sm, sm / K, min(ts), max(ts), trips_s),
+                      "          evaluation: batched sparse %.3f ms a batch (%d record a batch, %d eq_expand); single call sparse %.3f ms + 2 eq_expand of %.3f ms: K x = %.3f ms (+ %.3f)" % (
+                          bs_ms / 3, bs_n // 3, be_n // 3, one_sparse, one_eq, K * one_sparse, 2 * K * one_eq),
+                      "          sequential / batched = %.2f per proof%s" % (sm / mm, "" if sm >= mm else "   (the batch is SLOWER per proof)")]
+            if K == 16:
+                spread = max(max(tm) - min(tm), max(ts) - min(ts)) / K
+                gain = (sm - mm) / K
+                lines.append("          rule at K = 16: gain %.3f ms a proof, widest spread of the %d samples %.3f ms a proof: %s" % (
+                    gain, REPS, spread, "KEPT (a gain beyond the spread)" if gain > spread else "NOT kept by the rule (no gain beyond the spread)"))
+            print("\n".join(lines[-(5 if K == 16 else 4):]), flush=True)
+        gens.free(); inst.free()
+    ctx.close()
+    return lines
+
+
 def msm(args, orc):
     import random
     from tests import msm_var_cases as M
@@ -220,14 +285,16 @@ def finish(args, lines):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--sizes", default="16,20,22")
-    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm", "snark_many"])
-    ap.add_argument("--batch", default="1,4,16,64", help="--what snark_many: the batch sizes K")
+    ap.add_argument("--sizes", default=None, help="log2 sizes; default 16,20,22 (nizk_many: 16,20)")
+    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm", "snark_many", "nizk_many"])
+    ap.add_argument("--batch", default="1,4,16,64", help="--what snark_many / nizk_many: the batch sizes K")
     args = ap.parse_args()
+    if args.sizes is None:
+        args.sizes = "16,20" if args.what == "nizk_many" else "16,20,22"
     orc = load_oracle()
     orc.orc_set_threads(ctypes.c_int(16))
     if args.what != "nizk":
-        return finish(args, {"snark": snark, "msm": msm, "snark_many": snark_many}[args.what](args, orc))
+        return finish(args, {"snark": snark, "msm": msm, "snark_many": snark_many, "nizk_many": nizk_many}[args.what](args, orc))
     lines = ["NIZK::verify on the device against the oracle's verifier on the host (bench/verify_probe.py; host CPU: %s)" % cpu_model(),
              "(a): median of %d warm calls, host clock; msm_var: HIP events around its launch chain, runs of their own; (c): median of 3, 16 threads" % REPS,
              ""]

@@ -335,6 +335,17 @@ int32_t sp_sparse_evaluate(sp_ctx* ctx, const sp_sparse* m, const sp_table* tx, 
  * order): SNARK::prove (src/lib.rs:393-400) starts R1CSInstance::evaluate as soon as ry is known and collects the three values after
  * the witness opening. tx and ty must outlive the job. */
 int32_t sp_sparse_evaluate_begin(sp_ctx* ctx, const sp_sparse* const* ms, size_t count, const sp_table* tx, const sp_table* ty, sp_job** out);
+/* R1CSInstance::evaluate of up to four matrices at K points at once (NIZK::verify_many: K proofs of one circuit in lock step): proof k's point
+ * is (rx + 4 ell_x k, ry + 4 ell_y k), scalars in the form sp_eq_expand takes. Queued like sp_sparse_evaluate_begin (low-priority stream,
+ * behind what is queued on the context) and collected with sp_job_wait: 32 count K bytes, proof-major, out[k * count + m], each equal limb
+ * for limb to sp_eq_expand x 2 + sp_sparse_evaluate at that proof's point. rx and ry are copied before the call returns. Every entry is read
+ * once for all K proofs and no full chi table is built: device memory of a call is the half tables, 32 K (2^(ell_x - ell_x/2) + 2^(ell_x/2) +
+ * 2^(ell_y - ell_y/2) + 2^(ell_y/2)) bytes, plus 32 count K partial sums for at most 1024 blocks — nothing proportional to
+ * K (num_rows + num_cols). SP_EINVAL, before anything is allocated: a null pointer, count = 0 or > 4, K = 0 or > SP_EVAL_MANY_MAX_K, ell = 0 or
+ * > 32, a matrix with num_rows > 2^ell_x or num_cols > 2^ell_y. */
+#define SP_EVAL_MANY_MAX_K 64u               /* points of one sp_sparse_evaluate_many_begin call */
+int32_t sp_sparse_evaluate_many_begin(sp_ctx* ctx, const sp_sparse* const* ms, size_t count /*1..4*/, const uint64_t* rx /*4*ell_x*K*/, size_t ell_x,
+                                      const uint64_t* ry /*4*ell_y*K*/, size_t ell_y, size_t K /*1..SP_EVAL_MANY_MAX_K*/, sp_job** out);
 /* R1CSShape::is_sat (r1cs.rs:240-266): (A z)[r] * (B z)[r] == (C z)[r] for every row r; z has >= num_cols elements.
  * *violated = number of failing rows, *first_row = the smallest failing index (UINT64_MAX when none);
  * rows_out (may be NULL) receives the min(*violated, rows_cap) lowest failing indices in ascending order.

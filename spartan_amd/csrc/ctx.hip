@@ -331,6 +331,8 @@ void sp_ctx_destroy(sp_ctx* c) {
   if (c->vm_pinned) (void)hipHostFree(c->vm_pinned);
   if (c->vm_dstage) (void)hipFree(c->vm_dstage);
   if (c->vm_ev) (void)hipEventDestroy(c->vm_ev);
+  if (c->em_pinned) (void)hipHostFree(c->em_pinned);
+  if (c->em_ev) (void)hipEventDestroy(c->em_ev);
   if (c->sync_ev) (void)hipEventDestroy(c->sync_ev);
   if (c->side_ev) (void)hipEventDestroy(c->side_ev);
   if (c->stream_side) (void)hipStreamDestroy(c->stream_side);

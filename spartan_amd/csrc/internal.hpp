@@ -101,6 +101,8 @@ struct sp_ctx {
   uint8_t *vm_pinned = nullptr, *vm_dstage = nullptr;  // sp_vecmat_dev's own staging pair for L: the call does not wait (ctx.hip: vm_stage)
   size_t vm_cap = 0;
   hipEvent_t vm_ev = nullptr;
+  uint8_t* em_pinned = nullptr;  // sp_sparse_evaluate_many_begin's own page for the K challenge vectors: the call does not wait (sparse_many.hip)
+  hipEvent_t em_ev = nullptr;    // fired when the kernel that reads em_pinned has run
   struct { bool active; int kind; size_t nblk; bool on_host; uint32_t seq; } pend_eval = {false, 0, 0, false, 0};  // sp_sumcheck_bind_eval_start .. _collect
   uint8_t* hmap;  // host-mapped (fine-grained) page: small kernel inputs are read, small results written, without a DMA hop
 
@@ -144,6 +146,23 @@ struct sp_table {
   size_t d_bytes;  // pool size of d when owned
   Fq* alt;         // second pool buffer for out-of-place binds of tables shared between kernel instances
   size_t alt_bytes;
+};
+// a sparse R1CS matrix on the device (sparse.hip; sparse_many.hip reads the CSR copy)
+struct sp_sparse {
+  sp_ctx* ctx;
+  size_t nnz, num_rows, num_cols;
+  uint32_t *row_ptr, *csr_col, *csr_row;  // CSR (+ row of each entry for evaluate_with_tables)
+  Fq* csr_val;
+  uint32_t *col_ptr, *csc_row;  // CSC
+  Fq* csc_val;
+  uint32_t *ent_row, *ent_col;  // the entries in the order they were given (SparseMatPolynomial.M, sparse_mlpoly.rs:19-38): SNARK::encode's
+  Fq* ent_val;                  // address lists and value vectors are these, zero-padded (sparse_mlpoly.rs:367-427) — no host pass over them
+  // sp_r1cs_check's plan for the long rows of this matrix, built from row_ptr on the first check (check_plan below) and kept: the rows with
+  // more than CHK_LANE_MAX entries in ascending order, cut into chunks of <= CHK_CHUNK entries; chunk k covers entries [chk_beg[k], chk_end[k])
+  // and the chunks of chk_rows[j] are [chk_first[j], chk_first[j + 1])
+  mutable bool chk_built;
+  mutable uint32_t chk_nrows, chk_nchunks;
+  mutable uint32_t *chk_rows, *chk_first, *chk_beg, *chk_end;
 };
 // the 32-byte encodings of a generator set's points (kept by the process-wide table cache, gens.hip); *n = number of points
 extern "C" const uint8_t* gens_compressed_bytes(const sp_gens* g, size_t* n);

@@ -6,23 +6,6 @@
 
 #include "internal.hpp"
 
-struct sp_sparse {
-  sp_ctx* ctx;
-  size_t nnz, num_rows, num_cols;
-  uint32_t *row_ptr, *csr_col, *csr_row;  // CSR (+ row of each entry for evaluate_with_tables)
-  Fq* csr_val;
-  uint32_t *col_ptr, *csc_row;  // CSC
-  Fq* csc_val;
-  uint32_t *ent_row, *ent_col;  // the entries in the order they were given (SparseMatPolynomial.M, sparse_mlpoly.rs:19-38): SNARK::encode's
-  Fq* ent_val;                  // address lists and value vectors are these, zero-padded (sparse_mlpoly.rs:367-427) — no host pass over them
-  // sp_r1cs_check's plan for the long rows of this matrix, built from row_ptr on the first check (check_plan below) and kept: the rows with
-  // more than CHK_LANE_MAX entries in ascending order, cut into chunks of <= CHK_CHUNK entries; chunk k covers entries [chk_beg[k], chk_end[k])
-  // and the chunks of chk_rows[j] are [chk_first[j], chk_first[j + 1])
-  mutable bool chk_built;
-  mutable uint32_t chk_nrows, chk_nchunks;
-  mutable uint32_t *chk_rows, *chk_first, *chk_beg, *chk_end;
-};
-
 // multiply_vec (sparse_mlpoly.rs:454-464)
 __global__ void __launch_bounds__(256) k_spmv(const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, const Fq* __restrict__ val,
                                               const Fq* __restrict__ z, size_t num_rows, Fq* __restrict__ out) { SP_FG_PRIO();

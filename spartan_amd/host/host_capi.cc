@@ -414,6 +414,33 @@ int spz_nizk_verify_t(void* ctx, void* inst, void* gens, const uint8_t* proof, s
     return -2;
   }
 }
+// NIZK::verify_many: K untrusted proofs of one instance in lock step on the device (libspartan.hpp), with the return codes of
+// spz_snark_verify_many: status_out[k] = 1 accept, 0 reject, -1 malformed bytes and 0 returned; -2 with spz_last_error() for an error of the
+// CALL (bad arguments, "InvalidNumberOfInputs" before anything runs, a device failure), status_out then all -2. K = 0 is legal and does nothing.
+int spz_nizk_verify_many(void* ctx, void* inst, void* gens, const uint8_t* const* proofs, const size_t* proof_lens, const uint64_t* const* inputs,
+                         size_t n_inputs, size_t K, const char* transcript_label, int* status_out) {
+  try {
+    g_err.clear();
+    if (!ctx || !inst || !gens || !transcript_label || (K && (!proofs || !proof_lens || !status_out || (n_inputs && !inputs))))
+      throw Error("spz_nizk_verify_many: bad arguments");
+    for (size_t k = 0; k < K; k++) status_out[k] = -2;
+    std::vector<std::pair<const uint8_t*, size_t>> pv(K);
+    std::vector<FqVec> in(K);
+    std::vector<const FqVec*> inp(K);
+    for (size_t k = 0; k < K; k++) {
+      if (!proofs[k] || (n_inputs && !inputs[k])) throw Error("spz_nizk_verify_many: bad arguments");
+      pv[k] = std::make_pair(proofs[k], proof_lens[k]);
+      in[k] = limbs_vec(n_inputs ? inputs[k] : nullptr, n_inputs);
+      inp[k] = &in[k];
+    }
+    std::vector<int> v = NIZK::verify_many(*(Ctx*)ctx, *(Instance*)inst, pv, inp, transcript_label, *(NIZKGens*)gens);
+    for (size_t k = 0; k < K; k++) status_out[k] = v[k];
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -2;
+  }
+}
 // test hook (no GPU): parse proof bytes and serialise them again. Returns the number of bytes (written when cap suffices), -1 when malformed.
 long long spz_nizk_parse_probe(const uint8_t* proof, size_t len, uint8_t* out, size_t cap) {
   try {

@@ -367,6 +367,14 @@ struct NIZK {  // lib.rs:488-587
   // table-sized group operations run on the device (placement: verifier.cc). Throws Error("InvalidNumberOfInputs") for a wrong number of
   // inputs (lib.rs:569), Error for a device failure; a proof that is merely wrong, or carries undecodable points, is a 0.
   int verify(Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript& transcript, const NIZKGens& gens) const;
+  // K UNTRUSTED proofs (bytes, length) of one instance, under the conventions of SNARK::verify_many: verify() itself per proof, one host thread
+  // and one transcript each, in lock step through a gate. C_LZ and G_hat go out as one call a batch; R1CSInstance::evaluate at the K proofs'
+  // own points is ONE sp_sparse_evaluate_many_begin that reads every matrix entry once and builds no full chi table. The job belongs to the
+  // batch: a proof that is rejected early neither waits for it nor frees it. Verdicts 1 accept, 0 reject, -1 malformed bytes (these never start
+  // a thread). Lists longer than 64 are cut into batches of 64; the instance's digest is computed once per call. Throws
+  // Error("InvalidNumberOfInputs") before anything runs; Error for a device failure (then no verdict is given at all).
+  static std::vector<int> verify_many(Ctx& ctx, const Instance& inst, const std::vector<std::pair<const uint8_t*, size_t>>& proofs,
+                                      const std::vector<const FqVec*>& inputs, const char* transcript_label, const NIZKGens& gens);
 };
 
 std::vector<uint8_t> serialize_r1cs_proof(const R1CSProof& p);

@@ -2,6 +2,7 @@
 // Where each piece runs:
 //   R1CSInstance::evaluate(rx, ry)  NIZK: device: sp_eq_expand x 2, sp_sparse_evaluate_begin on the instance's resident matrices, collected with
 //                                   sp_job_wait when R1CSProof::verify needs the three values (the kernels run under the host's Sigma protocols).
+//                                   NIZK::verify_many: ONE sp_sparse_evaluate_many_begin for the batch, at every proof's own point
 //                                   SNARK: the three values the proof claims; the sparse-polynomial evaluation proof binds them to the commitment
 //   C_LZ = <L, comm.C>              device. Points that arrive with the proof (comm_vars; the SNARK's comm_derefs): sp_msm_var. The two commitments
 //                                   of a ComputationCommitment, fixed for a circuit: sp_msm_points over their resident point sets (sp_points) when
@@ -13,7 +14,8 @@
 //                                   ProductCircuitEvalProofBatched, ProductLayerProof, HashLayerProof::verify_helper)
 //   point equalities                comparisons of 32-byte encodings
 // SNARK::verify_many (at the end of the file) runs K of these verifications on K threads; their C_LZ and G_hat calls then meet at a gate
-// (batch_gate.hpp) and go out once per batch: sp_msm_var_many, sp_msm_points_many, sp_commit_rows with K rows.
+// (batch_gate.hpp) and go out once per batch: sp_msm_var_many, sp_msm_points_many, sp_commit_rows with K rows. NIZK::verify_many does the same
+// for NIZK::verify, whose third device request, the evaluation of the instance, becomes one job of the batch.
 // Verdicts: 1 accept, 0 reject, -1 malformed bytes. The input is untrusted: where the reference panics on attacker-controlled data
 // (decompress().unwrap() at dense_mlpoly.rs:382, r1csproof.rs:409, nizk/mod.rs:239; the length asserts of sumcheck.rs:38,44,97-98, nizk/mod.rs:381,
 // 536-537, product_tree.rs:395,417-418,425, sparse_mlpoly.rs:167,861-883,910,922-930,1238-1268,1379-1381,1531 and the slice indices next to
@@ -95,9 +97,11 @@ CP commit_gens(const sp_gens* g, const std::vector<uint32_t>& idx, const FqVec& 
 //   (var, n)                     sp_msm_var over n points of the proof        -> sp_msm_var_many
 //   (points, set, n)             sp_msm_points over a resident set            -> sp_msm_points_many
 //   (rows, gens, g_off, h, n)    sp_commit_rows of one unblinded row          -> sp_commit_rows with rows = the group's size
+//   (eval_start, instance)       R1CSInstance::evaluate at (rx, ry), started  -> sp_sparse_evaluate_many_begin, one job for the group
+//   (eval_collect, instance)     ... its three values                         -> sp_job_wait, once (NIZK::verify_many only)
 struct DevKey {
-  enum Kind { VAR, POINTS, ROWS } kind;
-  const void* obj;  // the sp_points or the sp_gens; null for VAR
+  enum Kind { VAR, POINTS, ROWS, EVAL_START, EVAL_COLLECT } kind;
+  const void* obj;  // the sp_points, the sp_gens or the Instance; null for VAR
   size_t g_off, h, n;
   bool operator<(const DevKey& o) const {
     if (kind != o.kind) return kind < o.kind;
@@ -107,8 +111,8 @@ struct DevKey {
     return n < o.n;
   }
 };
-struct DevReq { const uint8_t* points; const uint64_t* S; };  // n encodings (VAR only) and n scalars, alive while the member waits
-struct DevAns { int32_t rc = SP_OK; CP out{}; };
+struct DevReq { const uint8_t* points; const uint64_t* S; const uint64_t* S2 = nullptr; };  // n encodings (VAR only) and n scalars, alive while the member waits; EVAL_START: S = rx, S2 = ry
+struct DevAns { int32_t rc = SP_OK; CP out{}; uint64_t ev[12] = {0}; };  // ev: EVAL_COLLECT's (A, B, C)(rx, ry)
 typedef BatchGate<DevKey, DevReq, DevAns> VerifyGate;
 struct GateSeat { VerifyGate* gate = nullptr; size_t member = 0; };
 thread_local GateSeat tl_seat;  // set by a worker thread of verify_many for its lifetime; null on every other thread
@@ -683,10 +687,12 @@ bool NIZK::deserialize(const uint8_t* bytes, size_t len, NIZK* out) {
   return r.ok && r.o == len;  // trailing bytes are malformed
 }
 
-int NIZK::verify(Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript& t, const NIZKGens& gens) const {
+namespace {
+// NIZK::verify after the two things that belong to the call and not to the proof (the inputs' count and the instance's digest, which
+// NIZK::verify_many takes once for all its proofs). With a gate on the thread the evaluation of the instance is posted there, like C_LZ and G_hat.
+int nizk_verify_body(const NIZK& P, Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript& t, const NIZKGens& gens, const std::vector<uint8_t>& digest) {
   sp_ctx* c = ctx.h;
-  if (inputs.size() != inst.num_inputs) throw Error("InvalidNumberOfInputs");  // lib.rs:569: the caller's error, not the proof's
-  const std::vector<uint8_t> digest = inst.compute_digest();                   // lib.rs:559, as NIZK::prove absorbs it
+  const FqVec &rx = P.rx, &ry = P.ry;
   t.append_protocol_name("Spartan NIZK proof");
   t.append_message("R1CSShapeDigest", digest.data(), digest.size());
   // R1CSInstance::evaluate(claimed_rx, claimed_ry) (lib.rs:565 -> r1cs.rs:300-303) is started now and collected when the last check needs it
@@ -696,7 +702,11 @@ int NIZK::verify(Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript
     sp_job* job = nullptr;
     ~Eval() { if (job) { uint8_t sink[96]; (void)sp_job_wait(job, sink); } }
   } ev;
-  {
+  const bool gated = tl_seat.gate != nullptr;
+  if (gated) {  // the batch's one job, at this proof's own point: started by the leader, owned by the batch
+    DevAns a = tl_seat.gate->post(tl_seat.member, DevKey{DevKey::EVAL_START, &inst, 0, 0, 0}, DevReq{nullptr, U(rx), U(ry)});
+    spx(a.rc, "sp_sparse_evaluate_many_begin");
+  } else {
     sp_table* h = nullptr;
     spx(sp_eq_expand(c, U(rx), rx.size(), &h), "sp_eq_expand");
     ev.tx = DevTable(c, h);
@@ -706,6 +716,12 @@ int NIZK::verify(Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript
     spx(sp_sparse_evaluate_begin(c, ms, 3, ev.tx.h, ev.ty.h, &ev.job), "sp_sparse_evaluate_begin");
   }
   EvalsFn evals = [&](Fq out[3]) {
+    if (gated) {
+      DevAns a = tl_seat.gate->post(tl_seat.member, DevKey{DevKey::EVAL_COLLECT, &inst, 0, 0, 0}, DevReq{nullptr, nullptr});
+      spx(a.rc, "sp_job_wait");
+      for (int k = 0; k < 3; k++) memcpy(out[k].l, a.ev + 4 * k, 32);
+      return;
+    }
     uint8_t e3[96];
     sp_job* j = ev.job;
     ev.job = nullptr;
@@ -714,12 +730,18 @@ int NIZK::verify(Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript
   };
   try {
     FqVec vx, vy;
-    r1cs_verify(c, r1cs_sat_proof, inst.num_vars, inst.num_cons, inputs, evals, t, gens.gens_r1cs_sat, GenBytes{gens.stream_sat.compressed}, &vx, &vy);
+    r1cs_verify(c, P.r1cs_sat_proof, inst.num_vars, inst.num_cons, inputs, evals, t, gens.gens_r1cs_sat, GenBytes{gens.stream_sat.compressed}, &vx, &vy);
     if (vx != rx || vy != ry) return 0;  // lib.rs:580-581
   } catch (const Reject&) {
     return 0;
   }
   return 1;
+}
+}  // namespace
+
+int NIZK::verify(Ctx& ctx, const Instance& inst, const FqVec& inputs, Transcript& t, const NIZKGens& gens) const {
+  if (inputs.size() != inst.num_inputs) throw Error("InvalidNumberOfInputs");  // lib.rs:569: the caller's error, not the proof's
+  return nizk_verify_body(*this, ctx, inst, inputs, t, gens, inst.compute_digest());  // lib.rs:559, as NIZK::prove absorbs it
 }
 
 int SNARK::verify(Ctx& ctx, const ComputationCommitment& comm, const FqVec& inputs, Transcript& t, const SNARKGens& gens, const ResidentCommitment& res) const {
@@ -796,13 +818,9 @@ void serve_group(sp_ctx* c, const DevKey& key, const std::vector<const DevReq*>&
   }
 }
 
-// one batch of at most kVerifyBatch parsed proofs: verdict[i] for proofs[i]
-void verify_batch(Ctx& ctx, const ComputationCommitment& comm, const SNARK* const* proofs, const FqVec* const* inputs, size_t K, const char* label,
-                  const SNARKGens& gens, const ResidentCommitment& res, int* verdict) {
-  sp_ctx* c = ctx.h;
-  VerifyGate gate(K, [c](const DevKey& key, const std::vector<size_t>&, const std::vector<const DevReq*>& reqs, std::vector<DevAns>& answers) {
-    serve_group(c, key, reqs, answers);
-  });
+// one batch of at most kVerifyBatch parsed proofs, one thread each behind a gate served by `serve`: verdict[m] = verify_one(m)
+void run_batch(size_t K, VerifyGate::ServeFn serve, const std::function<int(size_t)>& verify_one, const char* who, int* verdict) {
+  VerifyGate gate(K, std::move(serve));
   std::mutex err_mu;
   std::string err;  // the first error of a worker, carried to the caller's thread
   bool have_err = false;
@@ -814,12 +832,11 @@ void verify_batch(Ctx& ctx, const ComputationCommitment& comm, const SNARK* cons
     tl_seat = GateSeat{&gate, m};
     GateMember<VerifyGate> seat(gate, m);  // leaves on return and on exception: a proof rejected early never holds the others up
     try {
-      Transcript t(label);
-      verdict[m] = proofs[m]->verify(ctx, comm, *inputs[m], t, gens, res);
+      verdict[m] = verify_one(m);
     } catch (const std::exception& e) {
       note(e.what());
     } catch (...) {
-      note("SNARK::verify_many: unknown exception in a verification");
+      note((std::string(who) + ": unknown exception in a verification").c_str());
     }
     tl_seat = GateSeat();
   };
@@ -828,11 +845,87 @@ void verify_batch(Ctx& ctx, const ComputationCommitment& comm, const SNARK* cons
   try {
     for (; started < K; started++) threads.emplace_back(work, started);
   } catch (const std::exception& e) {
-    note((std::string("SNARK::verify_many: cannot start a thread: ") + e.what()).c_str());
+    note((std::string(who) + ": cannot start a thread: " + e.what()).c_str());
     for (size_t m = started; m < K; m++) gate.leave(m);  // the others must not wait for members that never come
   }
   for (auto& th : threads) th.join();
   if (have_err) throw Error(err);  // on purpose the call's error: verify_many then returns no verdict at all, those of earlier batches of 64 included
+}
+void verify_batch(Ctx& ctx, const ComputationCommitment& comm, const SNARK* const* proofs, const FqVec* const* inputs, size_t K, const char* label,
+                  const SNARKGens& gens, const ResidentCommitment& res, int* verdict) {
+  sp_ctx* c = ctx.h;
+  run_batch(K, [c](const DevKey& key, const std::vector<size_t>&, const std::vector<const DevReq*>& reqs, std::vector<DevAns>& answers) {
+    serve_group(c, key, reqs, answers);
+  }, [&](size_t m) {
+    Transcript t(label);
+    return proofs[m]->verify(ctx, comm, *inputs[m], t, gens, res);
+  }, "SNARK::verify_many", verdict);
+}
+
+// The evaluation job of a NIZK batch. It belongs to the BATCH: the leader of the first rendezvous starts it for the members that posted a
+// point, the leader of the collect rendezvous waits for it once and hands every member its three values. A member that left in between never
+// touches it; if nobody collects (every member was rejected on the way), the calling thread waits for it after the join — drain(), by then the
+// only thread left. Touched by one leader at a time, like the context.
+struct EvalBatch {
+  static_assert(kVerifyBatch <= SP_EVAL_MANY_MAX_K, "a batch's evaluation is one call");
+  sp_job* job = nullptr;
+  size_t count = 0;                // points of the job
+  std::vector<size_t> slot;        // member -> its index in the job
+  std::vector<uint64_t> vals;      // 12 limbs a point once collected
+  bool collected = false;
+  explicit EvalBatch(size_t K) : slot(K, (size_t)-1) {}
+  ~EvalBatch() { drain(); }
+  void drain() noexcept {
+    if (!job) return;
+    std::vector<uint8_t> sink(96 * count);
+    (void)sp_job_wait(job, sink.data());
+    job = nullptr;
+  }
+  void start(sp_ctx* c, const Instance& inst, const std::vector<size_t>& members, const std::vector<const DevReq*>& reqs, std::vector<DevAns>& answers) {
+    if (job || collected) throw std::logic_error("NIZK::verify_many: a second evaluation in one batch");
+    const size_t G = reqs.size(), ex = log_2(inst.num_cons), ey = log_2(2 * inst.num_vars);
+    std::vector<uint64_t> rx(4 * ex * G), ry(4 * ey * G);
+    for (size_t i = 0; i < G; i++) {  // every member has checked its lengths before posting
+      memcpy(rx.data() + 4 * ex * i, reqs[i]->S, 32 * ex);
+      memcpy(ry.data() + 4 * ey * i, reqs[i]->S2, 32 * ey);
+      slot[members[i]] = i;
+    }
+    const sp_sparse* ms[3] = {inst.dA, inst.dB, inst.dC};
+    int32_t rc = sp_sparse_evaluate_many_begin(c, ms, 3, rx.data(), ex, ry.data(), ey, G, &job);
+    if (rc != SP_OK) { job = nullptr; throw Error(std::string("sp_sparse_evaluate_many_begin failed: ") + sp_strerror(rc) + " (" + std::to_string(rc) + ")"); }
+    count = G;
+    answers.assign(G, DevAns());
+  }
+  void collect(const std::vector<size_t>& members, std::vector<DevAns>& answers) {
+    if (!collected) {
+      if (!job) throw std::logic_error("NIZK::verify_many: an evaluation collected before it was started");
+      vals.assign(12 * count, 0);
+      sp_job* j = job;
+      job = nullptr;  // sp_job_wait frees it, whatever it returns
+      int32_t rc = sp_job_wait(j, (uint8_t*)vals.data());
+      if (rc != SP_OK) throw Error(std::string("sp_job_wait failed: ") + sp_strerror(rc) + " (" + std::to_string(rc) + ")");
+      collected = true;
+    }
+    answers.assign(members.size(), DevAns());
+    for (size_t i = 0; i < members.size(); i++) {
+      const size_t s = slot.at(members[i]);
+      if (s >= count) throw std::logic_error("NIZK::verify_many: a member collects an evaluation it did not start");
+      memcpy(answers[i].ev, vals.data() + 12 * s, 96);
+    }
+  }
+};
+void nizk_verify_batch(Ctx& ctx, const Instance& inst, const NIZK* const* proofs, const FqVec* const* inputs, size_t K, const char* label, const NIZKGens& gens,
+                       const std::vector<uint8_t>& digest, int* verdict) {
+  sp_ctx* c = ctx.h;
+  EvalBatch eval(K);  // outlives the threads: run_batch joins them all before it returns or throws
+  run_batch(K, [c, &inst, &eval](const DevKey& key, const std::vector<size_t>& members, const std::vector<const DevReq*>& reqs, std::vector<DevAns>& answers) {
+    if (key.kind == DevKey::EVAL_START) eval.start(c, inst, members, reqs, answers);
+    else if (key.kind == DevKey::EVAL_COLLECT) eval.collect(members, answers);
+    else serve_group(c, key, reqs, answers);
+  }, [&](size_t m) {
+    Transcript t(label);
+    return nizk_verify_body(*proofs[m], ctx, inst, *inputs[m], t, gens, digest);
+  }, "NIZK::verify_many", verdict);
 }
 }  // namespace
 
@@ -856,6 +949,31 @@ std::vector<int> SNARK::verify_many(Ctx& ctx, const ComputationCommitment& comm,
     if (pp.empty()) continue;
     std::vector<int> v(pp.size(), 0);
     verify_batch(ctx, comm, pp.data(), in.data(), pp.size(), transcript_label, gens, res, v.data());
+    for (size_t i = 0; i < pp.size(); i++) verdict[where[i]] = v[i];
+  }
+  return verdict;
+}
+
+std::vector<int> NIZK::verify_many(Ctx& ctx, const Instance& inst, const std::vector<std::pair<const uint8_t*, size_t>>& proofs,
+                                   const std::vector<const FqVec*>& inputs, const char* transcript_label, const NIZKGens& gens) {
+  const size_t K = proofs.size();
+  if (inputs.size() != K || !transcript_label) throw Error("NIZK::verify_many: bad arguments");
+  for (const FqVec* in : inputs)  // lib.rs:569, before any thread starts: the caller's error, not a proof's
+    if (!in || in->size() != inst.num_inputs) throw Error("InvalidNumberOfInputs");
+  std::vector<int> verdict(K, -1);
+  if (K == 0) return verdict;
+  const std::vector<uint8_t> digest = inst.compute_digest();  // lib.rs:559: once per call, every proof's transcript absorbs the same bytes
+  for (size_t b0 = 0; b0 < K; b0 += kVerifyBatch) {
+    const size_t kb = std::min(kVerifyBatch, K - b0);
+    std::vector<NIZK> parsed(kb);
+    std::vector<const NIZK*> pp;
+    std::vector<const FqVec*> in;
+    std::vector<size_t> where;
+    for (size_t i = 0; i < kb; i++)  // malformed bytes are a -1 here and never enter the gate
+      if (NIZK::deserialize(proofs[b0 + i].first, proofs[b0 + i].second, &parsed[i])) { pp.push_back(&parsed[i]); in.push_back(inputs[b0 + i]); where.push_back(b0 + i); }
+    if (pp.empty()) continue;
+    std::vector<int> v(pp.size(), 0);
+    nizk_verify_batch(ctx, inst, pp.data(), in.data(), pp.size(), transcript_label, gens, digest, v.data());
     for (size_t i = 0; i < pp.size(); i++) verdict[where[i]] = v[i];
   }
   return verdict;

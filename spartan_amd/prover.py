@@ -342,6 +342,32 @@ class NIZK:
         return NIZK.verify_status(ctx, inst, proof_bytes, inputs, gens, transcript_label) == 1
 
     @staticmethod
+    def verify_many(ctx, inst, proofs, inputs, gens, transcript_label):
+        """NIZK::verify of many untrusted proofs of ONE instance in lock step on the device (spz_nizk_verify_many): the list of verify_status's
+        verdicts, 1 accept, 0 reject, -1 malformed bytes, one per proof — every proof is verified as verify_status verifies it, but the K
+        verifications share their device round trips, and the instance is evaluated at the K proofs' points in one pass over its matrices.
+        `inputs`: one buffer of Montgomery limbs (a ctypes uint64 array, or the instance's own) shared by all proofs, or a list with one buffer
+        per proof. Raises SpartanHipError("InvalidNumberOfInputs") when a buffer's size is not the instance's num_inputs, and for a device
+        failure; no verdicts then."""
+        K = len(proofs)
+        per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * K
+        if len(per) != K:
+            raise SpartanHipError("NIZK::verify_many failed: one inputs buffer per proof")
+        sizes = {inst.num_inputs if x is inst.inputs else len(x) // 4 for x in per}
+        if len(sizes) > 1:
+            raise SpartanHipError("NIZK::verify_many failed: InvalidNumberOfInputs")
+        n_in = sizes.pop() if K else 0
+        keep = [ctypes.create_string_buffer(bytes(p), max(len(p), 1)) for p in proofs]
+        pa = (vp * K)(*[ctypes.cast(b, vp) for b in keep])
+        la = (sz * K)(*[len(p) for p in proofs])
+        ia = (vp * K)(*[ctypes.cast(x, vp) for x in per])
+        st = (ctypes.c_int * K)()
+        rc = H.spz_nizk_verify_many(ctx.h, inst.h, gens.h, pa, la, ia, sz(n_in), sz(K), transcript_label, st)
+        if rc != 0:
+            raise SpartanHipError(f"NIZK::verify_many failed: {H.spz_last_error().decode()}")
+        return [int(x) for x in st]
+
+    @staticmethod
     def verify_t(ctx, inst, proof_bytes, inputs, gens, transcript_state):
         """NIZK::verify on a caller-owned transcript: the 203-byte state (see SNARK.prove_t) is continued by the verification and left in the
         state it ends in — after an accepted proof, the state NIZK.prove_t left on the prover's side. Returns the status of verify_status."""
