@@ -196,9 +196,9 @@ int32_t sp_msm_var(sp_ctx* ctx, const uint8_t* points /*32*n*/, const uint64_t* 
 /* K such sums of one size in ONE launch chain and one round trip: out[k] = compress( sum_{j<n} S[k][j] * P[k][j] ), every multiplication with n
  * untrusted points of its own (MSM k: points + 32 n k, S + 4 n k). What K verifications of one circuit ask for when they advance in lock step
  * (SNARK::verify_many): a single multiplication leaves the chip idle behind one lane's Horner doublings, so K of them add width to each kernel,
- * not length (msm_many.hip). status[k] is SP_OK or SP_EPOINT: an invalid encoding fails ITS multiplication only (out[k] is then not written),
- * the other K - 1 results are what sp_msm_var gives. Returns SP_OK when the batch ran. SP_EINVAL: K = 0, K > SP_MSM_MANY_MAX_K (256), n = 0,
- * n > 65536, n K > SP_MSM_MANY_MAX_TERMS (2^20), a null pointer. */
+ * not length (msm_var.hip: sp_msm_var is this call with K = 1). status[k] is SP_OK or SP_EPOINT: an invalid encoding fails ITS multiplication
+ * only (out[k] is then not written), the other K - 1 results are what sp_msm_var gives. Returns SP_OK when the batch ran. SP_EINVAL: K = 0,
+ * K > SP_MSM_MANY_MAX_K (256), n = 0, n > 65536, n K > SP_MSM_MANY_MAX_TERMS (2^20), a null pointer. */
 #define SP_MSM_MANY_MAX_K 256u               /* multiplications of one sp_msm_var_many / sp_msm_points_many call */
 #define SP_MSM_MANY_MAX_TERMS (1u << 20)     /* n K of one call */
 int32_t sp_msm_var_many(sp_ctx* ctx, const uint8_t* points /*32*n*K*/, const uint64_t* S /*4*n*K, Montgomery*/, size_t n, size_t K, uint8_t* out /*32*K*/,
@@ -219,7 +219,7 @@ size_t sp_points_count(const sp_points* p);
  * Horner doublings (msm_var.hip). Synchronous, one launch chain, one round trip. SP_EINVAL: n is not the set's size, the set lives on
  * another device than ctx, a null pointer. */
 int32_t sp_msm_points(sp_ctx* ctx, const sp_points* pts, const uint64_t* S /*4*n, Montgomery*/, size_t n, uint8_t out[32]);
-/* K scalar vectors over the one set in ONE launch chain and one round trip: out[k] = compress( sum_{j<n} S[k][j] * P[j] ) (msm_many.hip); each
+/* K scalar vectors over the one set in ONE launch chain and one round trip: out[k] = compress( sum_{j<n} S[k][j] * P[j] ) (msm_var.hip); each
  * result is what sp_msm_points gives. SP_EINVAL: K = 0, K > 256, n K > 2^20, n is not the set's size, the set lives on another device than
  * ctx, a null pointer. */
 int32_t sp_msm_points_many(sp_ctx* ctx, const sp_points* pts, const uint64_t* S /*4*n*K, Montgomery*/, size_t n, size_t K, uint8_t* out /*32*K*/);

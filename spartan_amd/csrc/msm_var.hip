@@ -1,64 +1,112 @@
-// spartan_amd: variable-base multi-scalar multiplication, sum_j S[j] * P[j] over points that arrive WITH A PROOF (sp_msm_var):
+// spartan_amd: variable-base multi-scalar multiplication, sum_j S[j] * P[j] over points that arrive WITH A PROOF (sp_msm_var, sp_msm_var_many):
 // GroupElement::vartime_multiscalar_mul of PolyEvalProof::verify (src/dense_mlpoly.rs:382-384, C_LZ = <L, comm.C>). The points are not a
 // sp_gens — there are no precomputed tables and nothing is known about them: they may repeat, be each other's negatives or the identity, so
 // every addition is the complete one (pt_add, add-2008-hwcd-3) and every doubling pt_dbl.
 //
-// The launch is small (n = 32 at 2^10, 1024 at 2^20, 2048 at 2^22) and latency-bound, so the work is spread over (point, window) pairs with
-// signed 4-bit windows (64 windows: one wavefront's worth for the recombination):
-//   k_msmv_prepare   one lane per point: decode (a flag word reports an invalid encoding), the multiples 1..8 P (7 point operations), the
-//                    scalar taken out of Montgomery form and recoded into 64 signed digits;
-//   k_msmv_windows   one lane per (point, window), a block per (256 points, window): the lane's term is +-T[|d|] or the identity; 6 wavefront
-//                    shuffle levels, then the block's 4 wavefront sums through LDS: one partial window sum per block;
-//   k_msmv_finish    one block: the cross-block stage (4 lanes per window add the blocks' partial sums), then the Horner recombination of the
-//                    64 window sums (4 doublings + 1 addition each) and the RFC 9496 encode on one lane; result and flag go to the host page.
-// Point operations on the critical path: 7 + 8 (6 shuffle levels + 2 LDS) + ceil(nblocks / 4) + 2 + 63 * 5 + the encode, i.e. ~335 for
-// n <= 1024 of which 252 are the doublings no schedule avoids; in all 7 n + 64 n + 315 operations. One round trip.
+// A multiplication is small (n = 32 at 2^10, 1024 at 2^20, 2048 at 2^22) and latency-bound, so the work is spread over (point, window) pairs
+// with signed 4-bit windows (64 windows: one wavefront's worth for the recombination). Every kernel carries a batch dimension: a call runs K
+// multiplications of one size in ONE launch chain and one round trip, which is what a verifier of many proofs of one circuit asks for when its
+// K verifications advance in lock step (verifier.cc, SNARK::verify_many). K independent multiplications add WIDTH to every kernel and no
+// length; sp_msm_var is the call with K = 1.
+//   k_msmv_prepare   one lane per (MSM, point), K n lanes: decode (one flag word PER MSM reports an invalid encoding), the multiples 1..8 P
+//                    (7 point operations), the scalar taken out of Montgomery form and recoded into 64 signed digits, [K][64][n];
+//   k_msmv_windows   one lane per (point, window), grid (blocks, 64 windows, K), a block per (256 points, window) of one MSM: the lane's term
+//                    is +-T[|d|] or the identity; 6 wavefront shuffle levels, then the block's 4 wavefront sums through LDS: one partial window
+//                    sum per block;
+//   k_msmv_finish    K workgroups, one per MSM: the cross-block stage (4 lanes per window add the blocks' partial sums), then the Horner
+//                    recombination of the 64 window sums (4 doublings + 1 addition each) and the RFC 9496 encode on one lane; each writes its
+//                    own 36-byte slot (32 + the flag) of the host result page and counts itself in; the last one signals (sig_make(c, K)).
+// Point operations on the critical path, that of ONE multiplication whatever K: 7 + 8 (6 shuffle levels + 2 LDS) + ceil(nblocks / 4) + 2 +
+// 63 * 5 + the encode, i.e. ~335 for n <= 1024 of which 252 are one lane's doublings no schedule avoids, the rest of the chip idle; in all
+// K (7 n + 64 n + 315) operations.
 #include "internal.hpp"
-#include "msm_var.hpp"
+
+constexpr size_t MV_MAX_N = 65536;
+constexpr int MV_BLOCK = 256;
+
+struct sp_points {
+  int dev;
+  size_t n;
+  Pt* table;  // [64 windows][n][8]: table[(w * n + j) * 8 + m - 1] = m 16^w P[j]
+};
 
 namespace {
-__global__ void __launch_bounds__(64) k_msmv_prepare(const uint8_t* __restrict__ enc, const Fq* __restrict__ S, size_t n, Pt* __restrict__ table,
-                                                     int8_t* __restrict__ digits /*[64][n]*/, int* __restrict__ bad) { SP_FG_PRIO();
-  const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (j >= n) return;
+constexpr size_t MVM_MAX_K = SP_MSM_MANY_MAX_K;          // multiplications a call (spartan_hip.h): the result area holds MVM_MAX_K x 36 bytes
+constexpr size_t MVM_MAX_TERMS = SP_MSM_MANY_MAX_TERMS;  // n K of a call (1 GiB of per-point tables for sp_msm_var_many)
+constexpr size_t MVM_SLOT = 36;                          // k_msmv_finish: 32 bytes of encoding + the flag word
+static_assert(MVM_MAX_K * MVM_SLOT <= HMAP_SIZE - HMAP_IN, "the slots of a full batch fit the result area of the host page");
+
+__device__ __forceinline__ Pt pt_shfl_down(const Pt& p, int delta) {
+  Pt r;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    r.X.v[i] = __shfl_down((unsigned long long)p.X.v[i], delta, 64);
+    r.Y.v[i] = __shfl_down((unsigned long long)p.Y.v[i], delta, 64);
+    r.Z.v[i] = __shfl_down((unsigned long long)p.Z.v[i], delta, 64);
+    r.T.v[i] = __shfl_down((unsigned long long)p.T.v[i], delta, 64);
+  }
+  return r;
+}
+
+// The sum of one term per lane over a block of MV_BLOCK lanes, shared by the window kernels of sp_msm_var and sp_msm_points: 6 wavefront
+// shuffle levels, then the 4 wavefront sums through LDS; lane 0 writes the block's sum. EVERY lane of the block must call it (no early exit
+// before it): lane 0 of each wavefront ends with the sum of its 64 terms.
+__device__ __forceinline__ void msmv_block_sum(Pt p, Pt* sm /*[MV_BLOCK / 64], shared*/, Pt* __restrict__ out) {
+  const int t = threadIdx.x;
+#pragma unroll 1
+  for (int delta = 32; delta > 0; delta >>= 1) p = pt_add(p, pt_shfl_down(p, delta));
+  if ((t & 63) == 0) sm[t >> 6] = p;
+  __syncthreads();
+  if (t == 0) *out = pt_add(pt_add(sm[0], sm[1]), pt_add(sm[2], sm[3]));
+}
+
+__global__ void __launch_bounds__(64) k_msmv_prepare(const uint8_t* __restrict__ enc, const Fq* __restrict__ S, unsigned n, unsigned total /* K n */,
+                                                     Pt* __restrict__ table, int8_t* __restrict__ digits /*[K][64][n]*/, int* __restrict__ bad /*[K]*/) { SP_FG_PRIO();
+  const unsigned g = blockIdx.x * 64 + threadIdx.x;
+  if (g >= total) return;
+  const unsigned k = g / n, j = g - k * n;
   uint8_t b[32];
-  for (int k = 0; k < 32; k++) b[k] = enc[32 * j + k];
+  for (int i = 0; i < 32; i++) b[i] = enc[32 * (size_t)g + i];
   Pt p;
   if (!pt_decompress(b, &p)) {
-    atomicExch(bad, 1);
+    atomicExch(bad + k, 1);
     p = pt_identity();
   }
   Pt T[SP_VAR_TABLE];
   pt_var_table(p, T);
-  for (int m = 0; m < SP_VAR_TABLE; m++) table[j * SP_VAR_TABLE + m] = T[m];
+  for (int m = 0; m < SP_VAR_TABLE; m++) table[(size_t)g * SP_VAR_TABLE + m] = T[m];
   int8_t d[SP_VAR_WINDOWS];
-  fq_signed_digits4(fq_from_mont(ld_fq(S + j)), d);
-  for (int w = 0; w < SP_VAR_WINDOWS; w++) digits[(size_t)w * n + j] = d[w];
+  fq_signed_digits4(fq_from_mont(ld_fq(S + g)), d);
+  int8_t* dk = digits + (size_t)k * SP_VAR_WINDOWS * n;
+  for (int w = 0; w < SP_VAR_WINDOWS; w++) dk[(size_t)w * n + j] = d[w];
 }
 
-// grid (nblocks, 64 windows): partial[w * nblocks + blk] = sum over the block's 256 points of digit_w(S[j]) * P[j]
+// grid (nblocks, 64 windows, K): partial[(k * 64 + w) * nblocks + blk] = sum over the block's 256 points of digit_w(S[k][j]) * P[k][j]
 __global__ void __launch_bounds__(MV_BLOCK) k_msmv_windows(const Pt* __restrict__ table, const int8_t* __restrict__ digits, size_t n,
                                                            Pt* __restrict__ partial) { SP_FG_PRIO();
   __shared__ Pt sm[MV_BLOCK / 64];
   const int t = threadIdx.x;
-  const size_t w = blockIdx.y, j = (size_t)blockIdx.x * MV_BLOCK + t;
+  const size_t w = blockIdx.y, k = blockIdx.z, j = (size_t)blockIdx.x * MV_BLOCK + t;
   Pt p = pt_identity();
   if (j < n) {
-    const int d = digits[w * n + j];
+    const int d = digits[(k * SP_VAR_WINDOWS + w) * n + j];
     if (d != 0) {
-      p = table[j * SP_VAR_TABLE + ((d < 0 ? -d : d) - 1)];
+      p = table[(k * n + j) * SP_VAR_TABLE + ((d < 0 ? -d : d) - 1)];
       if (d < 0) p = pt_neg(p);
     }
   }
-  msmv_block_sum(p, sm, &partial[w * gridDim.x + blockIdx.x]);
+  msmv_block_sum(p, sm, &partial[(k * SP_VAR_WINDOWS + w) * gridDim.x + blockIdx.x]);
 }
 
-__global__ void __launch_bounds__(256) k_msmv_finish(const Pt* __restrict__ partial, size_t nblocks, const int* __restrict__ bad, uint8_t* __restrict__ out /*32 + 4*/,
+// K workgroups: workgroup k finishes MSM k
+__global__ void __launch_bounds__(256) k_msmv_finish(const Pt* __restrict__ partial, size_t nblocks, const int* __restrict__ bad, uint8_t* __restrict__ out /*K x 36*/,
                                                      DoneSig sig) { SP_FG_PRIO();
   __shared__ Pt win[SP_VAR_WINDOWS];
   const int t = threadIdx.x, w = t >> 2, q = t & 3;
+  const size_t k = blockIdx.x;
+  const Pt* part = partial + k * SP_VAR_WINDOWS * nblocks;
   Pt acc = pt_identity();
-  for (size_t b = q; b < nblocks; b += 4) acc = pt_add(acc, partial[(size_t)w * nblocks + b]);
+  for (size_t b = q; b < nblocks; b += 4) acc = pt_add(acc, part[(size_t)w * nblocks + b]);
   acc = pt_add(acc, pt_shfl_down(acc, 2));
   acc = pt_add(acc, pt_shfl_down(acc, 1));
   if (q == 0) win[w] = acc;
@@ -66,28 +114,30 @@ __global__ void __launch_bounds__(256) k_msmv_finish(const Pt* __restrict__ part
   if (t == 0) {
     Pt r = win[SP_VAR_WINDOWS - 1];
 #pragma unroll 1
-    for (int k = SP_VAR_WINDOWS - 2; k >= 0; k--) {
+    for (int i = SP_VAR_WINDOWS - 2; i >= 0; i--) {
       r = pt_dbl(pt_dbl(pt_dbl(pt_dbl(r))));
-      r = pt_add(r, win[k]);
+      r = pt_add(r, win[i]);
     }
     uint8_t c[32];
     Pt10 r10 = pt10_load(r);
     fe10_pin(r10.X); fe10_pin(r10.Y); fe10_pin(r10.Z); fe10_pin(r10.T);
     pt10_compress(r10, c);
-    for (int k = 0; k < 32; k++) out[k] = c[k];
-    *reinterpret_cast<int*>(out + 32) = *bad;
+    uint8_t* o = out + k * MVM_SLOT;
+    for (int i = 0; i < 32; i++) o[i] = c[i];
+    *reinterpret_cast<int*>(o + 32) = bad[k];
   }
   signal_done(sig);
 }
-// ---- resident point sets (sp_points, sp_msm_points): the same sum over points that do NOT change between calls — the two commitments of a
-// ComputationCommitment, fixed for the lifetime of a circuit. The set is decoded once and keeps, per point, the multiples 1..8 of 16^w P for
-// all 64 windows (64 KiB a point), so a multiplication is a flat sum of table entries: no decode, no table build, no Horner doublings.
+// ---- resident point sets (sp_points, sp_msm_points, sp_msm_points_many): the same sum over points that do NOT change between calls — the two
+// commitments of a ComputationCommitment, fixed for the lifetime of a circuit. The set is decoded once and keeps, per point, the multiples 1..8
+// of 16^w P for all 64 windows (64 KiB a point), so a multiplication is a flat sum of table entries: no decode, no table build, no Horner
+// doublings. K scalar vectors over the one set go through one launch chain, as above; sp_msm_points is the call with K = 1.
 //   k_points_build   one lane per point, at upload: decode (flag word as above), then per window the table of the running base and base <- 16 base;
-//   k_msmp_digits    one lane per scalar: out of Montgomery form, 64 signed digits, the [64][n] layout of k_msmv_prepare;
+//   k_msmp_digits    one lane per (MSM, scalar): out of Montgomery form, 64 signed digits, the [K][64][n] layout of k_msmv_prepare;
 //   k_msmp_windows   k_msmv_windows with the lane's term fetched from window w's slice of the resident table;
-//   k_msmp_finish    one block: 256 lanes stride over all 64 x nblocks partial sums (they carry their weight 16^w already), 6 shuffle levels,
-//                    the 4 wavefront sums through LDS, the encode on one lane; the result goes to the host page.
-// Point operations on the critical path: 8 + ceil(64 nblocks / 256) + 8 + the encode. One round trip.
+//   k_msmp_finish    K workgroups, one per MSM: 256 lanes stride over all 64 x nblocks partial sums (they carry their weight 16^w already),
+//                    6 shuffle levels, the 4 wavefront sums through LDS, the encode on one lane; each writes its 32-byte slot of the host page.
+// Point operations on the critical path: 8 + ceil(64 nblocks / 256) + 8 + the encode.
 __global__ void __launch_bounds__(64) k_points_build(const uint8_t* __restrict__ enc, size_t n, Pt* __restrict__ table /*[64][n][8]*/, int* __restrict__ bad) {
   const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (j >= n) return;
@@ -107,36 +157,41 @@ __global__ void __launch_bounds__(64) k_points_build(const uint8_t* __restrict__
   }
 }
 
-__global__ void __launch_bounds__(MV_BLOCK) k_msmp_digits(const Fq* __restrict__ S, size_t n, int8_t* __restrict__ digits /*[64][n]*/) { SP_FG_PRIO();
-  const size_t j = (size_t)blockIdx.x * MV_BLOCK + threadIdx.x;
-  if (j >= n) return;
+__global__ void __launch_bounds__(MV_BLOCK) k_msmp_digits(const Fq* __restrict__ S, unsigned n, unsigned total /* K n */, int8_t* __restrict__ digits /*[K][64][n]*/) { SP_FG_PRIO();
+  const unsigned g = blockIdx.x * MV_BLOCK + threadIdx.x;
+  if (g >= total) return;
+  const unsigned k = g / n, j = g - k * n;
   int8_t d[SP_VAR_WINDOWS];
-  fq_signed_digits4(fq_from_mont(ld_fq(S + j)), d);
-  for (int w = 0; w < SP_VAR_WINDOWS; w++) digits[(size_t)w * n + j] = d[w];
+  fq_signed_digits4(fq_from_mont(ld_fq(S + g)), d);
+  int8_t* dk = digits + (size_t)k * SP_VAR_WINDOWS * n;
+  for (int w = 0; w < SP_VAR_WINDOWS; w++) dk[(size_t)w * n + j] = d[w];
 }
 
-// grid (nblocks, 64 windows): partial[w * nblocks + blk] = sum over the block's 256 points of digit_w(S[j]) * 16^w P[j]
+// grid (nblocks, 64 windows, K): partial[(k * 64 + w) * nblocks + blk] = sum over the block's 256 points of digit_w(S[k][j]) * 16^w P[j]
 __global__ void __launch_bounds__(MV_BLOCK) k_msmp_windows(const Pt* __restrict__ table, const int8_t* __restrict__ digits, size_t n,
                                                            Pt* __restrict__ partial) { SP_FG_PRIO();
   __shared__ Pt sm[MV_BLOCK / 64];
   const int t = threadIdx.x;
-  const size_t w = blockIdx.y, j = (size_t)blockIdx.x * MV_BLOCK + t;
+  const size_t w = blockIdx.y, k = blockIdx.z, j = (size_t)blockIdx.x * MV_BLOCK + t;
   Pt p = pt_identity();
   if (j < n) {
-    const int d = digits[w * n + j];
+    const int d = digits[(k * SP_VAR_WINDOWS + w) * n + j];
     if (d != 0) {
       p = table[(w * n + j) * SP_VAR_TABLE + ((d < 0 ? -d : d) - 1)];
       if (d < 0) p = pt_neg(p);
     }
   }
-  msmv_block_sum(p, sm, &partial[w * gridDim.x + blockIdx.x]);
+  msmv_block_sum(p, sm, &partial[(k * SP_VAR_WINDOWS + w) * gridDim.x + blockIdx.x]);
 }
 
-__global__ void __launch_bounds__(256) k_msmp_finish(const Pt* __restrict__ partial, size_t nparts, uint8_t* __restrict__ out /*32*/, DoneSig sig) { SP_FG_PRIO();
+// K workgroups: workgroup k adds the nparts partial sums of MSM k
+__global__ void __launch_bounds__(256) k_msmp_finish(const Pt* __restrict__ partial, size_t nparts, uint8_t* __restrict__ out /*K x 32*/, DoneSig sig) { SP_FG_PRIO();
   __shared__ Pt sm[4];
   const int t = threadIdx.x;
+  const size_t k = blockIdx.x;
+  const Pt* part = partial + k * nparts;
   Pt acc = pt_identity();
-  for (size_t i = t; i < nparts; i += 256) acc = pt_add(acc, partial[i]);
+  for (size_t i = t; i < nparts; i += 256) acc = pt_add(acc, part[i]);
 #pragma unroll 1
   for (int delta = 32; delta > 0; delta >>= 1) acc = pt_add(acc, pt_shfl_down(acc, delta));
   if ((t & 63) == 0) sm[t >> 6] = acc;
@@ -147,31 +202,42 @@ __global__ void __launch_bounds__(256) k_msmp_finish(const Pt* __restrict__ part
     Pt10 r10 = pt10_load(r);
     fe10_pin(r10.X); fe10_pin(r10.Y); fe10_pin(r10.Z); fe10_pin(r10.T);
     pt10_compress(r10, c);
-    for (int k = 0; k < 32; k++) out[k] = c[k];
+    uint8_t* o = out + 32 * k;
+    for (int i = 0; i < 32; i++) o[i] = c[i];
   }
   signal_done(sig);
 }
-}  // namespace
 
-extern "C" int32_t sp_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t n, uint8_t out[32]) {
-  if (!c || !points || !S || !out || n == 0 || n > MV_MAX_N) return SP_EINVAL;
-  HIPCHK(hipSetDevice(c->dev));
-  const size_t nblocks = (n + MV_BLOCK - 1) / MV_BLOCK;
-  // device buffer: [table n x 8 Pt][partial 64 x nblocks Pt][digits 64 n][flag]
-  const size_t off_part = n * SP_VAR_TABLE * sizeof(Pt), off_dig = off_part + (size_t)SP_VAR_WINDOWS * nblocks * sizeof(Pt);
-  const size_t off_bad = (off_dig + (size_t)SP_VAR_WINDOWS * n + 255) & ~(size_t)255, total = off_bad + 256;
-  const uint8_t* d_enc;
-  const Fq* d_S;
-  if (64 * n <= HMAP_GEN) {  // proof-sized at 2^10..2^16: the kernel reads encodings and scalars straight from the host-mapped page
-    d_enc = (const uint8_t*)stage_small(c, 0, points, 32 * n);
-    d_S = (const Fq*)stage_small(c, 32 * n, S, 32 * n);
-  } else {
-    SPCHK(ensure_dstage(c, 64 * n));
-    SPCHK(stage_in(c, 0, points, 32 * n));
-    SPCHK(stage_in(c, 32 * n, S, 32 * n));
-    d_enc = (const uint8_t*)c->dstage;
-    d_S = (const Fq*)((const uint8_t*)c->dstage + 32 * n);
+bool many_args_ok(size_t n, size_t K) { return n != 0 && K != 0 && n <= MV_MAX_N && K <= MVM_MAX_K && n * K <= MVM_MAX_TERMS; }
+
+// the call's host inputs, back to back, where the kernels read them: the host-mapped page while they fit, else the device staging buffer
+// (the pinned buffer is sized for the whole call first: the second copy must never regrow it under the first, whatever ensure_pinned's
+// growth factor is)
+int32_t stage_inputs(sp_ctx* c, const void* a, size_t a_bytes, const void* b, size_t b_bytes, const uint8_t** d_a, const uint8_t** d_b) {
+  const size_t total = a_bytes + b_bytes;
+  if (total <= HMAP_GEN) {
+    *d_a = (const uint8_t*)stage_small(c, 0, a, a_bytes);
+    *d_b = b_bytes ? (const uint8_t*)stage_small(c, a_bytes, b, b_bytes) : nullptr;
+    return SP_OK;
   }
+  SPCHK(ensure_dstage(c, total));
+  SPCHK(ensure_pinned(c, total));
+  SPCHK(stage_in(c, 0, a, a_bytes));
+  if (b_bytes) SPCHK(stage_in(c, a_bytes, b, b_bytes));
+  *d_a = (const uint8_t*)c->dstage;
+  *d_b = (const uint8_t*)c->dstage + a_bytes;
+  return SP_OK;
+}
+
+// K multiplications over K x n points of the caller: status[k] is SP_OK or SP_EPOINT, out[k] is written where it is SP_OK. One round trip.
+int32_t msm_var_run(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t n, size_t K, uint8_t* out, int32_t* status) {
+  HIPCHK(hipSetDevice(c->dev));
+  const size_t nk = n * K, nblocks = (n + MV_BLOCK - 1) / MV_BLOCK;
+  // device buffer: [table K n x 8 Pt][partial K x 64 x nblocks Pt][digits K x 64 n][K flags]
+  const size_t off_part = nk * SP_VAR_TABLE * sizeof(Pt), off_dig = off_part + K * SP_VAR_WINDOWS * nblocks * sizeof(Pt);
+  const size_t off_bad = (off_dig + (size_t)SP_VAR_WINDOWS * nk + 255) & ~(size_t)255, total = off_bad + ((4 * K + 255) & ~(size_t)255);
+  const uint8_t *d_enc, *d_S;
+  SPCHK(stage_inputs(c, points, 32 * nk, S, 32 * nk, &d_enc, &d_S));
   void* buf = nullptr;
   SPCHK(pool_alloc(c, total, &buf));
   uint8_t* base = (uint8_t*)buf;
@@ -180,24 +246,69 @@ extern "C" int32_t sp_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* 
   int8_t* digits = (int8_t*)(base + off_dig);
   int* bad = (int*)(base + off_bad);
   uint8_t* res = hres(c);
-  if (hipMemsetAsync(bad, 0, 4, c->stream) != hipSuccess) { pool_release(c, buf, total); return SP_EHIP; }
-  DoneSig sig = sig_make(c, 1);
+  if (hipMemsetAsync(bad, 0, 4 * K, c->stream) != hipSuccess) { pool_release(c, buf, total); return SP_EHIP; }
+  DoneSig sig = sig_make(c, K);
   {
-    const double ops = (double)(SP_VAR_TABLE - 1) * (double)n + (double)SP_VAR_WINDOWS * (double)(nblocks * MV_BLOCK) + 5.0 * (SP_VAR_WINDOWS - 1);
-    ProfScope ps(c, PF_MSM_VAR, 64.0 * (double)n + 32.0, nullptr, ops);
-    hipLaunchKernelGGL(k_msmv_prepare, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, d_enc, d_S, n, table, digits, bad);
-    hipLaunchKernelGGL(k_msmv_windows, dim3((unsigned)nblocks, SP_VAR_WINDOWS), dim3(MV_BLOCK), 0, c->stream, (const Pt*)table, (const int8_t*)digits, n, partial);
-    hipLaunchKernelGGL(k_msmv_finish, dim3(1), dim3(256), 0, c->stream, (const Pt*)partial, nblocks, (const int*)bad, res, sig);
+    const double ops = (double)K * ((double)(SP_VAR_TABLE - 1) * (double)n + (double)SP_VAR_WINDOWS * (double)(nblocks * MV_BLOCK) + 5.0 * (SP_VAR_WINDOWS - 1));
+    ProfScope ps(c, PF_MSM_VAR, 64.0 * (double)nk + 32.0 * (double)K, nullptr, ops);
+    hipLaunchKernelGGL(k_msmv_prepare, dim3((unsigned)((nk + 63) / 64)), dim3(64), 0, c->stream, d_enc, (const Fq*)d_S, (unsigned)n, (unsigned)nk, table, digits, bad);
+    hipLaunchKernelGGL(k_msmv_windows, dim3((unsigned)nblocks, SP_VAR_WINDOWS, (unsigned)K), dim3(MV_BLOCK), 0, c->stream, (const Pt*)table, (const int8_t*)digits, n,
+                       partial);
+    hipLaunchKernelGGL(k_msmv_finish, dim3((unsigned)K), dim3(256), 0, c->stream, (const Pt*)partial, nblocks, (const int*)bad, res, sig);
   }
   int32_t rc = sig_wait(c, sig);
   pool_release(c, buf, total);
   if (rc != SP_OK) return rc;
   if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  int flag;
-  memcpy(&flag, res + 32, 4);
-  if (flag) return SP_EPOINT;
-  memcpy(out, res, 32);
+  for (size_t k = 0; k < K; k++) {
+    int flag;
+    memcpy(&flag, res + k * MVM_SLOT + 32, 4);
+    status[k] = flag ? SP_EPOINT : SP_OK;
+    if (!flag) memcpy(out + 32 * k, res + k * MVM_SLOT, 32);
+  }
   return SP_OK;
+}
+
+// K scalar vectors over the resident set pts (pts->n == n, on c's device): out[k], always written. One round trip.
+int32_t msm_points_run(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, size_t K, uint8_t* out) {
+  HIPCHK(hipSetDevice(c->dev));
+  const size_t nk = n * K, nblocks = (n + MV_BLOCK - 1) / MV_BLOCK, nparts = (size_t)SP_VAR_WINDOWS * nblocks;
+  // device buffer: [partial K x 64 x nblocks Pt][digits K x 64 n]
+  const size_t off_dig = K * nparts * sizeof(Pt), total = off_dig + (size_t)SP_VAR_WINDOWS * nk;
+  const uint8_t *d_S, *unused;
+  SPCHK(stage_inputs(c, S, 32 * nk, nullptr, 0, &d_S, &unused));
+  void* buf = nullptr;
+  SPCHK(pool_alloc(c, total, &buf));
+  Pt* partial = (Pt*)buf;
+  int8_t* digits = (int8_t*)((uint8_t*)buf + off_dig);
+  uint8_t* res = hres(c);
+  DoneSig sig = sig_make(c, K);
+  {
+    const double ops = (double)K * ((double)SP_VAR_WINDOWS * (double)(nblocks * MV_BLOCK) + (double)nparts);
+    ProfScope ps(c, PF_MSM_POINTS, 32.0 * (double)nk + 32.0 * (double)K, nullptr, ops);
+    hipLaunchKernelGGL(k_msmp_digits, dim3((unsigned)((nk + MV_BLOCK - 1) / MV_BLOCK)), dim3(MV_BLOCK), 0, c->stream, (const Fq*)d_S, (unsigned)n, (unsigned)nk, digits);
+    hipLaunchKernelGGL(k_msmp_windows, dim3((unsigned)nblocks, SP_VAR_WINDOWS, (unsigned)K), dim3(MV_BLOCK), 0, c->stream, (const Pt*)pts->table, (const int8_t*)digits, n,
+                       partial);
+    hipLaunchKernelGGL(k_msmp_finish, dim3((unsigned)K), dim3(256), 0, c->stream, (const Pt*)partial, nparts, res, sig);
+  }
+  int32_t rc = sig_wait(c, sig);
+  pool_release(c, buf, total);
+  if (rc != SP_OK) return rc;
+  if (hipGetLastError() != hipSuccess) return SP_EHIP;
+  memcpy(out, res, 32 * K);
+  return SP_OK;
+}
+}  // namespace
+
+extern "C" int32_t sp_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t n, uint8_t out[32]) {
+  if (!c || !points || !S || !out || n == 0 || n > MV_MAX_N) return SP_EINVAL;
+  int32_t status = SP_OK;
+  SPCHK(msm_var_run(c, points, S, n, 1, out, &status));
+  return status;  // SP_EPOINT: out is not written
+}
+extern "C" int32_t sp_msm_var_many(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t n, size_t K, uint8_t* out, int32_t* status) {
+  if (!c || !points || !S || !out || !status || !many_args_ok(n, K)) return SP_EINVAL;
+  return msm_var_run(c, points, S, n, K, out, status);
 }
 
 extern "C" int32_t sp_points_upload(sp_ctx* c, const uint8_t* compressed, size_t n, sp_points** out) {
@@ -235,36 +346,9 @@ extern "C" size_t sp_points_count(const sp_points* p) { return p ? p->n : 0; }
 
 extern "C" int32_t sp_msm_points(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, uint8_t out[32]) {
   if (!c || !pts || !S || !out || n == 0 || n != pts->n || pts->dev != c->dev) return SP_EINVAL;
-  HIPCHK(hipSetDevice(c->dev));
-  const size_t nblocks = (n + MV_BLOCK - 1) / MV_BLOCK, nparts = (size_t)SP_VAR_WINDOWS * nblocks;
-  // device buffer: [partial 64 x nblocks Pt][digits 64 n]
-  const size_t off_dig = nparts * sizeof(Pt), total = off_dig + (size_t)SP_VAR_WINDOWS * n;
-  const Fq* d_S;
-  if (32 * n <= HMAP_GEN) {
-    d_S = (const Fq*)stage_small(c, 0, S, 32 * n);
-  } else {
-    SPCHK(ensure_dstage(c, 32 * n));
-    SPCHK(stage_in(c, 0, S, 32 * n));
-    d_S = (const Fq*)c->dstage;
-  }
-  void* buf = nullptr;
-  SPCHK(pool_alloc(c, total, &buf));
-  Pt* partial = (Pt*)buf;
-  int8_t* digits = (int8_t*)((uint8_t*)buf + off_dig);
-  uint8_t* res = hres(c);
-  DoneSig sig = sig_make(c, 1);
-  {
-    const double ops = (double)SP_VAR_WINDOWS * (double)(nblocks * MV_BLOCK) + (double)nparts;
-    ProfScope ps(c, PF_MSM_POINTS, 32.0 * (double)n + 32.0, nullptr, ops);
-    hipLaunchKernelGGL(k_msmp_digits, dim3((unsigned)nblocks), dim3(MV_BLOCK), 0, c->stream, d_S, n, digits);
-    hipLaunchKernelGGL(k_msmp_windows, dim3((unsigned)nblocks, SP_VAR_WINDOWS), dim3(MV_BLOCK), 0, c->stream, (const Pt*)pts->table, (const int8_t*)digits, n,
-                       partial);
-    hipLaunchKernelGGL(k_msmp_finish, dim3(1), dim3(256), 0, c->stream, (const Pt*)partial, nparts, res, sig);
-  }
-  int32_t rc = sig_wait(c, sig);
-  pool_release(c, buf, total);
-  if (rc != SP_OK) return rc;
-  if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  memcpy(out, res, 32);
-  return SP_OK;
+  return msm_points_run(c, pts, S, n, 1, out);
+}
+extern "C" int32_t sp_msm_points_many(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, size_t K, uint8_t* out) {
+  if (!c || !pts || !S || !out || !many_args_ok(n, K) || n != pts->n || pts->dev != c->dev) return SP_EINVAL;
+  return msm_points_run(c, pts, S, n, K, out);
 }

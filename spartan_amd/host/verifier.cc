@@ -35,9 +35,10 @@ using namespace sp;
 namespace {
 struct Reject {};  // a check of the protocol failed, or a point of the proof does not decode: verdict 0
 
+Error dev_error(const char* what, int32_t rc) { return Error(std::string(what) + " failed: " + sp_strerror(rc) + " (" + std::to_string(rc) + ")"); }
 void spx(int32_t rc, const char* what) {
   if (rc == SP_EPOINT) throw Reject();
-  if (rc != SP_OK) throw Error(std::string(what) + " failed: " + sp_strerror(rc) + " (" + std::to_string(rc) + ")");
+  if (rc != SP_OK) throw dev_error(what, rc);
 }
 void require(bool cond) { if (!cond) throw Reject(); }
 const uint64_t* U(const FqVec& v) { return v.empty() ? nullptr : v[0].l; }
@@ -790,7 +791,6 @@ void serve_group(sp_ctx* c, const DevKey& key, const std::vector<const DevReq*>&
   std::vector<uint64_t> S;
   std::vector<uint8_t> pts, out;
   std::vector<int32_t> status;
-  auto failed = [](const char* what, int32_t rc) { return Error(std::string(what) + " failed: " + sp_strerror(rc) + " (" + std::to_string(rc) + ")"); };
   // the group in calls of at most `step` members: the whole group unless n K passes the library's cap (n >= 2^14 at 64 proofs)
   size_t step = n && SP_MSM_MANY_MAX_TERMS / n ? SP_MSM_MANY_MAX_TERMS / n : 1;
   if (step > SP_MSM_MANY_MAX_K) step = SP_MSM_MANY_MAX_K;
@@ -805,14 +805,14 @@ void serve_group(sp_ctx* c, const DevKey& key, const std::vector<const DevReq*>&
       status.assign(k, SP_OK);
       for (size_t i = 0; i < k; i++) memcpy(pts.data() + 32 * n * i, reqs[k0 + i]->points, 32 * n);
       int32_t rc = sp_msm_var_many(c, pts.data(), S.data(), n, k, out.data(), status.data());
-      if (rc != SP_OK) throw failed("sp_msm_var_many", rc);
+      if (rc != SP_OK) throw dev_error("sp_msm_var_many", rc);
       for (size_t i = 0; i < k; i++) answers[k0 + i].rc = status[i];  // SP_EPOINT: a Reject for that proof alone
     } else if (key.kind == DevKey::POINTS) {
       int32_t rc = sp_msm_points_many(c, (const sp_points*)key.obj, S.data(), n, k, out.data());
-      if (rc != SP_OK) throw failed("sp_msm_points_many", rc);
+      if (rc != SP_OK) throw dev_error("sp_msm_points_many", rc);
     } else {
       int32_t rc = sp_commit_rows(c, (const sp_gens*)key.obj, key.g_off, key.h, S.data(), k, n, nullptr, out.data());
-      if (rc != SP_OK) throw failed("sp_commit_rows", rc);
+      if (rc != SP_OK) throw dev_error("sp_commit_rows", rc);
     }
     for (size_t i = 0; i < k; i++) memcpy(answers[k0 + i].out.data(), out.data() + 32 * i, 32);
   }
@@ -892,7 +892,7 @@ struct EvalBatch {
     }
     const sp_sparse* ms[3] = {inst.dA, inst.dB, inst.dC};
     int32_t rc = sp_sparse_evaluate_many_begin(c, ms, 3, rx.data(), ex, ry.data(), ey, G, &job);
-    if (rc != SP_OK) { job = nullptr; throw Error(std::string("sp_sparse_evaluate_many_begin failed: ") + sp_strerror(rc) + " (" + std::to_string(rc) + ")"); }
+    if (rc != SP_OK) { job = nullptr; throw dev_error("sp_sparse_evaluate_many_begin", rc); }
     count = G;
     answers.assign(G, DevAns());
   }
@@ -903,7 +903,7 @@ struct EvalBatch {
       sp_job* j = job;
       job = nullptr;  // sp_job_wait frees it, whatever it returns
       int32_t rc = sp_job_wait(j, (uint8_t*)vals.data());
-      if (rc != SP_OK) throw Error(std::string("sp_job_wait failed: ") + sp_strerror(rc) + " (" + std::to_string(rc) + ")");
+      if (rc != SP_OK) throw dev_error("sp_job_wait", rc);
       collected = true;
     }
     answers.assign(members.size(), DevAns());
@@ -927,56 +927,51 @@ void nizk_verify_batch(Ctx& ctx, const Instance& inst, const NIZK* const* proofs
     return nizk_verify_body(*proofs[m], ctx, inst, *inputs[m], t, gens, digest);
   }, "NIZK::verify_many", verdict);
 }
+
+// The list in batches of at most kVerifyBatch: malformed bytes are a -1 and never enter a gate; run(pp, in, K, v) verifies the K parsed
+// proofs of a batch in lock step.
+template <class Proof, class Run>
+std::vector<int> verify_in_batches(const std::vector<std::pair<const uint8_t*, size_t>>& proofs, const std::vector<const FqVec*>& inputs, Run run) {
+  std::vector<int> verdict(proofs.size(), -1);
+  for (size_t b0 = 0; b0 < proofs.size(); b0 += kVerifyBatch) {
+    const size_t kb = std::min(kVerifyBatch, proofs.size() - b0);
+    std::vector<Proof> parsed(kb);
+    std::vector<const Proof*> pp;
+    std::vector<const FqVec*> in;
+    std::vector<size_t> where;
+    for (size_t i = 0; i < kb; i++)
+      if (Proof::deserialize(proofs[b0 + i].first, proofs[b0 + i].second, &parsed[i])) { pp.push_back(&parsed[i]); in.push_back(inputs[b0 + i]); where.push_back(b0 + i); }
+    if (pp.empty()) continue;
+    std::vector<int> v(pp.size(), 0);
+    run(pp.data(), in.data(), pp.size(), v.data());
+    for (size_t i = 0; i < pp.size(); i++) verdict[where[i]] = v[i];
+  }
+  return verdict;
+}
 }  // namespace
 
 std::vector<int> SNARK::verify_many(Ctx& ctx, const ComputationCommitment& comm, const std::vector<std::pair<const uint8_t*, size_t>>& proofs,
                                     const std::vector<const FqVec*>& inputs, const char* transcript_label, const SNARKGens& gens,
                                     const ResidentCommitment& res) {
-  const size_t K = proofs.size();
-  if (inputs.size() != K || !transcript_label) throw Error("SNARK::verify_many: bad arguments");
+  if (inputs.size() != proofs.size() || !transcript_label) throw Error("SNARK::verify_many: bad arguments");
   if (!res.ops || !res.mem) throw Error("SNARK::verify_many: the commitment's resident point sets are missing");
   for (const FqVec* in : inputs)  // lib.rs:437, before any thread starts: the caller's error, not a proof's
     if (!in || in->size() != comm.num_inputs) throw Error("InvalidNumberOfInputs");
-  std::vector<int> verdict(K, -1);
-  for (size_t b0 = 0; b0 < K; b0 += kVerifyBatch) {
-    const size_t kb = std::min(kVerifyBatch, K - b0);
-    std::vector<SNARK> parsed(kb);
-    std::vector<const SNARK*> pp;
-    std::vector<const FqVec*> in;
-    std::vector<size_t> where;
-    for (size_t i = 0; i < kb; i++)  // malformed bytes are a -1 here and never enter the gate
-      if (SNARK::deserialize(proofs[b0 + i].first, proofs[b0 + i].second, &parsed[i])) { pp.push_back(&parsed[i]); in.push_back(inputs[b0 + i]); where.push_back(b0 + i); }
-    if (pp.empty()) continue;
-    std::vector<int> v(pp.size(), 0);
-    verify_batch(ctx, comm, pp.data(), in.data(), pp.size(), transcript_label, gens, res, v.data());
-    for (size_t i = 0; i < pp.size(); i++) verdict[where[i]] = v[i];
-  }
-  return verdict;
+  return verify_in_batches<SNARK>(proofs, inputs, [&](const SNARK* const* pp, const FqVec* const* in, size_t K, int* v) {
+    verify_batch(ctx, comm, pp, in, K, transcript_label, gens, res, v);
+  });
 }
 
 std::vector<int> NIZK::verify_many(Ctx& ctx, const Instance& inst, const std::vector<std::pair<const uint8_t*, size_t>>& proofs,
                                    const std::vector<const FqVec*>& inputs, const char* transcript_label, const NIZKGens& gens) {
-  const size_t K = proofs.size();
-  if (inputs.size() != K || !transcript_label) throw Error("NIZK::verify_many: bad arguments");
+  if (inputs.size() != proofs.size() || !transcript_label) throw Error("NIZK::verify_many: bad arguments");
   for (const FqVec* in : inputs)  // lib.rs:569, before any thread starts: the caller's error, not a proof's
     if (!in || in->size() != inst.num_inputs) throw Error("InvalidNumberOfInputs");
-  std::vector<int> verdict(K, -1);
-  if (K == 0) return verdict;
+  if (proofs.empty()) return {};
   const std::vector<uint8_t> digest = inst.compute_digest();  // lib.rs:559: once per call, every proof's transcript absorbs the same bytes
-  for (size_t b0 = 0; b0 < K; b0 += kVerifyBatch) {
-    const size_t kb = std::min(kVerifyBatch, K - b0);
-    std::vector<NIZK> parsed(kb);
-    std::vector<const NIZK*> pp;
-    std::vector<const FqVec*> in;
-    std::vector<size_t> where;
-    for (size_t i = 0; i < kb; i++)  // malformed bytes are a -1 here and never enter the gate
-      if (NIZK::deserialize(proofs[b0 + i].first, proofs[b0 + i].second, &parsed[i])) { pp.push_back(&parsed[i]); in.push_back(inputs[b0 + i]); where.push_back(b0 + i); }
-    if (pp.empty()) continue;
-    std::vector<int> v(pp.size(), 0);
-    nizk_verify_batch(ctx, inst, pp.data(), in.data(), pp.size(), transcript_label, gens, digest, v.data());
-    for (size_t i = 0; i < pp.size(); i++) verdict[where[i]] = v[i];
-  }
-  return verdict;
+  return verify_in_batches<NIZK>(proofs, inputs, [&](const NIZK* const* pp, const FqVec* const* in, size_t K, int* v) {
+    nizk_verify_batch(ctx, inst, pp, in, K, transcript_label, gens, digest, v);
+  });
 }
 
 }  // namespace spz

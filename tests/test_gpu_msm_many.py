@@ -1,4 +1,4 @@
-"""sp_msm_var_many / sp_msm_points_many (spartan_amd/csrc/msm_many.hip): K variable-base multi-scalar multiplications of one size in one
+"""sp_msm_var_many / sp_msm_points_many (spartan_amd/csrc/msm_var.hip): K variable-base multi-scalar multiplications of one size in one
 launch chain and one round trip, every one of them byte for byte against the oracle's orc_pt_msm (M.oracle_msm). Sizes sit on the kernels'
 edges (a wavefront, a window-sum block, more than one block), batch sizes 1, 2, 3, 5 and the wide, short batch of a full SNARK batch at 2^10
 (n = 32, K = 64); both sides of the size at which the inputs leave the host-mapped page (read from internal.hpp); cross-talk between

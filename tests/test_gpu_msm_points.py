@@ -1,13 +1,17 @@
 """sp_points / sp_msm_points (spartan_amd/csrc/msm_var.hip): the multi-scalar multiplication over a resident point set, byte for byte against the
 oracle's orc_pt_msm and against sp_msm_var on the same inputs. Sizes sit on the kernels' edges: a wavefront (64), a block of the window-sum
-kernel (256), and finishing blocks of 64, 256 (its 256 lanes exactly full), 320 (the first uneven stride), 1024 and 1088 partial sums."""
+kernel (256), finishing blocks of 64, 256 (its 256 lanes exactly full), 320 (the first uneven stride), 1024 and 1088 partial sums, and the two
+sizes next to where the call's 32 n bytes of scalars leave the host-mapped page for the staging buffer (HMAP_GEN, read from internal.hpp)."""
 import ctypes, random
 import pytest
 from tests.helpers import *
 from tests import msm_var_cases as M
+from tests.test_gpu_msm_many import hmap_gen
 
 pytestmark = pytest.mark.gpu
-SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1024, 1025, 4096, 4097]
+PAGE_N = hmap_gen() // 32      # the last n whose scalars are read from the host-mapped page; PAGE_N + 1 is staged on the device
+SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1024, 1025, 4096, 4097,
+         pytest.param(PAGE_N, id="last_size_on_the_host_page"), pytest.param(PAGE_N + 1, id="first_size_off_the_host_page")]
 KINDS = ["uniform", "sparse", "small", "edge"]
 SP_EINVAL, SP_EPOINT = -1, -4
 

@@ -1,13 +1,16 @@
 """sp_msm_var (spartan_amd/csrc/msm_var.hip): the variable-base multi-scalar multiplication of the verifier, byte for byte against the
 oracle's orc_pt_msm. Sizes sit on the kernel's edges: a wavefront (64), a block of the window-sum kernel (256), the cross-block stage
-(> 256: 2, 4, 5 and 16 blocks; the finishing kernel gives 4 lanes to a window, so 5 blocks is its first uneven split)."""
+(> 256: 2, 4, 5 and 16 blocks; the finishing kernel gives 4 lanes to a window, so 5 blocks is its first uneven split), and the two sizes
+next to where the call's 64 n bytes of input leave the host-mapped page for the staging buffer (HMAP_GEN, read from internal.hpp)."""
 import ctypes, random
 import pytest
 from tests.helpers import *
 from tests import msm_var_cases as M
+from tests.test_gpu_msm_many import hmap_gen
 
 pytestmark = pytest.mark.gpu
-SIZES = [1, 2, 3, 63, 64, 65, 255, 256, 257, 1024, 1025, 4096]
+PAGE_N = hmap_gen() // 64      # the last n whose encodings and scalars are read from the host-mapped page; PAGE_N + 1 is staged on the device
+SIZES = [1, 2, 3, 63, 64, 65, 255, 256, 257, PAGE_N, PAGE_N + 1, 1024, 1025, 4096]
 SP_EINVAL, SP_EPOINT = -1, -4
 
 
@@ -19,9 +22,9 @@ def ctx():
     c.close()
 
 
-def msm_var(ctx, pts, scalars):
+def msm_var(ctx, pts, scalars, fill=0):
     from spartan_amd import capi
-    out = (ctypes.c_uint8 * 32)()
+    out = (ctypes.c_uint8 * 32)(*([fill] * 32))
     rc = capi.lib.sp_msm_var(ctx.h, b"".join(pts), mont_array(scalars), sz(len(pts)), out)
     return rc, bytes(out)
 
@@ -58,8 +61,9 @@ def test_result_does_not_depend_on_what_ran_before(ctx, orc):
     assert a == b == M.oracle_msm(orc, pts, S)
 
 
-@pytest.mark.parametrize("n", [1, 65, 1025])
+@pytest.mark.parametrize("n", [1, 65, 1025, pytest.param(PAGE_N + 1, id="first_size_off_the_host_page")])
 def test_invalid_encoding_is_reported_and_the_context_survives(ctx, orc, n):
+    """SP_EPOINT wherever the bad point sits (the last index included), `out` as the caller left it, and the next call is correct"""
     from tests.test_oracle_pins import RFC_BAD
     rng = random.Random(n)
     good = M.points(orc, n)
@@ -67,8 +71,9 @@ def test_invalid_encoding_is_reported_and_the_context_survives(ctx, orc, n):
     for k, where in enumerate(sorted({0, n // 2, n - 1})):
         pts = list(good)
         pts[where] = bytes.fromhex(RFC_BAD[(k * 7 + n) % len(RFC_BAD)])
-        rc, _ = msm_var(ctx, pts, S)
+        rc, out = msm_var(ctx, pts, S, fill=0xA5)
         assert rc == SP_EPOINT, (n, where, rc)
+        assert out == b"\xa5" * 32, (n, where)
     if n == 1:
         for enc in RFC_BAD:     # every class of RFC 9496 A.2
             assert msm_var(ctx, [bytes.fromhex(enc)], S)[0] == SP_EPOINT, enc
