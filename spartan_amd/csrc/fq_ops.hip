@@ -330,20 +330,34 @@ static void host_sum(const Fq* p, size_t nblk, int K, uint64_t* out) {
     o[k] = acc;
   }
 }
+// k_reduce_partials into the head of the result page; sig: raised by it (sig_none(): the caller ends the trip in another way)
+static void launch_reduce(sp_ctx* c, const Fq* partials, size_t nblk, int K, const DoneSig& sig) {
+  ProfScope ps(c, PF_REDUCE, 32.0 * (double)(nblk * K));
+  hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, c->stream, partials, nblk, K, (Fq*)hres(c), sig);
+}
+// ends the trip of a kernel that left its partial sums at `partials`: on the device, the reduction kernel and its signal; in the
+// host page, the stream's completion flag
+static int32_t reduce_and_wait(sp_ctx* c, const Fq* partials, size_t nblk, int K) {
+  const bool on_host = partials == (const Fq*)hres(c);
+  const DoneSig sig = on_host ? sig_none() : sig_make(c, 1);
+  if (!on_host) launch_reduce(c, partials, nblk, K, sig);
+  SPCHK(sig_wait(c, sig));
+  return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
+}
+// the K sums out of the result page, once the trip has ended
+static void fetch_sums(sp_ctx* c, bool on_host, size_t nblk, int K, uint64_t* out) {
+  if (on_host) host_sum((const Fq*)hres(c), nblk, K, out);
+  else memcpy(out, hres(c), 32 * K);
+}
+// ... as the evaluations of a sum-check round: e(0), e(2) and, but for kind 0, e(3)
+static void fetch_evals(sp_ctx* c, bool on_host, size_t nblk, int kind, uint64_t* out_evals) {
+  uint64_t e[12];
+  fetch_sums(c, on_host, nblk, 3, e);
+  memcpy(out_evals, e, kind == 0 ? 64 : 96);
+}
 int32_t reduce_and_fetch(sp_ctx* c, Fq* partials, size_t nblk, int K, uint64_t* out) {
-  if (partials != (Fq*)hres(c)) {
-    DoneSig sig = sig_make(c, 1);
-    {
-      ProfScope ps(c, PF_REDUCE, 32.0 * (double)(nblk * K));
-      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, c->stream, (const Fq*)partials, nblk, K, (Fq*)hres(c), sig);
-    }
-    SPCHK(sig_wait(c, sig));
-    memcpy(out, hres(c), 32 * K);
-    return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
-  }
-  SPCHK(sync_spin(c));
-  if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  host_sum((const Fq*)hres(c), nblk, K, out);
+  SPCHK(reduce_and_wait(c, partials, nblk, K));
+  fetch_sums(c, partials == (Fq*)hres(c), nblk, K, out);
   return SP_OK;
 }
 
@@ -395,38 +409,78 @@ int32_t sp_eq_expand(sp_ctx* c, const uint64_t* r, size_t ell, sp_table** out) {
   return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
 }
 
-static int32_t tabs_check(sp_ctx* c, sp_table* const* tabs, size_t ntabs, size_t need, Tabs4* T, size_t* len) {
-  if (!c || !tabs || ntabs != need) return SP_EINVAL;
-  size_t l = tabs[0] ? tabs[0]->len : 0;
-  for (size_t k = 0; k < ntabs; k++) {
-    if (!tabs[k] || tabs[k]->len != l) return SP_EINVAL;
-    T->p[k] = tabs[k]->d;
+// ---- the single-instance sum-check rounds: kind 0 (A B), 1 (A B C), 2 (A (B C - D)) on kind + 2 tables of one power-of-two length.
+// The shape of one round, computed once per call: `work` indices (len / 2 of an evaluation alone, len / 4 of a bind-and-evaluate) on
+// nblk blocks, which leave nblk x 3 partial sums at `partials`: in the host page (on_host), where the calling thread adds them, or in
+// the scratch, from where k_reduce_partials does
+struct RoundPlan {
+  Tabs4 T;
+  size_t len, work, nblk;
+  bool tiny, on_host;  // tiny: k_sc_bind_eval_tiny
+  Fq* partials;
+};
+// the argument checks of every round call (a refused call has touched nothing), then the device
+static int32_t plan_tables(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, size_t min_len, RoundPlan* p) {
+  if (kind < 0 || kind > 2 || !c || !tabs || ntabs != (size_t)kind + 2) return SP_EINVAL;
+  p->len = tabs[0] ? tabs[0]->len : 0;
+  for (size_t k = 0; k < 4; k++) {
+    if (k < ntabs && (!tabs[k] || tabs[k]->len != p->len)) return SP_EINVAL;
+    p->T.p[k] = k < ntabs ? tabs[k]->d : nullptr;
   }
-  for (size_t k = ntabs; k < 4; k++) T->p[k] = nullptr;
-  if (l < 2 || !is_pow2(l)) return SP_EINVAL;
-  *len = l;
+  if (p->len < min_len || !is_pow2(p->len)) return SP_EINVAL;
+  HIPCHK(hipSetDevice(c->dev));
   return SP_OK;
 }
-int32_t sp_sumcheck_eval(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, uint64_t* out_evals) {
-  if (kind < 0 || kind > 2 || !out_evals) return SP_EINVAL;
-  Tabs4 T;
-  size_t len;
-  SPCHK(tabs_check(c, tabs, ntabs, kind == 0 ? 2 : (kind == 1 ? 3 : 4), &T, &len));
-  HIPCHK(hipSetDevice(c->dev));
-  size_t half = len / 2, nblk = half <= 256 ? 1 : grid_for(half, 1024);
+static int32_t plan_sums(sp_ctx* c, size_t work, bool tiny, size_t nblk, bool start_form, RoundPlan* p) {
   SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * (nblk * 3 + 3)));
-  Fq* partials = partials_dst(c, nblk, 3);
+  // sp_sumcheck_bind_eval_start: the streaming form's sums go to the scratch whatever their number, so that it always ends in
+  // k_reduce_partials, whose signal is what _collect waits for
+  Fq* partials = tiny ? partials_dst(c, nblk, 3) : (Fq*)c->scratch;
+  if (!start_form) partials = partials_dst(c, nblk, 3);
+  p->work = work, p->tiny = tiny, p->nblk = nblk, p->partials = partials, p->on_host = partials == (Fq*)hres(c);
+  return SP_OK;
+}
+static int32_t eval_plan(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, RoundPlan* p) {
+  SPCHK(plan_tables(c, kind, tabs, ntabs, 2, p));
+  const size_t half = p->len / 2, nblk = half <= 256 ? 1 : grid_for(half, 1024);
+  return plan_sums(c, half, false, nblk, false, p);
+}
+static int32_t round_plan(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, bool start_form, RoundPlan* p) {
+  SPCHK(plan_tables(c, kind, tabs, ntabs, 4, p));
+  const size_t quarter = p->len / 4;
+  const bool tiny = kind != 1 && quarter <= 8192;  // latency-bound rounds: one index per 8 lanes
+  const size_t nblk = tiny ? (quarter + 31) / 32 : grid_for(quarter, 1024);
+  return plan_sums(c, quarter, tiny, nblk, start_form, p);
+}
+// Queues the bind at r and the next round's evaluation on the main stream and halves the tables' lengths. sig: handed to the tiny
+// form, whose last workgroup raises it (sig_none(): something queued behind it ends the trip); the streaming form raises nothing
+static void launch_bind_eval(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, const uint64_t r[4], const RoundPlan& p, const DoneSig& sig) {
+  const size_t quarter = p.work;
+  const Fq rr = limbs(r);
+  const dim3 grid((unsigned)p.nblk), blk(256);
   {
-    ProfScope ps(c, PF_SC_EVAL, 32.0 * (double)len * (double)ntabs, nullptr, (kind == 0 ? 2.0 : 6.0) * (double)half);
-    if (kind == 0) hipLaunchKernelGGL(k_sc_eval<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, half, partials);
-    if (kind == 1) hipLaunchKernelGGL(k_sc_eval<1>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, half, partials);
-    if (kind == 2) hipLaunchKernelGGL(k_sc_eval<2>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, half, partials);
+    ProfScope ps(c, PF_SC_BIND_EVAL, 48.0 * (double)p.len * (double)ntabs, nullptr, (kind == 0 ? 6.0 : (kind == 1 ? 12.0 : 14.0)) * (double)quarter);
+    if (p.tiny && kind == 0) hipLaunchKernelGGL(k_sc_bind_eval_tiny<0>, grid, blk, 0, c->stream, p.T, quarter, rr, p.partials, sig);
+    else if (p.tiny) hipLaunchKernelGGL(k_sc_bind_eval_tiny<2>, grid, blk, 0, c->stream, p.T, quarter, rr, p.partials, sig);
+    else if (kind == 0) hipLaunchKernelGGL(k_sc_bind_eval<0>, grid, blk, 0, c->stream, p.T, quarter, rr, p.partials);
+    else if (kind == 1) hipLaunchKernelGGL(k_sc_bind_eval<1>, grid, blk, 0, c->stream, p.T, quarter, rr, p.partials);
+    else hipLaunchKernelGGL(k_sc_bind_eval<2>, grid, blk, 0, c->stream, p.T, quarter, rr, p.partials);
   }
-  uint64_t e[12];
-  SPCHK(reduce_and_fetch(c, partials, nblk, 3, e));
-  memcpy(out_evals, e, 32);
-  memcpy(out_evals + 4, e + 4, 32);
-  if (kind != 0) memcpy(out_evals + 8, e + 8, 32);
+  for (size_t k = 0; k < ntabs; k++) tabs[k]->len = p.len / 2;
+}
+int32_t sp_sumcheck_eval(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, uint64_t* out_evals) {
+  if (!out_evals) return SP_EINVAL;
+  RoundPlan p;
+  SPCHK(eval_plan(c, kind, tabs, ntabs, &p));
+  const dim3 grid((unsigned)p.nblk), blk(256);
+  {
+    ProfScope ps(c, PF_SC_EVAL, 32.0 * (double)p.len * (double)ntabs, nullptr, (kind == 0 ? 2.0 : 6.0) * (double)p.work);
+    if (kind == 0) hipLaunchKernelGGL(k_sc_eval<0>, grid, blk, 0, c->stream, p.T, p.work, p.partials);
+    if (kind == 1) hipLaunchKernelGGL(k_sc_eval<1>, grid, blk, 0, c->stream, p.T, p.work, p.partials);
+    if (kind == 2) hipLaunchKernelGGL(k_sc_eval<2>, grid, blk, 0, c->stream, p.T, p.work, p.partials);
+  }
+  SPCHK(reduce_and_wait(c, p.partials, p.nblk, 3));
+  fetch_evals(c, p.on_host, p.nblk, kind, out_evals);
   return SP_OK;
 }
 int32_t sp_table_bind_top(sp_ctx* c, sp_table* const* tabs, size_t ntabs, const uint64_t r[4]) {
@@ -440,8 +494,7 @@ int32_t sp_table_bind_top(sp_ctx* c, sp_table* const* tabs, size_t ntabs, const 
       if (tabs[m] == tabs[k]) return SP_EINVAL;  // a table listed twice would be bound twice (as in bind_top_list)
   }
   HIPCHK(hipSetDevice(c->dev));
-  Fq rr;
-  memcpy(rr.l, r, 32);
+  const Fq rr = limbs(r);
   size_t half = len / 2;
   for (size_t k0 = 0; k0 < ntabs; k0 += 4) {
     size_t nk = ntabs - k0 < 4 ? ntabs - k0 : 4;
@@ -454,11 +507,6 @@ int32_t sp_table_bind_top(sp_ctx* c, sp_table* const* tabs, size_t ntabs, const 
     for (size_t k = 0; k < nk; k++) tabs[k0 + k]->len = half;
   }
   return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
-}
-static Fq limbs4(const uint64_t* p) {
-  Fq x;
-  memcpy(x.l, p, 32);
-  return x;
 }
 static int32_t bind_top_list(sp_ctx* c, sp_table* const* tabs, size_t ntabs, const uint64_t r[4], uint64_t* out_heads) {
   if (!c || !tabs || !r || ntabs == 0 || 8 * ntabs > HMAP_GEN || 32 * ntabs > HMAP_SIZE - HMAP_IN) return SP_EINVAL;
@@ -477,7 +525,7 @@ static int32_t bind_top_list(sp_ctx* c, sp_table* const* tabs, size_t ntabs, con
   DoneSig sig = sig_make(c, grid_for(ntabs * half));
   {
     ProfScope ps(c, PF_SC_BIND, 48.0 * (double)len * (double)ntabs);
-    hipLaunchKernelGGL(k_bind_top_list, dim3((unsigned)grid_for(ntabs * half)), dim3(256), 0, c->stream, dp, ntabs, half, limbs4(r),
+    hipLaunchKernelGGL(k_bind_top_list, dim3((unsigned)grid_for(ntabs * half)), dim3(256), 0, c->stream, dp, ntabs, half, limbs(r),
                        out_heads ? (Fq*)hres(c) : (Fq*)nullptr, sig);
   }
   for (size_t k = 0; k < ntabs; k++) tabs[k]->len = half;
@@ -490,71 +538,29 @@ int32_t sp_table_bind_top_heads(sp_ctx* c, sp_table* const* tabs, size_t ntabs, 
   return bind_top_list(c, tabs, ntabs, r, out_heads);
 }
 int32_t sp_sumcheck_bind_eval(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, const uint64_t r[4], uint64_t* out_evals) {
-  if (kind < 0 || kind > 2 || !out_evals || !r) return SP_EINVAL;
-  Tabs4 T;
-  size_t len;
-  SPCHK(tabs_check(c, tabs, ntabs, kind == 0 ? 2 : (kind == 1 ? 3 : 4), &T, &len));
-  if (len < 4) return SP_EINVAL;
-  HIPCHK(hipSetDevice(c->dev));
-  Fq rr;
-  memcpy(rr.l, r, 32);
-  size_t quarter = len / 4;
-  bool tiny = kind != 1 && quarter <= 8192;  // latency-bound rounds: one index per 8 lanes
-  size_t nblk = tiny ? (quarter + 31) / 32 : grid_for(quarter, 1024);
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * (nblk * 3 + 3)));
-  Fq* partials = partials_dst(c, nblk, 3);
-  {
-    ProfScope ps(c, PF_SC_BIND_EVAL, 48.0 * (double)len * (double)ntabs, nullptr, (kind == 0 ? 6.0 : (kind == 1 ? 12.0 : 14.0)) * (double)quarter);
-    if (tiny && kind == 0) hipLaunchKernelGGL(k_sc_bind_eval_tiny<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials, sig_none());
-    else if (tiny) hipLaunchKernelGGL(k_sc_bind_eval_tiny<2>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials, sig_none());
-    else if (kind == 0) hipLaunchKernelGGL(k_sc_bind_eval<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-    else if (kind == 1) hipLaunchKernelGGL(k_sc_bind_eval<1>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-    else hipLaunchKernelGGL(k_sc_bind_eval<2>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-  }
-  for (size_t k = 0; k < ntabs; k++) tabs[k]->len = len / 2;
-  uint64_t e[12];
-  SPCHK(reduce_and_fetch(c, partials, nblk, 3, e));
-  memcpy(out_evals, e, 32);
-  memcpy(out_evals + 4, e + 4, 32);
-  if (kind != 0) memcpy(out_evals + 8, e + 8, 32);
+  if (!out_evals || !r) return SP_EINVAL;
+  RoundPlan p;
+  SPCHK(round_plan(c, kind, tabs, ntabs, false, &p));
+  launch_bind_eval(c, kind, tabs, ntabs, r, p, sig_none());
+  SPCHK(reduce_and_wait(c, p.partials, p.nblk, 3));
+  fetch_evals(c, p.on_host, p.nblk, kind, out_evals);
   return SP_OK;
 }
 // The same round in two halves: _start queues the bind and the evaluation and returns; _collect waits for the sums. The
 // caller (the ZK sum-check of the host driver) computes the round's commitments on its own core in between. No other call
 // on this context may come between the two: the sums travel through the context's result page.
 int32_t sp_sumcheck_bind_eval_start(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, const uint64_t r[4]) {
-  if (kind < 0 || kind > 2 || !r) return SP_EINVAL;
-  Tabs4 T;
-  size_t len;
-  SPCHK(tabs_check(c, tabs, ntabs, kind == 0 ? 2 : (kind == 1 ? 3 : 4), &T, &len));
-  if (len < 4 || c->pend_eval.active) return SP_EINVAL;
-  HIPCHK(hipSetDevice(c->dev));
-  Fq rr;
-  memcpy(rr.l, r, 32);
-  size_t quarter = len / 4;
-  bool tiny = kind != 1 && quarter <= 8192;
-  size_t nblk = tiny ? (quarter + 31) / 32 : grid_for(quarter, 1024);
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * (nblk * 3 + 3)));
-  Fq* partials = tiny ? partials_dst(c, nblk, 3) : (Fq*)c->scratch;
-  const bool on_host = partials == (Fq*)hres(c);
-  DoneSig sig = sig_make(c, on_host ? nblk : 1);
-  {
-    ProfScope ps(c, PF_SC_BIND_EVAL, 48.0 * (double)len * (double)ntabs, nullptr, (kind == 0 ? 6.0 : (kind == 1 ? 12.0 : 14.0)) * (double)quarter);
-    if (tiny && kind == 0) hipLaunchKernelGGL(k_sc_bind_eval_tiny<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials, on_host ? sig : sig_none());
-    else if (tiny) hipLaunchKernelGGL(k_sc_bind_eval_tiny<2>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials, on_host ? sig : sig_none());
-    else if (kind == 0) hipLaunchKernelGGL(k_sc_bind_eval<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-    else if (kind == 1) hipLaunchKernelGGL(k_sc_bind_eval<1>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-    else hipLaunchKernelGGL(k_sc_bind_eval<2>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-  }
-  for (size_t k = 0; k < ntabs; k++) tabs[k]->len = len / 2;
-  if (!on_host) {
-    ProfScope ps(c, PF_REDUCE, 32.0 * (double)(nblk * 3));
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, c->stream, (const Fq*)partials, nblk, 3, (Fq*)hres(c), sig);
-  }
+  if (!r || (c && c->pend_eval.active)) return SP_EINVAL;  // one round in flight at a time
+  RoundPlan p;
+  SPCHK(round_plan(c, kind, tabs, ntabs, true, &p));
+  // one signal ends the trip: raised by the last of the tiny form's workgroups when the sums are in the host page, by the reduction kernel otherwise
+  const DoneSig sig = sig_make(c, p.on_host ? p.nblk : 1);
+  launch_bind_eval(c, kind, tabs, ntabs, r, p, p.on_host ? sig : sig_none());
+  if (!p.on_host) launch_reduce(c, p.partials, p.nblk, 3, sig);
   c->pend_eval.active = true;
   c->pend_eval.kind = kind;
-  c->pend_eval.nblk = nblk;
-  c->pend_eval.on_host = on_host;
+  c->pend_eval.nblk = p.nblk;
+  c->pend_eval.on_host = p.on_host;
   c->pend_eval.seq = sig.flag ? sig.seq : sync_post(c);
   return SP_OK;
 }
@@ -563,22 +569,14 @@ int32_t sp_sumcheck_bind_eval_collect(sp_ctx* c, uint64_t* out_evals) {
   c->pend_eval.active = false;
   SPCHK(sync_wait(c, c->pend_eval.seq));
   if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  uint64_t e[12];
-  if (c->pend_eval.on_host) host_sum((const Fq*)hres(c), c->pend_eval.nblk, 3, e);
-  else memcpy(e, hres(c), 96);
-  memcpy(out_evals, e, 32);
-  memcpy(out_evals + 4, e + 4, 32);
-  if (c->pend_eval.kind != 0) memcpy(out_evals + 8, e + 8, 32);
+  fetch_evals(c, c->pend_eval.on_host, c->pend_eval.nblk, c->pend_eval.kind, out_evals);
   return SP_OK;
 }
 int32_t sp_sumcheck_bind_eval_commit(sp_ctx* c, int kind, sp_table* const* tabs, size_t ntabs, const uint64_t r[4], uint64_t* out_evals,
                                      const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, uint8_t* out_points) {
-  if (kind < 0 || kind > 2 || !out_evals || !r || !out_points) return SP_EINVAL;
-  Tabs4 T;
-  size_t len;
-  SPCHK(tabs_check(c, tabs, ntabs, kind == 0 ? 2 : (kind == 1 ? 3 : 4), &T, &len));
-  if (len < 4) return SP_EINVAL;
-  HIPCHK(hipSetDevice(c->dev));
+  if (!out_evals || !r || !out_points) return SP_EINVAL;
+  RoundPlan p;
+  SPCHK(round_plan(c, kind, tabs, ntabs, false, &p));
   if (c->device_encode) {  // diagnostic mode (every encode on the GPU): the two halves one after the other
     SPCHK(sp_sumcheck_bind_eval(c, kind, tabs, ntabs, r, out_evals));
     return sp_msm_indexed(c, g, idx, cols, S, rows, out_points);
@@ -587,70 +585,50 @@ int32_t sp_sumcheck_bind_eval_commit(sp_ctx* c, int kind, sp_table* const* tabs,
   constexpr size_t SUMS_OFF = HMAP_SIZE - HMAP_IN - 1024;  // evaluations / partial sums at the head of the result area, row sums at its tail
   SPCHK(msm_small_enqueue(c, c->stream_side, g, idx, cols, S, rows, hres(c) + SUMS_OFF));
   HIPCHK(hipEventRecord(c->side_ev, c->stream_side));
-  Fq rr;
-  memcpy(rr.l, r, 32);
-  size_t quarter = len / 4;
-  bool tiny = kind != 1 && quarter <= 8192;  // latency-bound rounds: one index per 8 lanes
-  size_t nblk = tiny ? (quarter + 31) / 32 : grid_for(quarter, 1024);
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * (nblk * 3 + 3)));
-  Fq* partials = partials_dst(c, nblk, 3);
-  {
-    ProfScope ps(c, PF_SC_BIND_EVAL, 48.0 * (double)len * (double)ntabs, nullptr, (kind == 0 ? 6.0 : (kind == 1 ? 12.0 : 14.0)) * (double)quarter);
-    if (tiny && kind == 0) hipLaunchKernelGGL(k_sc_bind_eval_tiny<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials, sig_none());
-    else if (tiny) hipLaunchKernelGGL(k_sc_bind_eval_tiny<2>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials, sig_none());
-    else if (kind == 0) hipLaunchKernelGGL(k_sc_bind_eval<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-    else if (kind == 1) hipLaunchKernelGGL(k_sc_bind_eval<1>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-    else hipLaunchKernelGGL(k_sc_bind_eval<2>, dim3((unsigned)nblk), dim3(256), 0, c->stream, T, quarter, rr, partials);
-  }
-  for (size_t k = 0; k < ntabs; k++) tabs[k]->len = len / 2;
-  if (partials != (Fq*)hres(c)) {
-    ProfScope ps(c, PF_REDUCE, 32.0 * (double)(nblk * 3));
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, c->stream, (const Fq*)partials, nblk, 3, (Fq*)hres(c), sig_none());
-  }
+  launch_bind_eval(c, kind, tabs, ntabs, r, p, sig_none());
+  if (!p.on_host) launch_reduce(c, p.partials, p.nblk, 3, sig_none());
   HIPCHK(hipStreamWaitEvent(c->stream, c->side_ev, 0));  // one completion for both streams
   SPCHK(sync_spin(c));
   if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  uint64_t e[12];
-  if (partials == (Fq*)hres(c)) host_sum((const Fq*)hres(c), nblk, 3, e);
-  else memcpy(e, hres(c), 96);
-  memcpy(out_evals, e, 32);
-  memcpy(out_evals + 4, e + 4, 32);
-  if (kind != 0) memcpy(out_evals + 8, e + 8, 32);
+  fetch_evals(c, p.on_host, p.nblk, kind, out_evals);
   Pt sums[8];
   memcpy(sums, hres(c) + SUMS_OFF, sizeof(Pt) * rows);
   pt_compress_many(sums, rows, out_points);
   return SP_OK;
 }
+// L (Lsz scalars at dL) times Z viewed as Lsz rows of R: the scratch takes the chunk sums and leaves room for R results behind them
+struct VecmatPlan {
+  size_t R, jchunk, nchunks;
+};
+static int32_t vecmat_plan(sp_ctx* c, size_t Lsz, const sp_table* Z, VecmatPlan* p) {
+  const size_t R = Z->len / Lsz, jchunk = vecmat_jchunk(Lsz, R);
+  *p = VecmatPlan{R, jchunk, (Lsz + jchunk - 1) / jchunk};
+  return ensure(&c->scratch, &c->scratch_cap, 32 * (p->nchunks * R + R));
+}
+static void vecmat_launch(sp_ctx* c, const VecmatPlan& p, const Fq* dL, size_t Lsz, const sp_table* Z, Fq* dst) {
+  const size_t R = p.R, nchunks = p.nchunks;
+  Fq* partial = (Fq*)c->scratch;
+  ProfScope ps(c, PF_VECMAT, 32.0 * (double)Z->len + 32.0 * (double)R, nullptr, (double)Z->len);
+  hipLaunchKernelGGL(k_vecmat, dim3((unsigned)((R + 63) / 64), (unsigned)nchunks), dim3(256), 0, c->stream, dL, Lsz, (const Fq*)Z->d, R, p.jchunk, partial);
+  hipLaunchKernelGGL(k_colsum, dim3((unsigned)((R + 31) / 32)), dim3(256), 0, c->stream, (const Fq*)partial, nchunks, R, dst);
+}
 int32_t sp_vecmat(sp_ctx* c, const uint64_t* L, size_t Lsz, const sp_table* Z, uint64_t* out) {
   if (!c || !L || !Z || !out || Lsz == 0 || Z->len % Lsz) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
-  size_t R = Z->len / Lsz;
   SPCHK(ensure_dstage(c, 32 * Lsz));
   SPCHK(stage_in(c, 0, L, 32 * Lsz));
-  size_t jchunk = vecmat_jchunk(Lsz, R), nchunks = (Lsz + jchunk - 1) / jchunk;
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * (nchunks * R + R)));
-  Fq* partial = (Fq*)c->scratch;
-  Fq* dres = partial + nchunks * R;
-  {
-    ProfScope ps(c, PF_VECMAT, 32.0 * (double)Z->len + 32.0 * (double)R, nullptr, (double)Z->len);
-    hipLaunchKernelGGL(k_vecmat, dim3((unsigned)((R + 63) / 64), (unsigned)nchunks), dim3(256), 0, c->stream, (const Fq*)c->dstage, Lsz,
-                       (const Fq*)Z->d, R, jchunk, partial);
-    hipLaunchKernelGGL(k_colsum, dim3((unsigned)((R + 31) / 32)), dim3(256), 0, c->stream, (const Fq*)partial, nchunks, R, dres);
-  }
-  SPCHK(fetch_out(c, dres, out, 32 * R));
+  VecmatPlan p;
+  SPCHK(vecmat_plan(c, Lsz, Z, &p));
+  Fq* dres = (Fq*)c->scratch + p.nchunks * p.R;
+  vecmat_launch(c, p, (const Fq*)c->dstage, Lsz, Z, dres);
+  SPCHK(fetch_out(c, dres, out, 32 * p.R));
   return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
 }
 static int32_t vecmat_enqueue(sp_ctx* c, const Fq* dL, size_t Lsz, const sp_table* Z, sp_table** out) {
-  size_t R = Z->len / Lsz;
-  size_t jchunk = vecmat_jchunk(Lsz, R), nchunks = (Lsz + jchunk - 1) / jchunk;
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * (nchunks * R + R)));
-  SPCHK(table_new(c, R, false, out));
-  Fq* partial = (Fq*)c->scratch;
-  {
-    ProfScope ps(c, PF_VECMAT, 32.0 * (double)Z->len + 32.0 * (double)R, nullptr, (double)Z->len);
-    hipLaunchKernelGGL(k_vecmat, dim3((unsigned)((R + 63) / 64), (unsigned)nchunks), dim3(256), 0, c->stream, dL, Lsz, (const Fq*)Z->d, R, jchunk, partial);
-    hipLaunchKernelGGL(k_colsum, dim3((unsigned)((R + 31) / 32)), dim3(256), 0, c->stream, (const Fq*)partial, nchunks, R, (*out)->d);
-  }
+  VecmatPlan p;
+  SPCHK(vecmat_plan(c, Lsz, Z, &p));
+  SPCHK(table_new(c, p.R, false, out));
+  vecmat_launch(c, p, dL, Lsz, Z, (*out)->d);
   return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
 }
 int32_t sp_vecmat_dev(sp_ctx* c, const uint64_t* L, size_t Lsz, const sp_table* Z, sp_table** out) {

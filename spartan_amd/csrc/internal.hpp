@@ -339,6 +339,11 @@ static inline size_t grid_for(size_t work, size_t maxblocks = 2048) {
   return b > maxblocks ? maxblocks : b;
 }
 static inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
+static inline Fq limbs(const uint64_t* p) {  // a caller's scalar (4 Montgomery limbs) as a kernel argument
+  Fq x;
+  memcpy(x.l, p, 32);
+  return x;
+}
 static inline size_t ilog2(size_t x) {
   size_t l = 0;
   while (((size_t)1 << l) < x) l++;

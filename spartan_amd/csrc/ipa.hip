@@ -183,12 +183,6 @@ __global__ void __launch_bounds__(256) k_ipa_init(const Fq* __restrict__ a_src, 
   }
 }
 
-static Fq limbs(const uint64_t* p) {
-  Fq x;
-  memcpy(x.l, p, 32);
-  return x;
-}
-
 extern "C" {
 
 void sp_ipa_free(sp_ipa* ipa) {
@@ -484,8 +478,7 @@ static bool ipa_finish_on_host(sp_ipa* ipa, const uint64_t d[4], const uint64_t 
   if (off || !ipa->have_fin || !ipa->fold_pending || ipa->ctx->device_encode) return false;
   const Fq &a0 = ipa->fin_a[0], &a1 = ipa->fin_a[1], &b0 = ipa->fin_b[0], &b1 = ipa->fin_b[1], &u = ipa->fu, &ui = ipa->fu_inv;
   if (fq_is_zero(a0) || fq_is_zero(a1)) return false;
-  Fq dd, rr;
-  memcpy(dd.l, d, 32); memcpy(rr.l, r, 32);
+  const Fq dd = limbs(d), rr = limbs(r);
   const Fq inv01 = fq_invert(fq_mul(a0, a1));               // one inversion for both (the values derive from the witness: the constant chain)
   const Fq inv0 = fq_mul(inv01, a1), inv1 = fq_mul(inv01, a0);
   const Fq k0 = fq_mul(fq_mul(dd, u), inv0), k1 = fq_mul(fq_mul(dd, ui), inv1);
@@ -506,9 +499,7 @@ int32_t sp_host_msm2_probe(const uint8_t p1[32], const uint64_t k1[4], const uin
   if (!p1 || !k1 || !p2 || !k2 || !out) return SP_EINVAL;
   Pt P1, P2;
   if (!pt_decompress(p1, &P1) || !pt_decompress(p2, &P2)) return SP_EPOINT;
-  Fq a, b;
-  memcpy(a.l, k1, 32); memcpy(b.l, k2, 32);
-  pt_compress(pt_var_msm2(P1, a, P2, b), out);
+  pt_compress(pt_var_msm2(P1, limbs(k1), P2, limbs(k2)), out);
   return SP_OK;
 }
 // Device-free form of sp_msm_var for the few-term combinations of the verifiers (sumcheck.rs:127, r1csproof.rs:426,470, bullet.rs:216): sum_j S[j] P[j]
@@ -522,9 +513,7 @@ int32_t sp_host_msm_var(const uint8_t* points, const uint64_t* S, size_t n, uint
     Pt p;
     if (!pt_decompress(points + 32 * j, &p)) return SP_EPOINT;
     pt_var_table(p, &T[j * SP_VAR_TABLE]);
-    Fq k;
-    memcpy(k.l, S + 4 * j, 32);
-    fq_signed_digits4(fq_from_mont(k), &D[j * SP_VAR_WINDOWS]);
+    fq_signed_digits4(fq_from_mont(limbs(S + 4 * j)), &D[j * SP_VAR_WINDOWS]);
   }
   Pt acc = pt_identity();
   bool started = false;

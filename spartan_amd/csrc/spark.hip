@@ -515,12 +515,6 @@ __global__ void __launch_bounds__(256) k_dot3_many(const Fq* const* __restrict__
   if (threadIdx.x == 0) st_fq(partials + (size_t)blockIdx.y * gridDim.x + blockIdx.x, acc[0]);
 }
 
-static Fq limbs(const uint64_t* p) {
-  Fq x;
-  memcpy(x.l, p, 32);
-  return x;
-}
-
 extern "C" {
 
 int32_t sp_index_upload(sp_ctx* c, const uint64_t* idx, size_t n, sp_index** out) {
@@ -689,26 +683,27 @@ static int32_t batched_setup(sp_ctx* c, sp_table* const* A, sp_table* const* B, 
 // while a second launch to add them costs ~10 us on the critical path.
 static bool host_sums(size_t nblk, size_t ninst) { return nblk == 1 || 96 * nblk * ninst <= HOST_SUM_BYTES; }
 // sig: the completion signal of the trip — already raised by the evaluation kernel when it wrote its partials into the
-// host page (on_host), raised by the reduction kernel launched here otherwise
-static int32_t batched_finish(sp_ctx* c, Fq* partials, size_t nblk, size_t ninst, uint64_t* out, const DoneSig& sig) {
+// host page (on_host), raised by the reduction kernel launched here otherwise. K sums per instance: 3, or the 4 of the factored forms,
+// whose partials are never in the host page
+static int32_t batched_finish(sp_ctx* c, Fq* partials, size_t nblk, size_t ninst, int K, uint64_t* out, const DoneSig& sig) {
   if (partials != (Fq*)hres(c)) {
     {
-      ProfScope ps(c, PF_REDUCE, 96.0 * (double)(nblk * ninst));
-      hipLaunchKernelGGL(k_reduce_partials_batched, dim3((unsigned)ninst), dim3(256), 0, c->stream, (const Fq*)partials, nblk, 3, (Fq*)hres(c), sig);
+      ProfScope ps(c, PF_REDUCE, 32.0 * K * (double)(nblk * ninst));
+      hipLaunchKernelGGL(k_reduce_partials_batched, dim3((unsigned)ninst), dim3(256), 0, c->stream, (const Fq*)partials, nblk, K, (Fq*)hres(c), sig);
     }
     SPCHK(sig_wait(c, sig));
-    memcpy(out, hres(c), 96 * ninst);
+    memcpy(out, hres(c), 32 * K * ninst);
     return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
   }
   SPCHK(sig_wait(c, sig));
   if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  const Fq* p = (const Fq*)hres(c);  // [inst][blk][3]
+  const Fq* p = (const Fq*)hres(c);  // [inst][blk][K]
   Fq* o = (Fq*)out;
   for (size_t i = 0; i < ninst; i++)
-    for (int k = 0; k < 3; k++) {
-      Fq acc = p[(i * nblk) * 3 + k];
-      for (size_t b = 1; b < nblk; b++) acc = fq_add(acc, p[(i * nblk + b) * 3 + k]);
-      o[3 * i + k] = acc;
+    for (int k = 0; k < K; k++) {
+      Fq acc = p[(i * nblk) * K + k];
+      for (size_t b = 1; b < nblk; b++) acc = fq_add(acc, p[(i * nblk + b) * K + k]);
+      o[K * i + k] = acc;
     }
   return SP_OK;
 }
@@ -731,7 +726,7 @@ int32_t sp_sumcheck_eval_batched(sp_ctx* c, sp_table* const* A, sp_table* const*
     if (tiny) hipLaunchKernelGGL(k_cubic_eval_tiny, dim3((unsigned)nblk, (unsigned)ninst), dim3(256), 0, c->stream, Tdev, IN, half, partials, on_host ? sig : sig_none());
     else hipLaunchKernelGGL(k_cubic_eval_batched, dim3((unsigned)nblk, (unsigned)ninst), dim3(256), 0, c->stream, Tdev, IN, half, partials);
   }
-  return batched_finish(c, partials, nblk, ninst, out, sig);
+  return batched_finish(c, partials, nblk, ninst, 3, out, sig);
 }
 int32_t sp_sumcheck_bind_eval_batched(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, const uint64_t r[4],
                                       uint64_t* out) {
@@ -766,22 +761,13 @@ int32_t sp_sumcheck_bind_eval_batched(sp_ctx* c, sp_table* const* A, sp_table* c
   for (size_t k = 0; k < ninst; k++) { A[k]->len = len / 2; B[k]->len = len / 2; }
   for (size_t k = 0; k < ninst; k++)
     if (C[k]->len == len) table_swap_to_alt(C[k], len / 2);
-  return batched_finish(c, partials, nblk, ninst, out, sig);
+  return batched_finish(c, partials, nblk, ninst, 3, out, sig);
 }
 
 // ---- the factored forms (kernels above): instances [0, neq) are product-circuit instances sharing the eq table C[0] (never bound, its
 // length stays what it was: the rounds read its leading entries), instances [neq, ninst) are generic. out[4 * ninst]: {q(0), q(2), 0, 0} for
 // the former, {e(0), e(1), e(2), e(3)} for the latter. Throughput-sized tables only (the latency forms have no factored twin): SP_EINVAL
 // below 65536 entries, the caller hands over to the generic rounds there (sp_table_scale_prefix).
-static int32_t batched_finish4(sp_ctx* c, Fq* partials, size_t nblk, size_t ninst, uint64_t* out, const DoneSig& sig) {
-  {
-    ProfScope ps(c, PF_REDUCE, 128.0 * (double)(nblk * ninst));
-    hipLaunchKernelGGL(k_reduce_partials_batched, dim3((unsigned)ninst), dim3(256), 0, c->stream, (const Fq*)partials, nblk, 4, (Fq*)hres(c), sig);
-  }
-  SPCHK(sig_wait(c, sig));
-  memcpy(out, hres(c), 128 * ninst);
-  return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
-}
 static int32_t eq_form_check(sp_table* const* C, size_t ninst, size_t neq, size_t len) {
   if (neq == 0 || neq > ninst || ninst > 24 || 128 * ninst > HOST_SUM_BYTES) return SP_EINVAL;
   for (size_t k = 0; k < neq; k++)
@@ -830,7 +816,7 @@ int32_t sp_sumcheck_eval_batched_eq(sp_ctx* c, sp_table* const* A, sp_table* con
     if (ninst > neq)
       hipLaunchKernelGGL(k_cubic_eval_batched_eq<true>, dim3((unsigned)nblk, (unsigned)(ninst - neq)), dim3(256), 0, c->stream, IN, (unsigned)neq, half, partials);
   }
-  return batched_finish4(c, partials, nblk, ninst, out, sig);
+  return batched_finish(c, partials, nblk, ninst, 4, out, sig);
 }
 int32_t sp_sumcheck_bind_eval_batched_eq(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, size_t neq, const uint64_t r[4],
                                          uint64_t* out) {
@@ -854,7 +840,7 @@ int32_t sp_sumcheck_bind_eval_batched_eq(sp_ctx* c, sp_table* const* A, sp_table
   for (size_t k = 0; k < ninst; k++) { A[k]->len = len / 2; B[k]->len = len / 2; }
   for (size_t k = neq; k < ninst; k++)
     if (C[k]->len == len) table_swap_to_alt(C[k], len / 2);
-  return batched_finish4(c, partials, nblk, ninst, out, sig);
+  return batched_finish(c, partials, nblk, ninst, 4, out, sig);
 }
 // t[i] *= k for i < n, and n becomes the table's length: the hand-over from the factored rounds to the generic ones (queued, not waited for)
 int32_t sp_table_scale_prefix(sp_ctx* c, sp_table* t, size_t n, const uint64_t k[4]) {

@@ -206,12 +206,25 @@ SOURCE_TEXT = [
     "8 * ntabs > HMAP_GEN || 32 * ntabs > HMAP_SIZE - HMAP_IN",
     "32 * ntabs * count > HMAP_SIZE - HMAP_IN",
 ]
+# the shape of a single sum-check round is planned in ONE place (eval_plan, round_plan and plan_sums): sp_sumcheck_eval's block count, the
+# tiny threshold, the bind-and-evaluate block count and the _start placement rule. A second copy of one of them could drift unnoticed
+SOURCE_TEXT_ONCE = SOURCE_TEXT[:4]
+
+
+def _source():
+    return open(os.path.join(ROOT, "spartan_amd", "csrc", "fq_ops.hip")).read()
 
 
 def source_text_missing():
     """the entries of SOURCE_TEXT that fq_ops.hip no longer contains"""
-    src = open(os.path.join(ROOT, "spartan_amd", "csrc", "fq_ops.hip")).read()
+    src = _source()
     return [t for t in SOURCE_TEXT if t not in src]
+
+
+def source_text_counts():
+    """how often fq_ops.hip contains each entry of SOURCE_TEXT_ONCE"""
+    src = _source()
+    return {t: src.count(t) for t in SOURCE_TEXT_ONCE}
 
 
 def _grid_for(work, maxblocks=2048):

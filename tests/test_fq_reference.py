@@ -130,6 +130,9 @@ def test_the_constants_and_the_literal_thresholds_are_still_in_the_source():
     K = F.constants()
     assert set(K) == {"HOST_SUM_BYTES", "HMAP_IN", "HMAP_SIZE", "EQ_SLOTS", "EQ_SMALL_ELL", "EQ_TOPB"} and all(isinstance(v, int) and v > 0 for v in K.values())
     assert F.source_text_missing() == []
+    assert len(F.SOURCE_TEXT) >= 16 and len(F.SOURCE_TEXT_ONCE) == 4 and "half <= 256" in F.SOURCE_TEXT_ONCE[0] and "(Fq*)c->scratch" in F.SOURCE_TEXT_ONCE[3]
+    for text, count in F.source_text_counts().items():      # the plan of a single round stands once: `in` would pass while one of three copies is right
+        assert count == 1, (text, count)
     assert K["EQ_SMALL_ELL"] <= F.EQ_INLINE_MAX and F.EQ_MAX_ELL - F.EQ_MAX_ELL // 2 == F.EQ_SMALL_R      # 32 is the last ell whose upper half fits r[16]
     assert (F.EQ_MAX_ELL + 1) - (F.EQ_MAX_ELL + 1) // 2 > F.EQ_SMALL_R
 
@@ -179,6 +182,11 @@ def test_the_gpu_case_lists_reach_every_dispatch_boundary():
     st = [p for k, p in chain.items() if k[0] == "sc_bind_eval" and k[3]]
     assert any(p["form"] == "tiny" and p["sums"] == "host" for p in st) and any(p["form"] == "streaming" and p["sums"] == "device" for p in st)
     assert not any(p["form"] == "tiny" and p["sums"] == "device" for p in chain.values() if "form" in p)      # 256 blocks at the most
+    # --- _commit: a tiny plan and a streaming plan whose sums the host adds, and a streaming plan that goes through k_reduce_partials
+    cm = [F.plan("sc_bind_eval", n, k) for k, n, *_ in G.COMMIT_CASES]
+    for form, sums in (("tiny", "host"), ("streaming", "host"), ("streaming", "device")):
+        assert any(p["form"] == form and p["sums"] == sums for p in cm), (form, sums)
+    assert any(p["sums"] == "device" and p["nblk"] == 512 and 96 * p["nblk"] > K["HOST_SUM_BYTES"] for p in cm)
     # --- sp_sumcheck_eval: one block up to half = 256, then 256 indices per block
     ev = {k[2]: p for k, p in chain.items() if k[0] == "sc_eval" and k[1] == 0}
     assert ev[2 * F.ONE_BLOCK_HALF]["form"] == "one block" and ev[4 * F.ONE_BLOCK_HALF]["nblk"] == 2 and ev[2]["work"] == 1
@@ -291,7 +299,7 @@ def test_the_gpu_case_lists_keep_the_cases_they_were_given():
     rc = {(c, k, n) for c, k, n, *_ in G.ROUND_CASES}
     assert rc >= {("sc_eval", k, n) for k in (0, 1, 2) for n in (1 << 17, 1 << 18)} | {("sc_bind_eval", k, n) for k in (0, 1, 2) for n in (1 << 18, 1 << 19)}
     assert rc >= {("sc_eval", 0, 1 << 20), ("sc_bind_eval", 0, 1 << 21)}
-    assert {(k, n // 4, rows) for k, n, rows, *_ in G.COMMIT_CASES} >= {(2, 8192, 8), (1, 1, 1)}
+    assert {(k, n // 4, rows) for k, n, rows, *_ in G.COMMIT_CASES} >= {(2, 8192, 8), (1, 1, 1), (0, 1 << 17, 1)}
     assert set(G.DOT_N) >= {1, 255, 256, 257, 245760, 245761, 262144, 262145}
     assert set(G.EVAL_ELLS) >= {1, 2, 3, 4, 5, 12, 13} and "cycle" in G.EVAL_VECTORS
     assert set(G.VECMAT_CASES) >= {(1, 1), (1, 65), (3, 63), (4, 64), (16, 64), (17, 33), (128, 32), (129, 31), (64, 65536)}

@@ -54,7 +54,12 @@ ROUND_CASES = (
     [("sc_eval", 0, 1 << 20, "a", 60, None, "model"),            # grid-stride: a second pass from half = 2^19
      ("sc_bind_eval", 0, 1 << 21, "a", 64, 3, "oracle")])        # ... from quarter = 2^19
 # sp_sumcheck_bind_eval_commit: (kind, length, rows, layout, base, index of r)
-COMMIT_CASES = [(2, 4 * 8192, 8, "a", 68, 3), (1, 4, 1, "a", 72, 2)]
+# (the third: the tables and challenge of the round case at 2^19, kind 0: 512 blocks, their sums added by k_reduce_partials)
+COMMIT_CASES = [(2, 4 * 8192, 8, "a", 68, 3), (1, 4, 1, "a", 72, 2), (0, 1 << 19, 1, "c", 48, 3)]
+# records and round trips per call: (kind, length) at the smallest shape of each plan - tiny with host sums, streaming with host sums,
+# streaming with device sums by the _start rule alone (3 blocks), streaming with device sums (512 blocks)
+RECORD_SHAPES = [(2, 4 * 8192), (1, 4), (1, 1 << 12), (0, 1 << 19)]
+RECORD_CALLS = ["eval", "bind_eval", "start", "commit"]
 DOT_N = [1, 255, 256, 257, 245760, 245761, 262144, 262145]
 DOT_OFF = (3, 5)            # a_off, b_off
 DOT_BASE = 76
@@ -328,7 +333,8 @@ def test_single_rounds_above_the_host_sum_limit(ctx, orc, call, kind, length, la
 def test_round_body_with_commitments(ctx, orc, kind, length, rows, layout, base, ridx):
     """sp_sumcheck_bind_eval_commit: the evaluations and every table as for the fused call, and the `rows` commitments of the side stream
     against the oracle's orc_pt_msm over the same generators and residues (kind 2 at quarter 8192: the largest tiny round, 8 rows: the row
-    sums fill the last KiB of the result area; kind 1 at quarter 1: one row)"""
+    sums fill the last KiB of the result area; kind 1 at quarter 1: one row; kind 0 at quarter 2^17: 512 blocks, whose 49152 bytes of sums
+    are past what the host adds, so the call launches k_reduce_partials without a signal of its own and waits for both streams at once)"""
     from spartan_amd import capi
     pts = gens_bytes(orc, 39)      # 40 points: G[0..39), h = P[39]
     g = capi.Gens(ctx, compressed=pts)
@@ -355,6 +361,74 @@ def test_round_body_with_commitments(ctx, orc, kind, length, rows, layout, base,
         assert bytes(out_pts)[32 * k:32 * k + 32] == bytes(o), ("commitment of row %d, %s" % (k, what))
         COUNTS["commit"] += 1
     _free(tabs); g.free()
+
+
+# ------------------------------------------------------------------ what a single round call leaves behind
+# (call, kind, length) -> (round trips by sp_ctx_trips: of "start" those of _start and of _collect, {profile family: (records, alg_bytes)}
+# of every family the call left a record in).
+# MEASURED, not derived from the code under test: this test printed the table on the library as it stood before the single round calls
+# were given one plan and one launch path, and it was written down here as literals. The calls must go on leaving exactly this behind.
+CALL_RECORDS = {
+    ('eval', 2, 32768): ((1,), {'sumcheck_eval': (1, 4194304.0)}),
+    ('bind_eval', 2, 32768): ((1,), {'sumcheck_bind_eval': (1, 6291456.0)}),
+    ('start', 2, 32768): ((0, 1), {'sumcheck_bind_eval': (1, 6291456.0)}),
+    ('commit', 2, 32768): ((1,), {'msm_windows_fixed': (1, 256.0), 'sumcheck_bind_eval': (1, 6291456.0)}),
+    ('eval', 1, 4): ((1,), {'sumcheck_eval': (1, 384.0)}),
+    ('bind_eval', 1, 4): ((1,), {'sumcheck_bind_eval': (1, 576.0)}),
+    ('start', 1, 4): ((0, 1), {'sumcheck_bind_eval': (1, 576.0), 'fq_reduce': (1, 96.0)}),
+    ('commit', 1, 4): ((1,), {'msm_windows_fixed': (1, 256.0), 'sumcheck_bind_eval': (1, 576.0)}),
+    ('eval', 1, 4096): ((1,), {'sumcheck_eval': (1, 393216.0)}),
+    ('bind_eval', 1, 4096): ((1,), {'sumcheck_bind_eval': (1, 589824.0)}),
+    ('start', 1, 4096): ((0, 1), {'sumcheck_bind_eval': (1, 589824.0), 'fq_reduce': (1, 384.0)}),
+    ('commit', 1, 4096): ((1,), {'msm_windows_fixed': (1, 256.0), 'sumcheck_bind_eval': (1, 589824.0)}),
+    ('eval', 0, 524288): ((1,), {'sumcheck_eval': (1, 33554432.0), 'fq_reduce': (1, 98304.0)}),
+    ('bind_eval', 0, 524288): ((1,), {'sumcheck_bind_eval': (1, 50331648.0), 'fq_reduce': (1, 49152.0)}),
+    ('start', 0, 524288): ((0, 1), {'sumcheck_bind_eval': (1, 50331648.0), 'fq_reduce': (1, 49152.0)}),
+    ('commit', 0, 524288): ((1,), {'msm_windows_fixed': (1, 256.0), 'sumcheck_bind_eval': (1, 50331648.0), 'fq_reduce': (1, 49152.0)}),
+}
+
+
+@_flags_device_errors
+def test_records_and_round_trips_of_every_single_round_call(ctx, orc):
+    """sp_sumcheck_eval, sp_sumcheck_bind_eval, sp_sumcheck_bind_eval_start + _collect and sp_sumcheck_bind_eval_commit (one row of four
+    columns) at each of RECORD_SHAPES: the round trips each call makes and the profile records it leaves (how many per family, and their
+    algorithmic bytes) are those of CALL_RECORDS - one trip per call (at _collect for the split form), one sumcheck record per round, one
+    fq_reduce record exactly where the sums are added on the device, the commitment's records next to them."""
+    from spartan_amd import capi
+    L = capi.lib
+    g = capi.Gens(ctx, compressed=gens_bytes(orc, 39))
+    idx, Sc = (ctypes.c_uint32 * 4)(3, 4, 5, 6), _arr(F.edge_table("a", 4, 157))
+    out, out_pts = (ctypes.c_uint64 * 12)(), (ctypes.c_uint8 * 32)()
+    got = {}
+    ctx.prof_enable(True)
+    try:
+        for kind, length in RECORD_SHAPES:
+            nt, r = F.NTABS[kind], _arr([case_r(length, kind, 3)])
+            for call in RECORD_CALLS:
+                tabs = [_up(ctx, raw=raw) for raw in case_tables_raw(kind, "a", length, 150)]
+                h, k, what = _handles(tabs), ctypes.c_int(kind), "%s kind %d length %d" % (call, kind, length)
+                ctx.prof_reset()
+                trips = [L.sp_ctx_trips(ctx.h)]
+                if call == "eval":
+                    _ok(L.sp_sumcheck_eval(ctx.h, k, h, sz(nt), out), what)
+                elif call == "bind_eval":
+                    _ok(L.sp_sumcheck_bind_eval(ctx.h, k, h, sz(nt), r, out), what)
+                elif call == "start":
+                    _ok(L.sp_sumcheck_bind_eval_start(ctx.h, k, h, sz(nt), r), what)
+                    trips.append(L.sp_ctx_trips(ctx.h))
+                    _ok(L.sp_sumcheck_bind_eval_collect(ctx.h, out), what + " (collect)")
+                else:
+                    _ok(L.sp_sumcheck_bind_eval_commit(ctx.h, k, h, sz(nt), r, out, g.h, idx, sz(4), Sc, sz(1), out_pts), what)
+                trips.append(L.sp_ctx_trips(ctx.h))
+                rec = {n: (v["launches"], v["alg_bytes"]) for n, v in ctx.prof_read().items() if v["launches"] or v["alg_bytes"]}
+                got[(call, kind, length)] = (tuple(b - a for a, b in zip(trips, trips[1:])), rec)
+                _free(tabs)
+    finally:
+        ctx.prof_enable(False)
+    g.free()
+    for key in got:
+        print("    %r: %r," % (key, got[key]))
+    assert got == CALL_RECORDS
 
 
 # ------------------------------------------------------------------ dot and evaluate
