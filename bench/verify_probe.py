@@ -16,7 +16,12 @@ device time of the two variable-base MSM families per launch chain.
 --what nizk_many --batch 1,4,16,64: the same for NIZK.verify_many against K sequential NIZK.verify calls, with the device time of the batched
 evaluation (one `sparse` record a batch: sp_sparse_evaluate_many_begin) beside K times the single call's, and the keep-or-drop rule of DESIGN.md
 section 3 applied at K = 16: the per-proof medians must differ by more than the spread (max - min) of the samples.
-usage: python bench/verify_probe.py [--what nizk|snark|msm|snark_many|nizk_many] [--out profiles/nizk_verify.txt] [--sizes 16,20,22] [--batch 1,4,16,64]"""
+--gens prover|verifier (--what nizk, snark): which generators the timed verifications are handed — the prover's (fixed-base window tables; the
+proof is always made under them) or verifier-only ones (SNARKGens.verifier_only / NIZKGens.verifier_only: the streams as resident point sets).
+--what gens: both kinds in ONE session (profiles/verifier_gens.txt), per size: creation time and bytes held of either kind, and NIZK.verify /
+SNARK.verify of one proof under either, the two interleaved sample by sample, median of 20 after 3 warm pairs. The yardstick is the prover's.
+usage: python bench/verify_probe.py [--what nizk|snark|msm|snark_many|nizk_many|gens] [--gens prover|verifier] [--out profiles/nizk_verify.txt]
+       [--sizes 16,20,22] [--batch 1,4,16,64]"""
 import argparse, ctypes, faulthandler, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,10 +74,88 @@ def comm_parts(cb):
     return h, cb[56:o], cb[o + 8:o + 8 + 32 * n_mem]
 
 
+def gens_kind(args):
+    return "verifier-only (resident point sets; G_hat through sp_msm_points_range)" if args.gens == "verifier" else "the prover's (G_hat through sp_commit_rows)"
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    r = fn()
+    return r, (time.perf_counter() - t0) * 1e3
+
+
+def pair_medians(a, b):
+    """the two calls interleaved sample by sample: WARM warm pairs, then REPS samples each -> ((median, min, max) of a, of b)"""
+    ta, tb = [], []
+    for i in range(WARM + REPS):
+        _, x = timed(a)
+        _, y = timed(b)
+        if i >= WARM:
+            ta.append(x); tb.append(y)
+    ta.sort(); tb.sort()
+    return (ta[len(ta) // 2], ta[0], ta[-1]), (tb[len(tb) // 2], tb[0], tb[-1])
+
+
+def gens_session(args, orc):
+    """both kinds of generators in one session: what each costs to make and to hold, and what a verification costs under each"""
+    label = b"snark_example"
+    lines = ["Verifier-only generators against the prover's, one session (bench/verify_probe.py --what gens; host CPU: %s)" % cpu_model(),
+             "creation: host clock around the constructor, the prover's first (nothing of the size resident), then the verifier-only ones; bytes: HBM held by",
+             "the generator tables; verify: one proof under either kind, the two calls interleaved, %d warm pairs then %d samples each, median (min, max)" % (WARM, REPS),
+             ""]
+    ctx = P.Ctx(0)
+    raw = ctx.raw()
+    GiB = float(1 << 30)
+    row = lambda what, full, light: "  %-14s prover's %s   verifier-only %s" % (what, full, light)
+    stat = lambda m: "%9.3f ms (%.3f, %.3f)" % m
+    for s in [int(x) for x in args.sizes.split(",")]:
+        N, ni, seed = 1 << s, 10, s
+        inst = P.Instance.produce_synthetic_r1cs(ctx, N, N, ni, seed=seed)
+        inst.set_digest(b"digest-%d" % s)
+        # NIZK: one stream
+        ng, ng_ms = timed(lambda: P.NIZKGens(ctx, N, N, ni))
+        nv, nv_ms = timed(lambda: P.NIZKGens.verifier_only(ctx, N, N, ni))
+        proof = P.NIZK.prove(ctx, inst, inst.vars, inst.inputs, ng, LABEL, P.seed_scalar(b"tape", seed))
+        full = lambda: P.NIZK.verify_status(ctx, inst, proof, inst.inputs, ng, LABEL)
+        light = lambda: P.NIZK.verify_status(ctx, inst, proof, inst.inputs, nv, LABEL)
+        if full() != 1 or light() != 1:
+            raise SystemExit("2^%d: a NIZK verification rejected the prover's proof" % s)
+        mf, ml = pair_medians(full, light)
+        t0 = L.sp_ctx_trips(raw); light(); trips = L.sp_ctx_trips(raw) - t0
+        lines += ["synthetic 2^%d, NIZK: proof %d bytes, %d round trips per verification under verifier-only generators" % (s, len(proof), trips),
+                  row("creation", "%9.1f ms" % ng_ms, "%9.1f ms" % nv_ms),
+                  row("bytes held", "%9.3f GiB" % (ng.resident_bytes() / GiB), "%9.3f GiB" % (nv.resident_bytes() / GiB)),
+                  row("NIZK.verify", stat(mf), stat(ml))]
+        print("\n".join(lines[-4:]), flush=True)
+        nv.free(); ng.free()
+        # SNARK: two streams (the prover's tables of the first were freed with the NIZK generators: built again here)
+        sg, sg_ms = timed(lambda: P.SNARKGens(ctx, N, N, ni, N))
+        sv, sv_ms = timed(lambda: P.SNARKGens.verifier_only(ctx, N, N, ni, N))
+        enc = P.SNARK.encode(ctx, inst, sg)
+        proof = P.SNARK.prove(ctx, inst, enc, inst.vars, inst.inputs, sg, label, P.seed_scalar(b"tape", seed))
+        comm = P.Commitment.load(ctx, enc.serialize_commitment())
+        full = lambda: P.SNARK.verify_status(ctx, comm, proof, inst.inputs, sg, label)
+        light = lambda: P.SNARK.verify_status(ctx, comm, proof, inst.inputs, sv, label)
+        if full() != 1 or light() != 1:
+            raise SystemExit("2^%d: a SNARK verification rejected the prover's proof" % s)
+        mf, ml = pair_medians(full, light)
+        t0 = L.sp_ctx_trips(raw); light(); trips = L.sp_ctx_trips(raw) - t0
+        lines += ["synthetic 2^%d, SNARK: proof %d bytes, generator streams of %d + %d points, %d round trips per verification under verifier-only generators" % (
+                      s, len(proof), len(sv.stream(0)) // 32, len(sv.stream(1)) // 32, trips),
+                  row("creation", "%9.1f ms" % sg_ms, "%9.1f ms" % sv_ms),
+                  row("bytes held", "%9.3f GiB" % (sg.resident_bytes() / GiB), "%9.3f GiB" % (sv.resident_bytes() / GiB)),
+                  row("SNARK.verify", stat(mf), stat(ml))]
+        print("\n".join(lines[-4:]), flush=True)
+        comm.free(); enc.free(); sv.free(); sg.free(); inst.free()
+    ctx.close()
+    return lines
+
+
 def snark(args, orc):
     label = b"snark_example"
     lines = ["SNARK::verify on the device against the oracle's verifier on the host (bench/verify_probe.py --what snark; host CPU: %s)" % cpu_model(),
              "(a): median of %d warm calls, host clock; msm_var / msm_points: HIP events around their launch chains, runs of their own; (c): median of 3, 16 threads" % REPS,
+             "generators of the timed verifications: %s" % gens_kind(args),
              ""]
     ctx = P.Ctx(0)
     raw = ctx.raw()
@@ -84,7 +167,8 @@ def snark(args, orc):
         proof = P.SNARK.prove(ctx, inst, enc, inst.vars, inst.inputs, gens, label, P.seed_scalar(b"tape", seed))
         cb = enc.serialize_commitment()
         t0 = time.perf_counter(); comm = P.Commitment.load(ctx, cb); load_ms = (time.perf_counter() - t0) * 1e3
-        verify = lambda: P.SNARK.verify_status(ctx, comm, proof, inst.inputs, gens, label)
+        vgens = P.SNARKGens.verifier_only(ctx, N, N, ni, N) if args.gens == "verifier" else gens
+        verify = lambda: P.SNARK.verify_status(ctx, comm, proof, inst.inputs, vgens, label)
         if verify() != 1:
             raise SystemExit("2^%d: the device verifier rejected the prover's proof" % s)
         med, lo, hi = median_ms(verify, WARM, REPS)
@@ -94,6 +178,8 @@ def snark(args, orc):
             verify()
         mv_ms, mv_n = family(raw, "msm_var")
         mp_ms, mp_n = family(raw, "msm_points")
+        if vgens is not gens:
+            vgens.free()
         L.sp_prof_enable(raw, ctypes.c_int(0))
         h, ops, mem = comm_parts(cb)
         og = vp(orc.orc_snark_gens_new(sz(N), sz(N), sz(ni), sz(N)))
@@ -286,17 +372,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default=None, help="log2 sizes; default 16,20,22 (nizk_many: 16,20)")
-    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm", "snark_many", "nizk_many"])
+    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm", "snark_many", "nizk_many", "gens"])
+    ap.add_argument("--gens", default="prover", choices=["prover", "verifier"], help="--what nizk / snark: the generators the timed verifications take")
     ap.add_argument("--batch", default="1,4,16,64", help="--what snark_many / nizk_many: the batch sizes K")
     args = ap.parse_args()
     if args.sizes is None:
-        args.sizes = "16,20" if args.what == "nizk_many" else "16,20,22"
+        args.sizes = "16,20" if args.what in ("nizk_many", "gens") else "16,20,22"
     orc = load_oracle()
     orc.orc_set_threads(ctypes.c_int(16))
     if args.what != "nizk":
-        return finish(args, {"snark": snark, "msm": msm, "snark_many": snark_many, "nizk_many": nizk_many}[args.what](args, orc))
+        return finish(args, {"snark": snark, "msm": msm, "snark_many": snark_many, "nizk_many": nizk_many, "gens": gens_session}[args.what](args, orc))
     lines = ["NIZK::verify on the device against the oracle's verifier on the host (bench/verify_probe.py; host CPU: %s)" % cpu_model(),
              "(a): median of %d warm calls, host clock; msm_var: HIP events around its launch chain, runs of their own; (c): median of 3, 16 threads" % REPS,
+             "generators of the timed verifications: %s" % gens_kind(args),
              ""]
     ctx = P.Ctx(0)
     raw = ctx.raw()
@@ -307,7 +395,8 @@ def main():
         inst.set_digest(digest)
         gens = P.NIZKGens(ctx, N, N, ni)
         proof = P.NIZK.prove(ctx, inst, inst.vars, inst.inputs, gens, LABEL, P.seed_scalar(b"tape", seed))
-        verify = lambda: P.NIZK.verify_status(ctx, inst, proof, inst.inputs, gens, LABEL)
+        vgens = P.NIZKGens.verifier_only(ctx, N, N, ni) if args.gens == "verifier" else gens
+        verify = lambda: P.NIZK.verify_status(ctx, inst, proof, inst.inputs, vgens, LABEL)
         if verify() != 1:
             raise SystemExit("2^%d: the device verifier rejected the prover's proof" % s)
         med, lo, hi = median_ms(verify, WARM, REPS)
@@ -334,6 +423,8 @@ def main():
         if s == 20:
             lines.append("  reference, published for its own machine (BASELINE.md): NIZK::verify 414.5 ms")
         print("\n".join(lines[-6:]), flush=True)
+        if vgens is not gens:
+            vgens.free()
         gens.free(); inst.free()
     ctx.close()
     text = "\n".join(lines) + "\n"

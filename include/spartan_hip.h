@@ -35,6 +35,7 @@ typedef enum sp_status {
 typedef struct sp_ctx sp_ctx;     /* one GPU, one stream, scratch buffers */
 typedef struct sp_gens sp_gens;   /* device-resident generator list with fixed-base window tables */
 typedef struct sp_table sp_table; /* device-resident vector of F_q elements (a DensePolynomial's Z) */
+typedef struct sp_points sp_points; /* device-resident point set with 4-bit window tables (the verifiers: "resident point sets" below) */
 
 const char* sp_strerror(int32_t status);
 const char* sp_version(void);
@@ -171,6 +172,11 @@ int32_t sp_msm_indexed(sp_ctx* ctx, const sp_gens* g, const uint32_t* idx, size_
 typedef struct sp_host_point { uint64_t w[16]; } sp_host_point; /* an extended point in the library's own form; opaque to callers */
 int32_t sp_host_commit_small(const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, const sp_host_point* const* addend,
                              uint8_t* out /*32*rows*/);
+/* The same commitments over generators that have NO sp_gens: a resident point set the library made from a generator stream
+ * (sp_points_from_uniform below: the verifier-only generators), indexed like the stream. Same host window tables, built lazily from the
+ * encodings the set keeps and dropped when it is freed; same bytes. */
+int32_t sp_host_commit_small_points(const sp_points* pts, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows,
+                                    const sp_host_point* const* addend, uint8_t* out /*32*rows*/);
 /* One row left as a point (not encoded): a partial commitment to be added to a later one through `addend`. */
 int32_t sp_host_commit_point(const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, sp_host_point* out);
 /* Column-sharded commitments (DensePolynomial::commit_inner, src/dense_mlpoly.rs:164-177, when it has fewer rows than
@@ -211,10 +217,15 @@ int32_t sp_host_msm_var(const uint8_t* points, const uint64_t* S, size_t n, uint
  * set keeps the multiples 1..8 of 16^w P for all 64 signed 4-bit windows of every point: n x 64 x 8 extended points, 64 KiB of HBM a point.
  * Like the points of sp_msm_var they are untrusted — the identity, repeats and negatives of each other are legal — and every addition is the
  * complete one. 1 <= n <= 65536. SP_EPOINT (and no handle) when an encoding is invalid: checked here, once, and never again. */
-typedef struct sp_points sp_points;
 int32_t sp_points_upload(sp_ctx* ctx, const uint8_t* compressed /*32*n*/, size_t n, sp_points** out);
+/* The same kind of set straight from a generator stream: n blocks of 64 uniform bytes of the caller's SHAKE256 stream go through the one-way
+ * map of sp_gens_from_uniform (MultiCommitGens::new, commitments.rs:21-30) on the device, the 32 n encodings are written to compressed_out (may
+ * be NULL) — byte for byte those of sp_gens_from_uniform — and the 64-window tables are filled from the mapped points in the same launch: no
+ * decode, and none of the fixed-base window tables of a sp_gens. What a process that only verifies holds of a generator stream. */
+int32_t sp_points_from_uniform(sp_ctx* ctx, const uint8_t* uniform /*64*n*/, size_t n, uint8_t* compressed_out /*32*n*/, sp_points** out);
 void sp_points_free(sp_points* p);
 size_t sp_points_count(const sp_points* p);
+size_t sp_points_table_bytes(const sp_points* p); /* HBM held by the set's tables: 65536 bytes a point */
 /* out = compress( sum_{j<n} S[j] * P[j] ) over the set: the sum of sp_msm_var as a flat sum of table entries — no decode, no table build, no
  * Horner doublings (msm_var.hip). Synchronous, one launch chain, one round trip. SP_EINVAL: n is not the set's size, the set lives on
  * another device than ctx, a null pointer. */
@@ -223,6 +234,13 @@ int32_t sp_msm_points(sp_ctx* ctx, const sp_points* pts, const uint64_t* S /*4*n
  * result is what sp_msm_points gives. SP_EINVAL: K = 0, K > 256, n K > 2^20, n is not the set's size, the set lives on another device than
  * ctx, a null pointer. */
 int32_t sp_msm_points_many(sp_ctx* ctx, const sp_points* pts, const uint64_t* S /*4*n*K, Montgomery*/, size_t n, size_t K, uint8_t* out /*32*K*/);
+/* The same two calls over n CONSECUTIVE points of the set: out[k] = compress( sum_{j<n} S[k][j] * P[off + j] ), off + n <= the set's size (a
+ * verifier multiplies prefixes of a generator stream: G_hat of BulletReductionProof::verify, bullet.rs:213). Same kernels, same launch chain —
+ * sp_msm_points / sp_msm_points_many are the range (0, count) — and everything but the table fetch is sized by n. SP_EINVAL: n = 0,
+ * off + n > the set's size, and the conditions of the calls above. */
+int32_t sp_msm_points_range(sp_ctx* ctx, const sp_points* pts, size_t off, size_t n, const uint64_t* S /*4*n, Montgomery*/, uint8_t out[32]);
+int32_t sp_msm_points_range_many(sp_ctx* ctx, const sp_points* pts, size_t off, size_t n, const uint64_t* S /*4*n*K, Montgomery*/, size_t K,
+                                 uint8_t* out /*32*K*/);
 /* Look-ahead for the zero-knowledge sum-checks. Inside their round loop nothing but DotProductProof::prove draws from the
  * random tape (d_vec, r_delta, r_beta: nizk/mod.rs:330-334), so a caller can take the draws of all rounds up front, in the
  * reference's order, and have a helper thread compute everything that depends on the tape alone while the rounds run:

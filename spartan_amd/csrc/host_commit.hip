@@ -27,7 +27,7 @@ struct StreamTables {
   std::map<uint32_t, std::unique_ptr<Niels[]>> tab;
 };
 std::mutex g_reg_mu;
-std::map<const void*, std::shared_ptr<StreamTables>> g_reg;  // keyed by the generator set's cache entry (gens.hip)
+std::map<const void*, std::shared_ptr<StreamTables>> g_reg;  // keyed by the generator set's cache entry (gens.hip) or by the sp_points (msm_var.hip)
 
 // window table of one point: entry (w, m) = m * 2^(c w) * P for m = 1..2^(c-1), affine Niels form (msm_tidx layout, pt = 0)
 std::unique_ptr<Niels[]> build_table(const uint8_t comp[32]) {
@@ -56,19 +56,33 @@ std::unique_ptr<Niels[]> build_table(const uint8_t comp[32]) {
   return t;
 }
 
-std::shared_ptr<StreamTables> stream_of(const sp_gens* g) {
+// The generators a commitment is taken over: the encodings of a set and the registry entry its lazily built tables live under. A set is an
+// sp_gens (the prover's generators) or an sp_points made by the library (the verifier-only generators: no sp_gens exists there).
+struct GenSet {
+  const void* key = nullptr;
+  const uint8_t* comp = nullptr;
+  size_t n = 0;
+};
+GenSet set_of(const sp_gens* g) {
+  GenSet s;
+  s.key = g->cache_entry;
+  s.comp = gens_compressed_bytes(g, &s.n);
+  return s;
+}
+GenSet set_of(const sp_points* p) { return GenSet{p, p->comp.data(), p->comp.size() / 32}; }
+std::shared_ptr<StreamTables> stream_of(const GenSet& g) {
   std::lock_guard<std::mutex> lk(g_reg_mu);
-  auto& p = g_reg[g->cache_entry];
+  auto& p = g_reg[g.key];
   if (!p) p = std::make_shared<StreamTables>();
   return p;
 }
 // nullptr: index out of range or the point does not decode (cannot happen for a set the device accepted)
-const Niels* table_of(const sp_gens* g, StreamTables& st, uint32_t idx) {
+const Niels* table_of(const GenSet& g, StreamTables& st, uint32_t idx) {
   std::lock_guard<std::mutex> lk(st.mu);
   auto it = st.tab.find(idx);
   if (it != st.tab.end()) return it->second.get();
-  size_t n = 0;
-  const uint8_t* comp = gens_compressed_bytes(g, &n);
+  const size_t n = g.n;
+  const uint8_t* comp = g.comp;
   if (!comp || (size_t)idx >= n) return nullptr;
   auto t = build_table(comp + 32 * (size_t)idx);
   if (!t) return nullptr;
@@ -108,7 +122,7 @@ inline Fq limbs_at(const uint64_t* p, size_t i) {
 }
 static_assert(sizeof(sp_host_point) == sizeof(Pt), "sp_host_point is an extended point");
 
-int32_t row_point(const sp_gens* g, StreamTables& st, const Niels** tabs, const uint32_t* idx, size_t cols, const uint64_t* S, Pt* out) {
+int32_t row_point(const GenSet& g, StreamTables& st, const Niels** tabs, const uint32_t* idx, size_t cols, const uint64_t* S, Pt* out) {
   Pt acc = pt_identity();
   for (size_t k = 0; k < cols; k++) {
     Fq sc = limbs_at(S, k);
@@ -145,9 +159,8 @@ struct sp_zk_ahead {
 
 extern "C" {
 
-int32_t sp_host_commit_small(const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, const sp_host_point* const* addend,
-                             uint8_t* out) {
-  if (!g || !idx || !S || !out || cols == 0 || cols > 16 || rows == 0) return SP_EINVAL;
+static int32_t commit_small(const GenSet& g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, const sp_host_point* const* addend, uint8_t* out) {
+  if (!idx || !S || !out || cols == 0 || cols > 16 || rows == 0) return SP_EINVAL;
   auto st = stream_of(g);
   const Niels* tabs[16] = {nullptr};
   Pt accs[8];  // encoded together, up to four at a time (pt_compress_many: the inverse-square-root chains of a call's rows overlap)
@@ -167,12 +180,21 @@ int32_t sp_host_commit_small(const sp_gens* g, const uint32_t* idx, size_t cols,
   }
   return SP_OK;
 }
+int32_t sp_host_commit_small(const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, const sp_host_point* const* addend,
+                             uint8_t* out) {
+  return g ? commit_small(set_of(g), idx, cols, S, rows, addend, out) : SP_EINVAL;
+}
+int32_t sp_host_commit_small_points(const sp_points* p, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, const sp_host_point* const* addend,
+                                    uint8_t* out) {
+  return p ? commit_small(set_of(p), idx, cols, S, rows, addend, out) : SP_EINVAL;
+}
 int32_t sp_host_commit_point(const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, sp_host_point* out) {
   if (!g || !idx || !S || !out || cols == 0 || cols > 16) return SP_EINVAL;
-  auto st = stream_of(g);
+  const GenSet gs = set_of(g);
+  auto st = stream_of(gs);
   const Niels* tabs[16] = {nullptr};
   Pt acc;
-  SPCHK(row_point(g, *st, tabs, idx, cols, S, &acc));
+  SPCHK(row_point(gs, *st, tabs, idx, cols, S, &acc));
   memcpy(out, &acc, sizeof(Pt));
   return SP_OK;
 }
@@ -231,11 +253,12 @@ int32_t sp_host_zk_ahead_begin(const sp_gens* g, const uint32_t* idx_u, size_t W
   a->be_h.resize(rounds); a->rb_h.resize(rounds); a->bp_hn.resize(rounds);
   try {
     a->th = std::thread([a]() {
-      auto st = stream_of(a->g);
+      const GenSet gs = set_of(a->g);
+      auto st = stream_of(gs);
       const Niels* tabs[16] = {nullptr};
       const size_t nn = a->nn, W = a->W;
       const uint32_t ihn = a->idx_u[nn], ih1 = a->idx_u[nn + 2];
-      const Niels *thn = table_of(a->g, *st, ihn), *th1 = table_of(a->g, *st, ih1);
+      const Niels *thn = table_of(gs, *st, ihn), *th1 = table_of(gs, *st, ih1);
       int32_t rc = (thn && th1) ? SP_OK : SP_EINVAL;
       std::vector<uint64_t> row(4 * W);
       for (size_t j = 0; j < a->rounds && rc == SP_OK; j++) {
@@ -248,7 +271,7 @@ int32_t sp_host_zk_ahead_begin(const sp_gens* g, const uint32_t* idx_u, size_t W
         std::fill(row.begin(), row.end(), 0);  // delta = <d_j, G_n> + r_delta_j * h_n: nothing but the tape enters it
         memcpy(row.data(), a->d.data() + 4 * j * nn, 32 * nn);
         memcpy(row.data() + 4 * nn, a->r_delta.data() + 4 * j, 32);
-        rc = row_point(a->g, *st, tabs, a->idx_u.data(), W, row.data(), &p);
+        rc = row_point(gs, *st, tabs, a->idx_u.data(), W, row.data(), &p);
         if (rc != SP_OK) break;
         pt_compress(p, a->delta.data() + 32 * j);
         p = pt_identity();

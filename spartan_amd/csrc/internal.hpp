@@ -133,6 +133,12 @@ struct sp_gens {
   MsmGeom geom_lds;
   void* cache_entry;
 };
+struct sp_points {  // a resident point set (msm_var.hip); host_commit.hip builds the host window tables of its few-term commitments from comp
+  int dev;
+  size_t n;
+  Pt* table;  // [64 windows][n][8]: table[(w * n + j) * 8 + m - 1] = m 16^w P[j]
+  std::vector<uint8_t> comp;  // the n encodings the set was made from (sp_points_upload) or that it produced (sp_points_from_uniform)
+};
 struct sp_index {  // a usize vector kept as u32 on the device (addresses of the SPARK memory checks)
   sp_ctx* ctx;
   uint32_t* d;

@@ -24,12 +24,6 @@
 constexpr size_t MV_MAX_N = 65536;
 constexpr int MV_BLOCK = 256;
 
-struct sp_points {
-  int dev;
-  size_t n;
-  Pt* table;  // [64 windows][n][8]: table[(w * n + j) * 8 + m - 1] = m 16^w P[j]
-};
-
 namespace {
 constexpr size_t MVM_MAX_K = SP_MSM_MANY_MAX_K;          // multiplications a call (spartan_hip.h): the result area holds MVM_MAX_K x 36 bytes
 constexpr size_t MVM_MAX_TERMS = SP_MSM_MANY_MAX_TERMS;  // n K of a call (1 GiB of per-point tables for sp_msm_var_many)
@@ -132,12 +126,25 @@ __global__ void __launch_bounds__(256) k_msmv_finish(const Pt* __restrict__ part
 // commitments of a ComputationCommitment, fixed for the lifetime of a circuit. The set is decoded once and keeps, per point, the multiples 1..8
 // of 16^w P for all 64 windows (64 KiB a point), so a multiplication is a flat sum of table entries: no decode, no table build, no Horner
 // doublings. K scalar vectors over the one set go through one launch chain, as above; sp_msm_points is the call with K = 1.
-//   k_points_build   one lane per point, at upload: decode (flag word as above), then per window the table of the running base and base <- 16 base;
+//   k_points_build   one lane per point, at upload: decode (flag word as above), then per window the table of the running base and base <- 16 base
+//                    (points_fill); k_points_build_uniform: the same set from the generator stream's uniform bytes (sp_points_from_uniform: the
+//                    verifier-only generators), the hash-to-curve map instead of the decode, the encoding written out;
 //   k_msmp_digits    one lane per (MSM, scalar): out of Montgomery form, 64 signed digits, the [K][64][n] layout of k_msmv_prepare;
-//   k_msmp_windows   k_msmv_windows with the lane's term fetched from window w's slice of the resident table;
+//   k_msmp_windows   k_msmv_windows with the lane's term fetched from window w's slice of the resident table, at the range's offset: a call
+//                    multiplies n consecutive points of the set (sp_msm_points_range; the whole set is the range (0, count));
 //   k_msmp_finish    K workgroups, one per MSM: 256 lanes stride over all 64 x nblocks partial sums (they carry their weight 16^w already),
 //                    6 shuffle levels, the 4 wavefront sums through LDS, the encode on one lane; each writes its 32-byte slot of the host page.
 // Point operations on the critical path: 8 + ceil(64 nblocks / 256) + 8 + the encode.
+// the 64 window tables of point j of a set of n: per window the multiples 1..8 of the running base, then base <- 16 base
+__device__ __forceinline__ void points_fill(Pt base, size_t j, size_t n, Pt* __restrict__ table /*[64][n][8]*/) {
+#pragma unroll 1
+  for (size_t w = 0; w < SP_VAR_WINDOWS; w++) {
+    Pt T[SP_VAR_TABLE];
+    pt_var_table(base, T);
+    for (int m = 0; m < SP_VAR_TABLE; m++) table[(w * n + j) * SP_VAR_TABLE + m] = T[m];
+    base = pt_dbl(T[SP_VAR_TABLE - 1]);  // 16 base = 2 (8 base)
+  }
+}
 __global__ void __launch_bounds__(64) k_points_build(const uint8_t* __restrict__ enc, size_t n, Pt* __restrict__ table /*[64][n][8]*/, int* __restrict__ bad) {
   const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (j >= n) return;
@@ -148,13 +155,21 @@ __global__ void __launch_bounds__(64) k_points_build(const uint8_t* __restrict__
     atomicExch(bad, 1);
     base = pt_identity();
   }
-#pragma unroll 1
-  for (size_t w = 0; w < SP_VAR_WINDOWS; w++) {
-    Pt T[SP_VAR_TABLE];
-    pt_var_table(base, T);
-    for (int m = 0; m < SP_VAR_TABLE; m++) table[(w * n + j) * SP_VAR_TABLE + m] = T[m];
-    base = pt_dbl(T[SP_VAR_TABLE - 1]);  // 16 base = 2 (8 base)
-  }
+  points_fill(base, j, n, table);
+}
+// the same set from 64 uniform bytes a point (MultiCommitGens::new, commitments.rs:21-30: from_uniform_bytes, the map k_points_load of gens.hip
+// runs in mode 1): one lane per point; the encoding goes out first, the tables are filled from the point the map produced
+__global__ void __launch_bounds__(64) k_points_build_uniform(const uint8_t* __restrict__ uniform, size_t n, Pt* __restrict__ table /*[64][n][8]*/,
+                                                             uint8_t* __restrict__ comp_out /*32 n*/) {
+  const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (j >= n) return;
+  uint8_t b[64];
+  for (int k = 0; k < 64; k++) b[k] = uniform[64 * j + k];
+  const Pt base = pt_from_uniform_bytes(b);
+  uint8_t c[32];
+  pt_compress(base, c);
+  for (int k = 0; k < 32; k++) comp_out[32 * j + k] = c[k];
+  points_fill(base, j, n, table);
 }
 
 __global__ void __launch_bounds__(MV_BLOCK) k_msmp_digits(const Fq* __restrict__ S, unsigned n, unsigned total /* K n */, int8_t* __restrict__ digits /*[K][64][n]*/) { SP_FG_PRIO();
@@ -167,8 +182,9 @@ __global__ void __launch_bounds__(MV_BLOCK) k_msmp_digits(const Fq* __restrict__
   for (int w = 0; w < SP_VAR_WINDOWS; w++) dk[(size_t)w * n + j] = d[w];
 }
 
-// grid (nblocks, 64 windows, K): partial[(k * 64 + w) * nblocks + blk] = sum over the block's 256 points of digit_w(S[k][j]) * 16^w P[j]
-__global__ void __launch_bounds__(MV_BLOCK) k_msmp_windows(const Pt* __restrict__ table, const int8_t* __restrict__ digits, size_t n,
+// grid (nblocks, 64 windows, K): partial[(k * 64 + w) * nblocks + blk] = sum over the block's 256 terms of digit_w(S[k][j]) * 16^w P[off + j], j < n:
+// the n points from `off` of a resident table of `stride` points a window (the whole set: off = 0, n = stride)
+__global__ void __launch_bounds__(MV_BLOCK) k_msmp_windows(const Pt* __restrict__ table, size_t stride, size_t off, const int8_t* __restrict__ digits, size_t n,
                                                            Pt* __restrict__ partial) { SP_FG_PRIO();
   __shared__ Pt sm[MV_BLOCK / 64];
   const int t = threadIdx.x;
@@ -177,7 +193,7 @@ __global__ void __launch_bounds__(MV_BLOCK) k_msmp_windows(const Pt* __restrict_
   if (j < n) {
     const int d = digits[(k * SP_VAR_WINDOWS + w) * n + j];
     if (d != 0) {
-      p = table[(w * n + j) * SP_VAR_TABLE + ((d < 0 ? -d : d) - 1)];
+      p = table[(w * stride + off + j) * SP_VAR_TABLE + ((d < 0 ? -d : d) - 1)];
       if (d < 0) p = pt_neg(p);
     }
   }
@@ -269,8 +285,9 @@ int32_t msm_var_run(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t 
   return SP_OK;
 }
 
-// K scalar vectors over the resident set pts (pts->n == n, on c's device): out[k], always written. One round trip.
-int32_t msm_points_run(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, size_t K, uint8_t* out) {
+// K scalar vectors over the points [off, off + n) of the resident set pts (off + n <= pts->n, on c's device): out[k], always written. One round
+// trip. Everything but the table fetch has the length of the range: the digits, the blocks, the partial sums and where the scalars are staged.
+int32_t msm_points_run(sp_ctx* c, const sp_points* pts, size_t off, size_t n, const uint64_t* S, size_t K, uint8_t* out) {
   HIPCHK(hipSetDevice(c->dev));
   const size_t nk = n * K, nblocks = (n + MV_BLOCK - 1) / MV_BLOCK, nparts = (size_t)SP_VAR_WINDOWS * nblocks;
   // device buffer: [partial K x 64 x nblocks Pt][digits K x 64 n]
@@ -287,8 +304,8 @@ int32_t msm_points_run(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_
     const double ops = (double)K * ((double)SP_VAR_WINDOWS * (double)(nblocks * MV_BLOCK) + (double)nparts);
     ProfScope ps(c, PF_MSM_POINTS, 32.0 * (double)nk + 32.0 * (double)K, nullptr, ops);
     hipLaunchKernelGGL(k_msmp_digits, dim3((unsigned)((nk + MV_BLOCK - 1) / MV_BLOCK)), dim3(MV_BLOCK), 0, c->stream, (const Fq*)d_S, (unsigned)n, (unsigned)nk, digits);
-    hipLaunchKernelGGL(k_msmp_windows, dim3((unsigned)nblocks, SP_VAR_WINDOWS, (unsigned)K), dim3(MV_BLOCK), 0, c->stream, (const Pt*)pts->table, (const int8_t*)digits, n,
-                       partial);
+    hipLaunchKernelGGL(k_msmp_windows, dim3((unsigned)nblocks, SP_VAR_WINDOWS, (unsigned)K), dim3(MV_BLOCK), 0, c->stream, (const Pt*)pts->table, pts->n, off, (const int8_t*)digits,
+                       n, partial);
     hipLaunchKernelGGL(k_msmp_finish, dim3((unsigned)K), dim3(256), 0, c->stream, (const Pt*)partial, nparts, res, sig);
   }
   int32_t rc = sig_wait(c, sig);
@@ -311,44 +328,80 @@ extern "C" int32_t sp_msm_var_many(sp_ctx* c, const uint8_t* points, const uint6
   return msm_var_run(c, points, S, n, K, out, status);
 }
 
-extern "C" int32_t sp_points_upload(sp_ctx* c, const uint8_t* compressed, size_t n, sp_points** out) {
-  if (!c || !compressed || !out || n == 0 || n > MV_MAX_N) return SP_EINVAL;
+namespace {
+// a resident set of n points from their encodings (uniform == false: 32 bytes a point, decoded and checked) or from the generator stream's
+// uniform bytes (64 a point: the set produces its encodings). One launch, one lane per point; the set keeps the encodings on the host too.
+int32_t points_make(sp_ctx* c, const uint8_t* in, bool uniform, size_t n, uint8_t* compressed_out, sp_points** out) {
+  if (!c || !in || !out || n == 0 || n > MV_MAX_N) return SP_EINVAL;
   *out = nullptr;
   HIPCHK(hipSetDevice(c->dev));
-  SPCHK(ensure_dstage(c, 32 * n));
-  SPCHK(stage_in(c, 0, compressed, 32 * n));
-  const size_t table_bytes = n * SP_VAR_WINDOWS * SP_VAR_TABLE * sizeof(Pt);
-  uint8_t* buf = nullptr;  // the table, then the flag word
-  HIPCHK(hipMalloc((void**)&buf, table_bytes + 256));
-  int* bad = (int*)(buf + table_bytes);
+  const size_t in_bytes = (uniform ? 64 : 32) * n;
+  SPCHK(ensure_dstage(c, in_bytes));
+  SPCHK(stage_in(c, 0, in, in_bytes));
+  const size_t table_bytes = n * SP_VAR_WINDOWS * SP_VAR_TABLE * sizeof(Pt), comp_bytes = uniform ? (32 * n + 255) & ~(size_t)255 : 0;
+  uint8_t* buf = nullptr;  // the table, then (uniform) the encodings the kernel writes, then the flag word
+  HIPCHK(hipMalloc((void**)&buf, table_bytes + comp_bytes + 256));
+  uint8_t* d_comp = buf + table_bytes;
+  int* bad = (int*)(buf + table_bytes + comp_bytes);
   int flag = 0;
-  int32_t rc = hipMemsetAsync(bad, 0, 4, c->stream) == hipSuccess ? SP_OK : SP_EHIP;
-  if (rc == SP_OK)
-    hipLaunchKernelGGL(k_points_build, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t*)c->dstage, n, (Pt*)buf, bad);
-  if (rc == SP_OK) rc = fetch_out(c, bad, &flag, 4);
+  std::vector<uint8_t> comp;
+  int32_t rc = SP_OK;
+  try {
+    if (uniform) comp.resize(32 * n);
+    else comp.assign(in, in + 32 * n);
+  } catch (const std::bad_alloc&) {
+    rc = SP_ENOMEM;
+  }
+  if (rc == SP_OK && !uniform) rc = hipMemsetAsync(bad, 0, 4, c->stream) == hipSuccess ? SP_OK : SP_EHIP;
+  if (rc == SP_OK) {
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (uniform) hipLaunchKernelGGL(k_points_build_uniform, grid, dim3(64), 0, c->stream, (const uint8_t*)c->dstage, n, (Pt*)buf, d_comp);
+    else hipLaunchKernelGGL(k_points_build, grid, dim3(64), 0, c->stream, (const uint8_t*)c->dstage, n, (Pt*)buf, bad);
+    rc = uniform ? fetch_out(c, d_comp, comp.data(), 32 * n) : fetch_out(c, bad, &flag, 4);
+  }
   if (rc == SP_OK && hipGetLastError() != hipSuccess) rc = SP_EHIP;
   if (rc == SP_OK && flag) rc = SP_EPOINT;
-  sp_points* p = rc == SP_OK ? new (std::nothrow) sp_points{c->dev, n, (Pt*)buf} : nullptr;
+  sp_points* p = rc == SP_OK ? new (std::nothrow) sp_points{c->dev, n, (Pt*)buf, {}} : nullptr;
   if (!p) {
     (void)hipFree(buf);
     return rc == SP_OK ? SP_ENOMEM : rc;
   }
+  if (uniform && compressed_out) memcpy(compressed_out, comp.data(), 32 * n);
+  p->comp = std::move(comp);
   *out = p;
   return SP_OK;
 }
+bool range_ok(const sp_points* pts, size_t off, size_t n) { return n != 0 && off <= pts->n && n <= pts->n - off; }
+}  // namespace
+
+extern "C" int32_t sp_points_upload(sp_ctx* c, const uint8_t* compressed, size_t n, sp_points** out) { return points_make(c, compressed, false, n, nullptr, out); }
+extern "C" int32_t sp_points_from_uniform(sp_ctx* c, const uint8_t* uniform, size_t n, uint8_t* compressed_out, sp_points** out) {
+  return points_make(c, uniform, true, n, compressed_out, out);
+}
 extern "C" void sp_points_free(sp_points* p) {
   if (!p) return;
+  host_commit_forget(p);  // the host window tables of its few-term commitments (host_commit.hip)
   (void)hipSetDevice(p->dev);
   (void)hipFree(p->table);  // waits for whatever still reads the table
   delete p;
 }
 extern "C" size_t sp_points_count(const sp_points* p) { return p ? p->n : 0; }
+extern "C" size_t sp_points_table_bytes(const sp_points* p) { return p ? p->n * SP_VAR_WINDOWS * SP_VAR_TABLE * sizeof(Pt) : 0; }
 
+// one launch path: the whole-set calls are the (0, count) range
+extern "C" int32_t sp_msm_points_range(sp_ctx* c, const sp_points* pts, size_t off, size_t n, const uint64_t* S, uint8_t out[32]) {
+  if (!c || !pts || !S || !out || !range_ok(pts, off, n) || pts->dev != c->dev) return SP_EINVAL;
+  return msm_points_run(c, pts, off, n, S, 1, out);
+}
+extern "C" int32_t sp_msm_points_range_many(sp_ctx* c, const sp_points* pts, size_t off, size_t n, const uint64_t* S, size_t K, uint8_t* out) {
+  if (!c || !pts || !S || !out || !many_args_ok(n, K) || !range_ok(pts, off, n) || pts->dev != c->dev) return SP_EINVAL;
+  return msm_points_run(c, pts, off, n, S, K, out);
+}
 extern "C" int32_t sp_msm_points(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, uint8_t out[32]) {
-  if (!c || !pts || !S || !out || n == 0 || n != pts->n || pts->dev != c->dev) return SP_EINVAL;
-  return msm_points_run(c, pts, S, n, 1, out);
+  if (!pts || n != pts->n) return SP_EINVAL;
+  return sp_msm_points_range(c, pts, 0, n, S, out);
 }
 extern "C" int32_t sp_msm_points_many(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, size_t K, uint8_t* out) {
-  if (!c || !pts || !S || !out || !many_args_ok(n, K) || n != pts->n || pts->dev != c->dev) return SP_EINVAL;
-  return msm_points_run(c, pts, S, n, K, out);
+  if (!pts || n != pts->n) return SP_EINVAL;
+  return sp_msm_points_range_many(c, pts, 0, n, S, K, out);
 }

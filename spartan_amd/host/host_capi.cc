@@ -24,6 +24,15 @@ void fill_times(const ProveTimes& t, double* o) {
   o[0] = t.polycommit; o[1] = t.sc_phase_one; o[2] = t.sc_phase_two; o[3] = t.polyeval; o[4] = t.r1cs_sat; o[5] = t.eval_sparse_polys;
   o[6] = t.commit_nondet_witness; o[7] = t.build_layered_network; o[8] = t.evalproof_layered_network; o[9] = t.total;
 }
+// A generator handle where the PROVER's generators are needed (encode, every prove, the window-table accessors): a verifier-only handle
+// (spz_*_verifier_gens_new) is refused here, before any device call — it has no sp_gens, and a null one must never reach a kernel.
+template <typename G>
+G& prover_gens(void* gens, const char* what) {
+  if (!gens) throw Error(std::string(what) + ": bad arguments");
+  G& g = *(G*)gens;
+  if (g.is_verifier_only()) throw Error(std::string(what) + ": verifier-only generators (they verify; they hold no fixed-base window tables)");
+  return g;
+}
 template <typename F>
 auto guard(F f) -> decltype(f()) {
   try {
@@ -190,10 +199,22 @@ void spz_instance_free(void* i) { delete (Instance*)i; }
 void* spz_snark_gens_new(void* ctx, size_t nc, size_t nv, size_t ni, size_t nnz) {
   return guard([&]() -> void* { return new SNARKGens(*(Ctx*)ctx, nc, nv, ni, nnz); });
 }
+// the verifier's generators (libspartan.hpp: SNARKGens::verifier_only): the same handle type, taken by every spz_snark_verify* entry and by
+// spz_snark_gens_stream; refused by spz_snark_encode, every spz_snark_prove* and the window-table accessors
+void* spz_snark_verifier_gens_new(void* ctx, size_t nc, size_t nv, size_t ni, size_t nnz) {
+  return guard([&]() -> void* { return new SNARKGens(SNARKGens::verifier_only(*(Ctx*)ctx, nc, nv, ni, nnz)); });
+}
+int spz_snark_gens_is_verifier_only(void* g) { return ((SNARKGens*)g)->is_verifier_only() ? 1 : 0; }
+size_t spz_snark_gens_resident_bytes(void* g) { return ((SNARKGens*)g)->resident_bytes(); }  // HBM held by the tables of both streams, either kind
 void spz_snark_gens_free(void* g) { delete (SNARKGens*)g; }
 void* spz_nizk_gens_new(void* ctx, size_t nc, size_t nv, size_t ni) {
   return guard([&]() -> void* { return new NIZKGens(*(Ctx*)ctx, nc, nv, ni); });
 }
+void* spz_nizk_verifier_gens_new(void* ctx, size_t nc, size_t nv, size_t ni) {  // NIZKGens::verifier_only: for spz_nizk_verify*; refused by spz_nizk_prove*
+  return guard([&]() -> void* { return new NIZKGens(NIZKGens::verifier_only(*(Ctx*)ctx, nc, nv, ni)); });
+}
+int spz_nizk_gens_is_verifier_only(void* g) { return ((NIZKGens*)g)->is_verifier_only() ? 1 : 0; }
+size_t spz_nizk_gens_resident_bytes(void* g) { return ((NIZKGens*)g)->resident_bytes(); }
 void spz_nizk_gens_free(void* g) { delete (NIZKGens*)g; }
 // compressed points of the two generator streams (for parity checks against the oracle's MultiCommitGens)
 size_t spz_snark_gens_stream(void* g, int which, uint8_t* out, size_t cap) {
@@ -204,9 +225,20 @@ size_t spz_snark_gens_stream(void* g, int which, uint8_t* out, size_t cap) {
 // library options of the context (include/spartan_hip.h: sp_ctx_set_option); ctx == NULL: the process-wide defaults
 int spz_ctx_set_option(void* ctx, const char* key, const char* value) { return sp_ctx_set_option(ctx ? ((Ctx*)ctx)->h : nullptr, key, value); }
 // window width of the fixed-base tables of a generator stream (0: gens_r1cs_sat, 1: gens_r1cs_eval)
-int spz_snark_gens_window_bits(void* g, int which) { return sp_gens_window_bits(which == 0 ? ((SNARKGens*)g)->stream_sat.g : ((SNARKGens*)g)->stream_eval.g); }
-int spz_snark_gens_windows(void* g, int which) { return sp_gens_windows(which == 0 ? ((SNARKGens*)g)->stream_sat.g : ((SNARKGens*)g)->stream_eval.g); }
-size_t spz_snark_gens_table_bytes(void* g, int which) { return sp_gens_table_bytes(which == 0 ? ((SNARKGens*)g)->stream_sat.g : ((SNARKGens*)g)->stream_eval.g); }
+// (a verifier-only handle has no such tables: -1 / 0 with spz_last_error())
+static const sp_gens* window_tables_of(void* g, int which, const char* what) {
+  try {
+    g_err.clear();
+    SNARKGens& G = prover_gens<SNARKGens>(g, what);
+    return which == 0 ? G.stream_sat.g : G.stream_eval.g;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+int spz_snark_gens_window_bits(void* g, int which) { const sp_gens* t = window_tables_of(g, which, "spz_snark_gens_window_bits"); return t ? sp_gens_window_bits(t) : -1; }
+int spz_snark_gens_windows(void* g, int which) { const sp_gens* t = window_tables_of(g, which, "spz_snark_gens_windows"); return t ? sp_gens_windows(t) : -1; }
+size_t spz_snark_gens_table_bytes(void* g, int which) { const sp_gens* t = window_tables_of(g, which, "spz_snark_gens_table_bytes"); return t ? sp_gens_table_bytes(t) : 0; }
 // bincode of SNARKGens / ComputationCommitment (wire formats)
 size_t spz_snark_gens_bincode(void* g, uint8_t* out, size_t cap) {
   std::vector<uint8_t> b = ((SNARKGens*)g)->serialize();
@@ -216,9 +248,10 @@ size_t spz_snark_gens_bincode(void* g, uint8_t* out, size_t cap) {
 size_t spz_commitment_bincode(void* e, uint8_t* out, size_t cap);
 void* spz_snark_encode(void* ctx, void* inst, void* gens) {
   return guard([&]() -> void* {
+    SNARKGens* pg = &prover_gens<SNARKGens>(gens, "spz_snark_encode");
     EncH* e = new EncH;
     try {
-      SNARK::encode(*(Ctx*)ctx, *(Instance*)inst, *(SNARKGens*)gens, &e->comm, &e->decomm);
+      SNARK::encode(*(Ctx*)ctx, *(Instance*)inst, *pg, &e->comm, &e->decomm);
     } catch (...) {
       delete e;
       throw;
@@ -253,12 +286,13 @@ size_t spz_encode_comm(void* ev, int which, uint8_t* out, size_t cap) {
 void* spz_snark_prove(void* ctx, void* inst, void* gens, void* enc, const uint64_t* vars, size_t nvars, const uint64_t* inputs, size_t ninputs,
                       const char* transcript_label, const uint64_t tape_seed[4], double* times10) {
   return guard([&]() -> void* {
+    SNARKGens& G = prover_gens<SNARKGens>(gens, "spz_snark_prove");
     Transcript t(transcript_label);
     Fq seed;  // tape_seed == NULL: RandomTape::new, seeded from OS entropy (random.rs:13-15)
     if (tape_seed) memcpy(seed.l, tape_seed, 32);
     ProveTimes tm;
     EncH* e = (EncH*)enc;
-    SNARK p = SNARK::prove(*(Ctx*)ctx, *(Instance*)inst, e->comm, e->decomm, (const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs), *(SNARKGens*)gens,
+    SNARK p = SNARK::prove(*(Ctx*)ctx, *(Instance*)inst, e->comm, e->decomm, (const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs), G,
                            t, tape_seed ? &seed : nullptr, &tm);
     fill_times(tm, times10);
     ProofH* h = new ProofH;
@@ -274,6 +308,7 @@ void* spz_snark_prove(void* ctx, void* inst, void* gens, void* enc, const uint64
 void* spz_snark_prove_t(void* ctx, void* inst, void* gens, void* enc, void* assignment, const uint64_t* vars, size_t nvars, const uint64_t* inputs,
                         size_t ninputs, uint8_t transcript_state[203], const uint64_t tape_seed[4], double* times10) {
   return guard([&]() -> void* {
+    SNARKGens& G = prover_gens<SNARKGens>(gens, "spz_snark_prove_t");
     if (!transcript_state || (!assignment && !vars)) throw Error("spz_snark_prove_t: bad arguments");
     Transcript t(Transcript::FromState(), transcript_state);
     Fq seed;
@@ -281,9 +316,9 @@ void* spz_snark_prove_t(void* ctx, void* inst, void* gens, void* enc, void* assi
     ProveTimes tm;
     EncH* e = (EncH*)enc;
     SNARK p = assignment ? SNARK::prove(*(Ctx*)ctx, *(Instance*)inst, e->comm, e->decomm, *(VarsAssignment*)assignment, limbs_vec(inputs, ninputs),
-                                        *(SNARKGens*)gens, t, tape_seed ? &seed : nullptr, &tm)
+                                        G, t, tape_seed ? &seed : nullptr, &tm)
                          : SNARK::prove(*(Ctx*)ctx, *(Instance*)inst, e->comm, e->decomm, (const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs),
-                                        *(SNARKGens*)gens, t, tape_seed ? &seed : nullptr, &tm);
+                                        G, t, tape_seed ? &seed : nullptr, &tm);
     fill_times(tm, times10);
     ProofH* h = new ProofH;
     h->bytes = p.serialize();
@@ -294,14 +329,15 @@ void* spz_snark_prove_t(void* ctx, void* inst, void* gens, void* enc, void* assi
 void* spz_nizk_prove_t(void* ctx, void* inst, void* gens, void* assignment, const uint64_t* vars, size_t nvars, const uint64_t* inputs, size_t ninputs,
                        uint8_t transcript_state[203], const uint64_t tape_seed[4], double* times10) {
   return guard([&]() -> void* {
+    NIZKGens& G = prover_gens<NIZKGens>(gens, "spz_nizk_prove_t");
     if (!transcript_state || (!assignment && !vars)) throw Error("spz_nizk_prove_t: bad arguments");
     Transcript t(Transcript::FromState(), transcript_state);
     Fq seed;
     if (tape_seed) memcpy(seed.l, tape_seed, 32);
     ProveTimes tm;
-    NIZK p = assignment ? NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, *(VarsAssignment*)assignment, limbs_vec(inputs, ninputs), *(NIZKGens*)gens, t,
+    NIZK p = assignment ? NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, *(VarsAssignment*)assignment, limbs_vec(inputs, ninputs), G, t,
                                       tape_seed ? &seed : nullptr, &tm)
-                        : NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, (const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs), *(NIZKGens*)gens, t,
+                        : NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, (const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs), G, t,
                                       tape_seed ? &seed : nullptr, &tm);
     fill_times(tm, times10);
     ProofH* h = new ProofH;
@@ -338,12 +374,13 @@ int spz_instance_is_sat(void* inst, void* assignment, const uint64_t* vars, size
 void* spz_snark_prove_resident(void* ctx, void* inst, void* gens, void* enc, void* assignment, const uint64_t* inputs, size_t ninputs,
                                const char* transcript_label, const uint64_t tape_seed[4], double* times10) {
   return guard([&]() -> void* {
+    SNARKGens& G = prover_gens<SNARKGens>(gens, "spz_snark_prove_resident");
     Transcript t(transcript_label);
     Fq seed;
     if (tape_seed) memcpy(seed.l, tape_seed, 32);
     ProveTimes tm;
     EncH* e = (EncH*)enc;
-    SNARK p = SNARK::prove(*(Ctx*)ctx, *(Instance*)inst, e->comm, e->decomm, *(VarsAssignment*)assignment, limbs_vec(inputs, ninputs), *(SNARKGens*)gens,
+    SNARK p = SNARK::prove(*(Ctx*)ctx, *(Instance*)inst, e->comm, e->decomm, *(VarsAssignment*)assignment, limbs_vec(inputs, ninputs), G,
                            t, tape_seed ? &seed : nullptr, &tm);
     fill_times(tm, times10);
     ProofH* h = new ProofH;
@@ -354,11 +391,12 @@ void* spz_snark_prove_resident(void* ctx, void* inst, void* gens, void* enc, voi
 void* spz_nizk_prove_resident(void* ctx, void* inst, void* gens, void* assignment, const uint64_t* inputs, size_t ninputs, const char* transcript_label,
                               const uint64_t tape_seed[4], double* times10) {
   return guard([&]() -> void* {
+    NIZKGens& G = prover_gens<NIZKGens>(gens, "spz_nizk_prove_resident");
     Transcript t(transcript_label);
     Fq seed;
     if (tape_seed) memcpy(seed.l, tape_seed, 32);
     ProveTimes tm;
-    NIZK p = NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, *(VarsAssignment*)assignment, limbs_vec(inputs, ninputs), *(NIZKGens*)gens, t,
+    NIZK p = NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, *(VarsAssignment*)assignment, limbs_vec(inputs, ninputs), G, t,
                          tape_seed ? &seed : nullptr, &tm);
     fill_times(tm, times10);
     ProofH* h = new ProofH;
@@ -369,11 +407,12 @@ void* spz_nizk_prove_resident(void* ctx, void* inst, void* gens, void* assignmen
 void* spz_nizk_prove(void* ctx, void* inst, void* gens, const uint64_t* vars, size_t nvars, const uint64_t* inputs, size_t ninputs,
                      const char* transcript_label, const uint64_t tape_seed[4], double* times10) {
   return guard([&]() -> void* {
+    NIZKGens& G = prover_gens<NIZKGens>(gens, "spz_nizk_prove");
     Transcript t(transcript_label);
     Fq seed;
     if (tape_seed) memcpy(seed.l, tape_seed, 32);
     ProveTimes tm;
-    NIZK p = NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, (const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs), *(NIZKGens*)gens, t, tape_seed ? &seed : nullptr, &tm);
+    NIZK p = NIZK::prove(*(Ctx*)ctx, *(Instance*)inst, (const sp::Fq*)vars, nvars, limbs_vec(inputs, ninputs), G, t, tape_seed ? &seed : nullptr, &tm);
     fill_times(tm, times10);
     ProofH* h = new ProofH;
     h->bytes = p.serialize();

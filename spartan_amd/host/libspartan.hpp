@@ -99,7 +99,8 @@ struct DevTable {  // DensePolynomial with Z resident in HBM (src/dense_mlpoly.r
 
 // MultiCommitGens (src/commitments.rs:8-13) as a view into a device generator stream
 struct MultiCommitGens {
-  sp_gens* g = nullptr;
+  sp_gens* g = nullptr;           // the stream's fixed-base set; null under verifier-only generators
+  const sp_points* p = nullptr;   // ... whose stream is a resident point set instead (GensStream::pts)
   std::vector<uint32_t> G;  // stream indices of G[0..n)
   uint32_t h = 0;           // stream index of h
   size_t n() const { return G.size(); }
@@ -111,15 +112,22 @@ struct DotProductProofGens {  // src/nizk/mod.rs:408-419
 struct PolyCommitmentGens {  // src/dense_mlpoly.rs:25-36
   DotProductProofGens gens;
 };
-struct GensStream {  // one SHAKE256 stream of points (label), uploaded once with its window tables
+// One SHAKE256 stream of points (label). The prover's form is uploaded once with its fixed-base window tables (g). The VERIFIER-ONLY form
+// (verifier_only, verifier.cc) has the same points, the same `compressed` bytes and the same index structure, but no sp_gens: the stream is a
+// resident point set (pts: 64 KiB a point, made on the device from the same uniform bytes), which is all a verification multiplies over.
+struct GensStream {
   sp_ctx* c = nullptr;
   sp_gens* g = nullptr;
+  std::shared_ptr<sp_points> pts;  // verifier-only form; freed by the deleter verifier.cc gave it
   std::vector<uint8_t> compressed;
   GensStream() {}
   GensStream(sp_ctx* c, const char* label, size_t npoints, int windows = 0 /* table geometry planned by the caller, or 0: the library's per-set policy */);
-  GensStream(GensStream&& o) noexcept : c(o.c), g(o.g), compressed(std::move(o.compressed)) { o.g = nullptr; }
+  GensStream(GensStream&& o) noexcept : c(o.c), g(o.g), pts(std::move(o.pts)), compressed(std::move(o.compressed)) { o.g = nullptr; }
   GensStream& operator=(GensStream&& o) noexcept;
   ~GensStream();
+  static std::vector<uint8_t> uniform_bytes(const char* label, size_t npoints);  // 64 bytes a point: SHAKE256(label || basepoint) (commitments.rs:16-19)
+  static GensStream verifier_only(sp_ctx* c, const char* label, size_t npoints);  // verifier.cc
+  size_t npoints() const { return compressed.size() / 32; }
   MultiCommitGens multi_commit_gens(size_t n) const;        // MultiCommitGens::new(n, label)
   DotProductProofGens dot_product_gens(size_t n) const;     // DotProductProofGens::new(n, label)
   PolyCommitmentGens poly_commitment_gens(size_t num_vars) const;
@@ -131,19 +139,41 @@ struct R1CSGens {                                                      // src/r1
 };
 struct SparseMatPolyCommitmentGens { PolyCommitmentGens gens_ops, gens_mem, gens_derefs; };  // src/sparse_mlpoly.rs:302-337
 
+// Point counts and polynomial sizes of the generator streams of an instance shape (lib.rs:288-307, 476-484): shared by the prover's
+// constructors and the verifier-only ones, which differ only in how a stream is made.
+struct GensLayout {
+  size_t num_vars_padded = 0, sat_points = 0;                                   // gens_r1cs_sat
+  size_t num_vars_ops = 0, num_vars_mem = 0, num_vars_derefs = 0, eval_points = 0;  // gens_r1cs_eval (SNARK only)
+  size_t num_nz_padded = 0;
+  GensLayout(size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_nz_entries);
+};
 struct NIZKGens {  // src/lib.rs:468-486
   GensStream stream_sat;
   R1CSGens gens_r1cs_sat;
   NIZKGens(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs);
+  // the verifier's form (verifier.cc): NIZK::verify / verify_many take it; NIZK::prove refuses it
+  static NIZKGens verifier_only(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs);
+  bool is_verifier_only() const { return stream_sat.g == nullptr; }
+  size_t resident_bytes() const;  // HBM held by the stream's tables, either form
+ private:
+  NIZKGens() {}
+  void index(const GensLayout& l);  // the MultiCommitGens views into the stream
 };
 struct SNARKGens {  // src/lib.rs:276-309
   GensStream stream_sat, stream_eval;
   R1CSGens gens_r1cs_sat;
   SparseMatPolyCommitmentGens gens_r1cs_eval;
   SNARKGens(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_nz_entries);
+  // the verifier's form (verifier.cc): SNARK::verify / verify_many take it; SNARK::encode and SNARK::prove refuse it
+  static SNARKGens verifier_only(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_nz_entries);
+  bool is_verifier_only() const { return stream_sat.g == nullptr; }
+  size_t resident_bytes() const;  // HBM held by the two streams' tables, either form
   // bincode of the serde-derived struct (lib.rs:278-282 -> r1csproof.rs:39-66, r1cs.rs:28-31, sparse_mlpoly.rs:284-289,
   // dense_mlpoly.rs:24-27, nizk/mod.rs:407-412, commitments.rs:7-12): every MultiCommitGens is {n, Vec<G>, h}, points as 32 bytes
   std::vector<uint8_t> serialize() const;
+ private:
+  SNARKGens() {}
+  void index(const GensLayout& l);  // the MultiCommitGens views into the two streams
 };
 
 // ---- instance ----

@@ -122,7 +122,7 @@ DevIndex& DevIndex::operator=(DevIndex&& o) noexcept {
 GensStream::~GensStream() { sp_gens_free(g); }
 GensStream& GensStream::operator=(GensStream&& o) noexcept {
   if (this != &o) {
-    sp_gens_free(g); c = o.c; g = o.g; compressed = std::move(o.compressed); o.g = nullptr;
+    sp_gens_free(g); c = o.c; g = o.g; pts = std::move(o.pts); compressed = std::move(o.compressed); o.g = nullptr;
   }
   return *this;
 }
@@ -142,18 +142,23 @@ GensStream::GensStream(sp_ctx* c_, const char* label, size_t npoints, int window
   // library as option msm.windows for the time of this creation
   struct WindowsFor { sp_ctx* c; bool on; WindowsFor(sp_ctx* c_, int w) : c(c_), on(w != 0) { if (on) SPX(sp_ctx_set_option(c, "msm.windows", std::to_string(w).c_str())); }
                       ~WindowsFor() { if (on) (void)sp_ctx_set_option(c, "msm.windows", "0"); } } windows_for(c_, windows);
+  const std::vector<uint8_t> uniform = uniform_bytes(label, npoints);
+  compressed.resize(32 * npoints);
+  SPX(sp_gens_from_uniform(c, uniform.data(), npoints, compressed.data(), &g));  // from_uniform_bytes on the device (:21-30)
+}
+std::vector<uint8_t> GensStream::uniform_bytes(const char* label, size_t npoints) {
   Shake256 shake;  // commitments.rs:16-19
   shake.absorb(label, strlen(label));
   shake.absorb(kBasepointCompressed, 32);
   std::vector<uint8_t> uniform(64 * npoints);
   shake.squeeze(uniform.data(), uniform.size());
-  compressed.resize(32 * npoints);
-  SPX(sp_gens_from_uniform(c, uniform.data(), npoints, compressed.data(), &g));  // from_uniform_bytes on the device (:21-30)
+  return uniform;
 }
 MultiCommitGens GensStream::multi_commit_gens(size_t n) const {
-  REQUIRE(n + 1 <= sp_gens_len(g));
+  REQUIRE(n + 1 <= (g ? sp_gens_len(g) : npoints()));
   MultiCommitGens m;
   m.g = g;
+  m.p = pts.get();
   m.G.resize(n);
   for (size_t i = 0; i < n; i++) m.G[i] = (uint32_t)i;
   m.h = (uint32_t)n;
@@ -164,6 +169,7 @@ DotProductProofGens GensStream::dot_product_gens(size_t n) const {  // nizk/mod.
   DotProductProofGens d;
   d.n = n;
   d.gens_n.g = d.gens_1.g = g;
+  d.gens_n.p = d.gens_1.p = pts.get();
   d.gens_n.G.assign(all.G.begin(), all.G.begin() + n);
   d.gens_1.G.assign(all.G.begin() + n, all.G.end());
   d.gens_n.h = d.gens_1.h = all.h;
@@ -190,28 +196,40 @@ static size_t sat_stream_points(size_t nvp) {
   size_t n = pow2(lv - lv / 2) + 2;
   return n < 5 ? 5 : n;
 }
-NIZKGens::NIZKGens(Ctx& ctx, size_t, size_t num_vars, size_t num_inputs)
-    : stream_sat(ctx.h, "gens_r1cs_sat", sat_stream_points(pad_vars(num_vars, num_inputs))),
-      gens_r1cs_sat(make_r1cs_gens(stream_sat, pad_vars(num_vars, num_inputs))) {}
-SNARKGens::SNARKGens(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, size_t nnz) {
-  size_t nvp = pad_vars(num_vars, num_inputs);
+GensLayout::GensLayout(size_t num_cons, size_t num_vars, size_t num_inputs, size_t nnz) {
+  num_vars_padded = pad_vars(num_vars, num_inputs);
+  sat_points = sat_stream_points(num_vars_padded);
   // r1cs.rs:33-48 -> sparse_mlpoly.rs:313-337, batch_size = 3
-  size_t nvx = log_2(num_cons), nvy = log_2(2 * nvp);
-  size_t num_vars_ops = log_2(next_pow2(nnz)) + log_2(next_pow2(3 * 5));
-  size_t num_vars_mem = (nvx > nvy ? nvx : nvy) + 1;
-  size_t num_vars_derefs = log_2(next_pow2(nnz)) + log_2(next_pow2(3 * 2));
+  size_t nvx = log_2(num_cons), nvy = log_2(2 * num_vars_padded);
+  num_nz_padded = next_pow2(nnz);
+  num_vars_ops = log_2(num_nz_padded) + log_2(next_pow2(3 * 5));
+  num_vars_mem = (nvx > nvy ? nvx : nvy) + 1;
+  num_vars_derefs = log_2(num_nz_padded) + log_2(next_pow2(3 * 2));
   size_t mx = 0;
   for (size_t v : {num_vars_ops, num_vars_mem, num_vars_derefs}) mx = std::max(mx, pow2(v - v / 2));
+  eval_points = mx + 2;
+}
+void NIZKGens::index(const GensLayout& l) { gens_r1cs_sat = make_r1cs_gens(stream_sat, l.num_vars_padded); }
+void SNARKGens::index(const GensLayout& l) {
+  gens_r1cs_sat = make_r1cs_gens(stream_sat, l.num_vars_padded);
+  gens_r1cs_eval.gens_ops = stream_eval.poly_commitment_gens(l.num_vars_ops);
+  gens_r1cs_eval.gens_mem = stream_eval.poly_commitment_gens(l.num_vars_mem);
+  gens_r1cs_eval.gens_derefs = stream_eval.poly_commitment_gens(l.num_vars_derefs);
+}
+NIZKGens::NIZKGens(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs) {
+  const GensLayout l(num_cons, num_vars, num_inputs, 1);
+  stream_sat = GensStream(ctx.h, "gens_r1cs_sat", l.sat_points);
+  index(l);
+}
+SNARKGens::SNARKGens(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, size_t nnz) {
+  const GensLayout l(num_cons, num_vars, num_inputs, nnz);
   // the window tables of the two streams are sized TOGETHER (round 6): a proof commits num_vars scalars under the first stream and
   // 6 * nnz (`derefs`) under the second; the library picks the pair of window counts with the fewest additions that fits the free HBM
   int w_sat = 0, w_eval = 0;
-  SPX(sp_gens_plan_pair(ctx.h, sat_stream_points(nvp), mx + 2, (double)nvp, 6.0 * (double)next_pow2(nnz), &w_sat, &w_eval));
-  stream_sat = GensStream(ctx.h, "gens_r1cs_sat", sat_stream_points(nvp), w_sat);
-  gens_r1cs_sat = make_r1cs_gens(stream_sat, nvp);
-  stream_eval = GensStream(ctx.h, "gens_r1cs_eval", mx + 2, w_eval);
-  gens_r1cs_eval.gens_ops = stream_eval.poly_commitment_gens(num_vars_ops);
-  gens_r1cs_eval.gens_mem = stream_eval.poly_commitment_gens(num_vars_mem);
-  gens_r1cs_eval.gens_derefs = stream_eval.poly_commitment_gens(num_vars_derefs);
+  SPX(sp_gens_plan_pair(ctx.h, l.sat_points, l.eval_points, (double)l.num_vars_padded, 6.0 * (double)l.num_nz_padded, &w_sat, &w_eval));
+  stream_sat = GensStream(ctx.h, "gens_r1cs_sat", l.sat_points, w_sat);
+  stream_eval = GensStream(ctx.h, "gens_r1cs_eval", l.eval_points, w_eval);
+  index(l);
 }
 
 // ------------------------------------------------------------------ instance (lib.rs:121-228)
@@ -1194,6 +1212,7 @@ bool Instance::is_sat(const VarsAssignment& vars, const FqVec& inputs, SatReport
 }
 NIZK NIZK::prove(Ctx& ctx, const Instance& inst, const Fq* vars, size_t nvars_given, const FqVec& inputs, const NIZKGens& gens, Transcript& t,
                  const Fq* tape_seed, ProveTimes* tm, const sp_table* vars_resident) {  // lib.rs:501-546
+  if (gens.is_verifier_only()) throw Error("NIZK::prove: verifier-only generators have no fixed-base tables");
   double t0 = now_s();
   const std::vector<uint8_t> digest = inst.compute_digest();  // lib.rs:514 absorbs inst.digest (r1cs.rs:154-158); computed once per instance, under its lock
   Fq shared_seed;  // lock-step ranks of a sharded proof must share one tape: rank 0 draws it (shard.cc)

@@ -5,6 +5,7 @@
 // ------------------------------------------------------------------ encode: dense representation (sparse_mlpoly.rs:367-427)
 
 void SNARK::encode(Ctx& ctx, const Instance& inst, const SNARKGens& gens, ComputationCommitment* comm, ComputationDecommitment* decomm) {
+  if (gens.is_verifier_only()) throw Error("SNARK::encode: verifier-only generators have no fixed-base tables");
   sp_ctx* c = ctx.h;
   const std::vector<SparseEntry>* mats[3] = {&inst.A, &inst.B, &inst.C};
   size_t N = 0;
@@ -956,6 +957,7 @@ struct ProofGateHold {  // released by hand when the derefs commitment is in (sp
 SNARK SNARK::prove(Ctx& ctx, const Instance& inst, const ComputationCommitment& comm, const ComputationDecommitment& decomm, const Fq* vars,
                    size_t nvars_given, const FqVec& inputs, const SNARKGens& gens, Transcript& t, const Fq* tape_seed, ProveTimes* tm,
                    const sp_table* vars_resident) {  // lib.rs:339-420
+  if (gens.is_verifier_only()) throw Error("SNARK::prove: verifier-only generators have no fixed-base tables");
   double t0 = now_s();
   sp_ctx* c = ctx.h;
   SNARK P;

@@ -7,14 +7,16 @@
 //   C_LZ = <L, comm.C>              device. Points that arrive with the proof (comm_vars; the SNARK's comm_derefs): sp_msm_var. The two commitments
 //                                   of a ComputationCommitment, fixed for a circuit: sp_msm_points over their resident point sets (sp_points) when
 //                                   the caller holds them, else sp_msm_var as well. polyeval_verify is the one place that chooses
-//   G_hat = <s, G>                  device: sp_commit_rows, one row over the fixed-base tables of gens_n
+//   G_hat = <s, G>                  device: sp_commit_rows, one row over the fixed-base tables of gens_n; under VERIFIER-ONLY generators
+//                                   (GensStream::verifier_only, below: a stream is a resident point set there and no sp_gens exists)          
+//                                   sp_msm_points_range over gens_n's range of the stream's set. dev_commit_row is the one place that chooses
 //   everything with <= 64 terms     calling thread: sp_host_msm_var (proof points, generators by their encodings), sp_host_commit_small when
-//                                   every base is a generator
+//                                   every base is a generator (sp_host_commit_small_points under verifier-only generators: commit_gens)
 //   the SPARK sum-checks            calling thread: field arithmetic over the proof's scalars and the transcript, no groups (SumcheckInstanceProof,
 //                                   ProductCircuitEvalProofBatched, ProductLayerProof, HashLayerProof::verify_helper)
 //   point equalities                comparisons of 32-byte encodings
 // SNARK::verify_many (at the end of the file) runs K of these verifications on K threads; their C_LZ and G_hat calls then meet at a gate
-// (batch_gate.hpp) and go out once per batch: sp_msm_var_many, sp_msm_points_many, sp_commit_rows with K rows. NIZK::verify_many does the same
+// (batch_gate.hpp) and go out once per batch: sp_msm_var_many, sp_msm_points_range_many, sp_commit_rows with K rows. NIZK::verify_many does the same
 // for NIZK::verify, whose third device request, the evaluation of the instance, becomes one job of the batch.
 // Verdicts: 1 accept, 0 reject, -1 malformed bytes. The input is untrusted: where the reference panics on attacker-controlled data
 // (decompress().unwrap() at dense_mlpoly.rs:382, r1csproof.rs:409, nizk/mod.rs:239; the length asserts of sumcheck.rs:38,44,97-98, nizk/mod.rs:381,
@@ -86,9 +88,11 @@ struct GenBytes {
   const uint8_t* at(uint32_t idx) const { return comp.data() + 32 * (size_t)idx; }
 };
 // sum_k s[k] * P[idx[k]] over generators only (Scalar::commit / [Scalar]::commit, commitments.rs:73-92)
-CP commit_gens(const sp_gens* g, const std::vector<uint32_t>& idx, const FqVec& s) {
+// over the host window tables of the stream's set, whichever kind of set the generators hold
+CP commit_gens(const MultiCommitGens& g, const std::vector<uint32_t>& idx, const FqVec& s) {
   CP out;
-  spx(sp_host_commit_small(g, idx.data(), idx.size(), U(s), 1, nullptr, out.data()), "sp_host_commit_small");
+  if (g.g) spx(sp_host_commit_small(g.g, idx.data(), idx.size(), U(s), 1, nullptr, out.data()), "sp_host_commit_small");
+  else spx(sp_host_commit_small_points(g.p, idx.data(), idx.size(), U(s), 1, nullptr, out.data()), "sp_host_commit_small_points");
   return out;
 }
 
@@ -96,7 +100,7 @@ CP commit_gens(const sp_gens* g, const std::vector<uint32_t>& idx, const FqVec& 
 // the call is then POSTED there and answered by the batch's leader, who issues one device call for all the requests of the same shape. Without
 // a gate (every single-proof verifier) the call goes straight to the device. Requests that may share a call have equal keys:
 //   (var, n)                     sp_msm_var over n points of the proof        -> sp_msm_var_many
-//   (points, set, n)             sp_msm_points over a resident set            -> sp_msm_points_many
+//   (points, set, g_off, n)      sp_msm_points[_range] over a resident set    -> sp_msm_points_range_many
 //   (rows, gens, g_off, h, n)    sp_commit_rows of one unblinded row          -> sp_commit_rows with rows = the group's size
 //   (eval_start, instance)       R1CSInstance::evaluate at (rx, ry), started  -> sp_sparse_evaluate_many_begin, one job for the group
 //   (eval_collect, instance)     ... its three values                         -> sp_job_wait, once (NIZK::verify_many only)
@@ -129,11 +133,19 @@ void dev_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t n, 
 }
 void dev_msm_points(sp_ctx* c, const sp_points* set, const uint64_t* S, size_t n, uint8_t out[32]) {
   if (!tl_seat.gate) spx(sp_msm_points(c, set, S, n, out), "sp_msm_points");  // SP_EINVAL for another size cannot happen: the caller required it
-  else dev_answer(DevKey{DevKey::POINTS, set, 0, 0, n}, DevReq{nullptr, S}, out, "sp_msm_points_many");
+  else dev_answer(DevKey{DevKey::POINTS, set, 0, 0, n}, DevReq{nullptr, S}, out, "sp_msm_points_range_many");
 }
-void dev_commit_row(sp_ctx* c, const sp_gens* g, size_t g_off, size_t h, const uint64_t* S, size_t n, uint8_t out[32]) {
-  if (!tl_seat.gate) spx(sp_commit_rows(c, g, g_off, h, S, 1, n, nullptr, out), "sp_commit_rows");
-  else dev_answer(DevKey{DevKey::ROWS, g, g_off, h, n}, DevReq{nullptr, S}, out, "sp_commit_rows");
+// <S, gn.G>, one unblinded row over the n generators of gn (consecutive in their stream): the fixed-base tables of the prover's generators, or
+// that range of the resident set of verifier-only ones
+void dev_commit_row(sp_ctx* c, const MultiCommitGens& gn, const uint64_t* S, size_t n, uint8_t out[32]) {
+  const size_t g_off = gn.G[0];
+  if (gn.g) {
+    if (!tl_seat.gate) spx(sp_commit_rows(c, gn.g, g_off, gn.h, S, 1, n, nullptr, out), "sp_commit_rows");
+    else dev_answer(DevKey{DevKey::ROWS, gn.g, g_off, gn.h, n}, DevReq{nullptr, S}, out, "sp_commit_rows");
+  } else {
+    if (!tl_seat.gate) spx(sp_msm_points_range(c, gn.p, g_off, n, S, out), "sp_msm_points_range");
+    else dev_answer(DevKey{DevKey::POINTS, gn.p, g_off, 0, n}, DevReq{nullptr, S}, out, "sp_msm_points_range_many");
+  }
 }
 
 // ---- nizk/mod.rs ----
@@ -142,7 +154,7 @@ void knowledge_verify(const KnowledgeProof& p, const MultiCommitGens& g, Transcr
   t.append_point("C", C.data());
   t.append_point("alpha", p.alpha.data());
   Fq c = t.challenge_scalar("c");
-  CP lhs = commit_gens(g.g, {g.G[0], g.h}, {p.z1, p.z2});
+  CP lhs = commit_gens(g, {g.G[0], g.h}, {p.z1, p.z2});
   CP rhs = Terms().add(C, c).add(p.alpha, fq_one()).eval();
   require(lhs == rhs);
 }
@@ -153,7 +165,7 @@ void equality_verify(const EqualityProof& p, const MultiCommitGens& g, Transcrip
   t.append_point("alpha", p.alpha.data());
   Fq c = t.challenge_scalar("c");
   CP rhs = Terms().add(C1, c).add(C2, -c).add(p.alpha, fq_one()).eval();  // c (C1 - C2) + alpha
-  CP lhs = commit_gens(g.g, {g.h}, {p.z});
+  CP lhs = commit_gens(g, {g.h}, {p.z});
   require(lhs == rhs);
 }
 void product_verify(const ProductProof& p, const MultiCommitGens& g, const GenBytes& gb, Transcript& t, const CP& X, const CP& Y, const CP& Z) {  // :245-289
@@ -166,8 +178,8 @@ void product_verify(const ProductProof& p, const MultiCommitGens& g, const GenBy
   t.append_point("delta", p.delta.data());
   Fq c = t.challenge_scalar("c");
   // check_equality (:231-243): P + c X == commit(z1, z2)
-  require(Terms().add(p.alpha, fq_one()).add(X, c).eval() == commit_gens(g.g, {g.G[0], g.h}, {p.z[0], p.z[1]}));
-  require(Terms().add(p.beta, fq_one()).add(Y, c).eval() == commit_gens(g.g, {g.G[0], g.h}, {p.z[2], p.z[3]}));
+  require(Terms().add(p.alpha, fq_one()).add(X, c).eval() == commit_gens(g, {g.G[0], g.h}, {p.z[0], p.z[1]}));
+  require(Terms().add(p.beta, fq_one()).add(Y, c).eval() == commit_gens(g, {g.G[0], g.h}, {p.z[2], p.z[3]}));
   // the third under {G: X, h}: delta + c Z == z3 X + z5 h
   require(Terms().add(p.delta, fq_one()).add(Z, c).eval() == Terms().add(X, p.z[2]).add(gb.at(g.h), p.z[4]).eval());
 }
@@ -185,8 +197,8 @@ void dotproduct_verify(const DotProductProof& p, const MultiCommitGens& g1, cons
   idx.push_back(gn.h);
   FqVec zs(p.z);
   zs.push_back(p.z_delta);
-  bool ok = Terms().add(Cx, c).add(p.delta, fq_one()).eval() == commit_gens(gn.g, idx, zs);
-  ok &= Terms().add(Cy, c).add(p.beta, fq_one()).eval() == commit_gens(g1.g, {g1.G[0], g1.h}, {dot(p.z, a), p.z_beta});
+  bool ok = Terms().add(Cx, c).add(p.delta, fq_one()).eval() == commit_gens(gn, idx, zs);
+  ok &= Terms().add(Cy, c).add(p.beta, fq_one()).eval() == commit_gens(g1, {g1.G[0], g1.h}, {dot(p.z, a), p.z_beta});
   require(ok);
 }
 // BulletReductionProof::verify with verification_scalars (bullet.rs:137-225). Gamma = Cx + r Cy is folded into the Gamma_hat combination.
@@ -214,8 +226,8 @@ void bullet_verify(sp_ctx* c, const BulletReductionProof& p, size_t n, const FqV
     while (((size_t)2 << lg_i) <= i) lg_i++;
     s[i] = s[i - ((size_t)1 << lg_i)] * u_sq[(lg_n - 1) - lg_i];
   }
-  // G_hat = <s, G> (:213): fixed bases, the device's window tables
-  dev_commit_row(c, gn.g, gn.G[0], gn.h, U(s), n, g_hat->data());
+  // G_hat = <s, G> (:213): fixed bases, the device's window tables (verifier-only generators: that range of the stream's resident set)
+  dev_commit_row(c, gn, U(s), n, g_hat->data());
   *a_hat = dot(a, s);                                          // :214
   Terms g;                                                     // :216-222
   for (size_t i = 0; i < lg_n; i++) g.add(p.L_vec[i], u_sq[i]);
@@ -466,7 +478,7 @@ Fq combine_n_to_one(FqVec evals, Transcript& t, const char* chal_label, const Fq
 void polyeval_verify_plain(sp_ctx* c, const PolyEvalProof& p, const PolyCommitmentGens& gens, const GenBytes& gb, Transcript& t, const FqVec& r, const Fq& Zr,
                            const PolyCommitment& comm, const sp_points* resident = nullptr) {
   const MultiCommitGens& g1 = gens.gens.gens_1;
-  CP C_Zr = commit_gens(g1.g, {g1.G[0]}, {Zr});
+  CP C_Zr = commit_gens(g1, {g1.G[0]}, {Zr});
   polyeval_verify(c, p, gens, gb, t, r.data(), r.size(), C_Zr, comm, resident);
 }
 // HashLayerProof::verify_helper (sparse_mlpoly.rs:837-886)
@@ -649,6 +661,39 @@ void r_evalproof(Rd& r, SparseMatPolyEvalProof& p) {  // sparse_mlpoly.rs:1418-1
 }
 }  // namespace
 
+// ---- verifier-only generators: the streams of SNARKGens / NIZKGens as resident point sets. A verification multiplies one range of a stream per
+// opening (G_hat) and combines a handful of generators on the host; neither needs the prover's fixed-base window tables, which take most of
+// the device and seconds to build. The set comes out of the same uniform bytes through the same one-way map, on the device, with its encodings.
+GensStream GensStream::verifier_only(sp_ctx* c, const char* label, size_t npoints) {
+  GensStream s;
+  s.c = c;
+  const std::vector<uint8_t> uniform = uniform_bytes(label, npoints);
+  s.compressed.resize(32 * npoints);
+  sp_points* p = nullptr;
+  int32_t rc = sp_points_from_uniform(c, uniform.data(), npoints, s.compressed.data(), &p);
+  if (rc != SP_OK) throw dev_error("sp_points_from_uniform", rc);
+  s.pts = std::shared_ptr<sp_points>(p, [](sp_points* q) { sp_points_free(q); });
+  return s;
+}
+NIZKGens NIZKGens::verifier_only(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs) {
+  const GensLayout l(num_cons, num_vars, num_inputs, 1);
+  NIZKGens g;
+  g.stream_sat = GensStream::verifier_only(ctx.h, "gens_r1cs_sat", l.sat_points);
+  g.index(l);
+  return g;
+}
+SNARKGens SNARKGens::verifier_only(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_nz_entries) {
+  const GensLayout l(num_cons, num_vars, num_inputs, num_nz_entries);
+  SNARKGens g;
+  g.stream_sat = GensStream::verifier_only(ctx.h, "gens_r1cs_sat", l.sat_points);
+  g.stream_eval = GensStream::verifier_only(ctx.h, "gens_r1cs_eval", l.eval_points);
+  g.index(l);
+  return g;
+}
+static size_t stream_resident_bytes(const GensStream& s) { return s.g ? sp_gens_table_bytes(s.g) : sp_points_table_bytes(s.pts.get()); }
+size_t NIZKGens::resident_bytes() const { return stream_resident_bytes(stream_sat); }
+size_t SNARKGens::resident_bytes() const { return stream_resident_bytes(stream_sat) + stream_resident_bytes(stream_eval); }
+
 bool SNARK::deserialize(const uint8_t* bytes, size_t len, SNARK* out) {
   if (!bytes || !out) return false;
   Rd r{bytes, len};
@@ -808,8 +853,8 @@ void serve_group(sp_ctx* c, const DevKey& key, const std::vector<const DevReq*>&
       if (rc != SP_OK) throw dev_error("sp_msm_var_many", rc);
       for (size_t i = 0; i < k; i++) answers[k0 + i].rc = status[i];  // SP_EPOINT: a Reject for that proof alone
     } else if (key.kind == DevKey::POINTS) {
-      int32_t rc = sp_msm_points_many(c, (const sp_points*)key.obj, S.data(), n, k, out.data());
-      if (rc != SP_OK) throw dev_error("sp_msm_points_many", rc);
+      int32_t rc = sp_msm_points_range_many(c, (const sp_points*)key.obj, key.g_off, n, S.data(), k, out.data());  // a whole set: the range (0, count)
+      if (rc != SP_OK) throw dev_error("sp_msm_points_range_many", rc);
     } else {
       int32_t rc = sp_commit_rows(c, (const sp_gens*)key.obj, key.g_off, key.h, S.data(), k, n, nullptr, out.data());
       if (rc != SP_OK) throw dev_error("sp_commit_rows", rc);

@@ -11,9 +11,10 @@ ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
 H = ctypes.CDLL(HOST_PATH)
 for f in ("spz_ctx_new", "spz_instance_new", "spz_instance_synthetic", "spz_snark_gens_new", "spz_nizk_gens_new", "spz_snark_encode",
           "spz_snark_prove", "spz_nizk_prove", "spz_ctx_raw", "spz_vars_assignment_new", "spz_snark_prove_resident", "spz_nizk_prove_resident",
-          "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load"):
+          "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load", "spz_snark_verifier_gens_new", "spz_nizk_verifier_gens_new"):
     getattr(H, f).restype = vp
-for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode"):
+for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode",
+          "spz_snark_gens_resident_bytes", "spz_nizk_gens_resident_bytes", "spz_snark_gens_table_bytes"):
     getattr(H, f).restype = sz
 H.spz_last_error.restype = ctypes.c_char_p
 for f in ("spz_nizk_parse_probe", "spz_snark_reserialize", "spz_commitment_reserialize"):
@@ -150,6 +151,23 @@ class SNARKGens:
     def __init__(self, ctx, num_cons, num_vars, num_inputs, num_nz_entries):
         self.h = _chk(H.spz_snark_gens_new(ctx.h, sz(num_cons), sz(num_vars), sz(num_inputs), sz(num_nz_entries)), "SNARKGens::new")
 
+    @classmethod
+    def verifier_only(cls, ctx, num_cons, num_vars, num_inputs, num_nz_entries):
+        """the generators of a process that only verifies: the same streams (stream(which) gives the same bytes) held as resident point
+        sets of 64 KiB a point, without the prover's fixed-base window tables. SNARK.verify / verify_status / verify_t / verify_many take
+        them; SNARK.encode, SNARK.prove* and the window-table accessors raise SpartanHipError."""
+        g = cls.__new__(cls)
+        g.h = _chk(H.spz_snark_verifier_gens_new(ctx.h, sz(num_cons), sz(num_vars), sz(num_inputs), sz(num_nz_entries)), "SNARKGens::verifier_only")
+        return g
+
+    @property
+    def is_verifier_only(self):
+        return bool(H.spz_snark_gens_is_verifier_only(self.h))
+
+    def resident_bytes(self):
+        """HBM held by the tables of the two generator streams (verifier-only: 65536 bytes a point)"""
+        return int(H.spz_snark_gens_resident_bytes(self.h))
+
     def stream(self, which):
         n = H.spz_snark_gens_stream(self.h, ctypes.c_int(which), None, sz(0))
         b = (ctypes.c_uint8 * n)()
@@ -158,16 +176,20 @@ class SNARKGens:
 
     def window_bits(self, which):
         """signed window width of the fixed-base tables of generator stream `which` (0: gens_r1cs_sat, 1: gens_r1cs_eval)"""
-        return int(H.spz_snark_gens_window_bits(self.h, ctypes.c_int(which)))
+        return self._tables(H.spz_snark_gens_window_bits(self.h, ctypes.c_int(which)), "window_bits")
+
+    def _tables(self, value, what):
+        if int(value) <= 0 and self.is_verifier_only:
+            raise SpartanHipError(f"SNARKGens::{what} failed: {H.spz_last_error().decode()}")
+        return int(value)
 
     def windows(self, which):
         """windows per scalar (= mixed additions per committed scalar) of the tables of generator stream `which`"""
-        return int(H.spz_snark_gens_windows(self.h, ctypes.c_int(which)))
+        return self._tables(H.spz_snark_gens_windows(self.h, ctypes.c_int(which)), "windows")
 
     def table_bytes(self, which):
         """HBM held by the window tables of generator stream `which`"""
-        H.spz_snark_gens_table_bytes.restype = sz
-        return int(H.spz_snark_gens_table_bytes(self.h, ctypes.c_int(which)))
+        return self._tables(H.spz_snark_gens_table_bytes(self.h, ctypes.c_int(which)), "table_bytes")
 
     def serialize(self):
         n = H.spz_snark_gens_bincode(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
@@ -182,6 +204,22 @@ class SNARKGens:
 class NIZKGens:
     def __init__(self, ctx, num_cons, num_vars, num_inputs):
         self.h = _chk(H.spz_nizk_gens_new(ctx.h, sz(num_cons), sz(num_vars), sz(num_inputs)), "NIZKGens::new")
+
+    @classmethod
+    def verifier_only(cls, ctx, num_cons, num_vars, num_inputs):
+        """the generators of a process that only verifies (see SNARKGens.verifier_only): for NIZK.verify / verify_status / verify_t /
+        verify_many; NIZK.prove* raise SpartanHipError"""
+        g = cls.__new__(cls)
+        g.h = _chk(H.spz_nizk_verifier_gens_new(ctx.h, sz(num_cons), sz(num_vars), sz(num_inputs)), "NIZKGens::verifier_only")
+        return g
+
+    @property
+    def is_verifier_only(self):
+        return bool(H.spz_nizk_gens_is_verifier_only(self.h))
+
+    def resident_bytes(self):
+        """HBM held by the tables of the generator stream (verifier-only: 65536 bytes a point)"""
+        return int(H.spz_nizk_gens_resident_bytes(self.h))
 
     def free(self):
         if self.h:
