@@ -20,8 +20,13 @@ section 3 applied at K = 16: the per-proof medians must differ by more than the 
 proof is always made under them) or verifier-only ones (SNARKGens.verifier_only / NIZKGens.verifier_only: the streams as resident point sets).
 --what gens: both kinds in ONE session (profiles/verifier_gens.txt), per size: creation time and bytes held of either kind, and NIZK.verify /
 SNARK.verify of one proof under either, the two interleaved sample by sample, median of 20 after 3 warm pairs. The yardstick is the prover's.
-usage: python bench/verify_probe.py [--what nizk|snark|msm|snark_many|nizk_many|gens] [--gens prover|verifier] [--out profiles/nizk_verify.txt]
-       [--sizes 16,20,22] [--batch 1,4,16,64]"""
+--what encode: obtaining the circuit's commitment, both ways in ONE session (profiles/verifier_encode.txt), per size: SNARKGens.verifier_only +
+Commitment.encode (sp_commit_rows_points over the resident sets) against SNARKGens(...) + SNARK.encode (window tables): time of each step on
+the host clock, peak HBM above the session's baseline while it runs (free device memory polled from a second thread) and HBM held afterwards,
+then the encode call alone, warm (median of 3), and the HIP-event time of its commit_rows_points launch chains. --kernel-stats FILE adds the
+kernels' own times from the kernel statistics (csv) of a SEPARATE profiler run of `--what encode --kernel-run` (the verifier's path alone, once).
+usage: python bench/verify_probe.py [--what nizk|snark|msm|snark_many|nizk_many|gens|encode] [--gens prover|verifier] [--out profiles/nizk_verify.txt]
+       [--sizes 16,20,22] [--batch 1,4,16,64] [--kernel-run] [--kernel-stats FILE]"""
 import argparse, ctypes, faulthandler, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -148,6 +153,114 @@ def gens_session(args, orc):
         print("\n".join(lines[-4:]), flush=True)
         comm.free(); enc.free(); sv.free(); sg.free(); inst.free()
     ctx.close()
+    return lines
+
+
+class PeakHBM:
+    """device memory in use above `base` while the block runs: free memory polled every millisecond from a second thread"""
+    def __init__(self, base):
+        import threading, torch
+        self.base, self.low, self.stop, self.torch = base, base, False, torch
+        self.th = threading.Thread(target=self.poll, daemon=True)
+
+    def poll(self):
+        while not self.stop:
+            self.low = min(self.low, self.torch.cuda.mem_get_info(0)[0])
+            time.sleep(0.001)
+
+    def __enter__(self):
+        self.th.start()
+        return self
+
+    def __exit__(self, *exc):
+        self.stop = True
+        self.th.join()
+        self.low = min(self.low, self.torch.cuda.mem_get_info(0)[0])
+        self.peak = self.base - self.low
+        self.held = self.base - self.torch.cuda.mem_get_info(0)[0]
+
+
+def kernel_stats_lines(path):
+    """the k_rowp_* rows of a profiler's kernel statistics csv (columns Name, Calls, TotalDurationNs, AverageNs, MinNs, MaxNs)"""
+    import csv
+    out = []
+    for row in csv.DictReader(open(path)):
+        name = row.get("Name") or row.get("KernelName") or ""
+        if "k_rowp_" in name:
+            short = "k_rowp_sum" if "k_rowp_sum" in name else "k_rowp_finish"
+            out.append("  %-14s calls %s, total %.3f ms, average %.3f ms (min %.3f, max %.3f)" % (
+                short, row["Calls"], float(row["TotalDurationNs"]) / 1e6, float(row["AverageNs"]) / 1e6, float(row["MinNs"]) / 1e6, float(row["MaxNs"]) / 1e6))
+    return out
+
+
+def encode_session(args, orc):
+    """the commitment of a circuit, obtained by a verifier (verifier-only generators, Commitment.encode) and by a prover (SNARKGens, SNARK.encode)"""
+    import torch
+    sizes = [int(x) for x in args.sizes.split(",")]
+    ctx = P.Ctx(0)
+    raw = ctx.raw()
+    if args.kernel_run:       # under a profiler: the verifier's path alone, once a size (two launch chains: comb_ops, comb_mem)
+        for s in sizes:
+            N, ni = 1 << s, 10
+            inst = P.Instance.produce_synthetic_r1cs(ctx, N, N, ni, seed=s)
+            sv = P.SNARKGens.verifier_only(ctx, N, N, ni, N)
+            h = P.Commitment.encode(ctx, inst, sv)
+            print("2^%d: commitment of %d bytes" % (s, len(h.serialize())), flush=True)
+            h.free(); sv.free(); inst.free()
+        ctx.close()
+        return ["kernel run done"]
+    lines = ["The commitment of a circuit without the prover's tables (bench/verify_probe.py --what encode; host CPU: %s)" % cpu_model(),
+             "one session, warm (both paths run once at 2^10 first); per step: host clock around the call; peak: HBM in use above the baseline of the size while",
+             "the two steps run (free memory polled each ms); held: above the baseline once both have returned; `again`: the encode call alone, %d more times, median (min, max)" % 3,
+             ""]
+    GiB = float(1 << 30)
+
+    def warm():
+        inst = P.Instance.produce_synthetic_r1cs(ctx, 1024, 1024, 10, seed=1)
+        sv = P.SNARKGens.verifier_only(ctx, 1024, 1024, 10, 1024); sg = P.SNARKGens(ctx, 1024, 1024, 10, 1024)
+        h = P.Commitment.encode(ctx, inst, sv); e = P.SNARK.encode(ctx, inst, sg)
+        assert h.serialize() == e.serialize_commitment()
+        e.free(); h.free(); sg.free(); sv.free(); inst.free()
+    warm()
+    torch.cuda.synchronize()
+    stat = lambda m: "%9.3f ms (%.3f, %.3f)" % m
+    for s in sizes:
+        N, ni = 1 << s, 10
+        inst = P.Instance.produce_synthetic_r1cs(ctx, N, N, ni, seed=s)
+        L.sp_ctx_sync(raw)
+        base = torch.cuda.mem_get_info(0)[0]
+        with PeakHBM(base) as v:
+            sv, sv_ms = timed(lambda: P.SNARKGens.verifier_only(ctx, N, N, ni, N))
+            h, h_ms = timed(lambda: P.Commitment.encode(ctx, inst, sv))
+        cb = h.serialize()
+        again_v = median_ms(lambda: P.Commitment.encode(ctx, inst, sv).free(), 0, 3)
+        L.sp_prof_enable(raw, ctypes.c_int(1)); L.sp_prof_reset(raw)
+        P.Commitment.encode(ctx, inst, sv).free()
+        cp_ms, cp_n = family(raw, "commit_rows_points")
+        L.sp_prof_enable(raw, ctypes.c_int(0))
+        _, ops, mem = comm_parts(cb)
+        h.free(); sv.free()
+        L.sp_ctx_sync(raw)
+        with PeakHBM(base) as p:
+            sg, sg_ms = timed(lambda: P.SNARKGens(ctx, N, N, ni, N))
+            enc, enc_ms = timed(lambda: P.SNARK.encode(ctx, inst, sg))
+        if enc.serialize_commitment() != cb:
+            raise SystemExit("2^%d: the two commitments differ" % s)
+        enc.free()
+        again_p = median_ms(lambda: P.SNARK.encode(ctx, inst, sg).free(), 0, 3)
+        lines += ["synthetic 2^%d: commitment of %d + %d shares, %d bytes, the same either way" % (s, len(ops) // 32, len(mem) // 32, len(cb)),
+                  "  verifier: SNARKGens.verifier_only %9.1f ms + Commitment.encode %9.1f ms = %9.1f ms; peak %8.3f GiB, held %8.3f GiB" % (
+                      sv_ms, h_ms, sv_ms + h_ms, v.peak / GiB, v.held / GiB),
+                  "  prover:   SNARKGens               %9.1f ms + SNARK.encode      %9.1f ms = %9.1f ms; peak %8.3f GiB, held %8.3f GiB (the decommitment included)" % (
+                      sg_ms, enc_ms, sg_ms + enc_ms, p.peak / GiB, p.held / GiB),
+                  "  again:    Commitment.encode %s; SNARK.encode %s" % (stat(again_v), stat(again_p)),
+                  "  commit_rows_points launch chains (HIP events, a run of its own): %d, %.3f ms in all" % (cp_n, cp_ms)]
+        print("\n".join(lines[-5:]), flush=True)
+        sg.free(); inst.free()
+    ctx.close()
+    if args.kernel_stats:
+        lines += ["", "kernels of the verifier's path, from the kernel statistics of a separate profiler run (--kernel-run, sizes %s, one Commitment.encode each):" % args.sizes]
+        lines += kernel_stats_lines(args.kernel_stats) or ["  (no k_rowp_* row in %s)" % os.path.basename(args.kernel_stats)]
     return lines
 
 
@@ -372,16 +485,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default=None, help="log2 sizes; default 16,20,22 (nizk_many: 16,20)")
-    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm", "snark_many", "nizk_many", "gens"])
+    ap.add_argument("--what", default="nizk", choices=["nizk", "snark", "msm", "snark_many", "nizk_many", "gens", "encode"])
     ap.add_argument("--gens", default="prover", choices=["prover", "verifier"], help="--what nizk / snark: the generators the timed verifications take")
     ap.add_argument("--batch", default="1,4,16,64", help="--what snark_many / nizk_many: the batch sizes K")
+    ap.add_argument("--kernel-run", action="store_true", help="--what encode: the verifier's path alone, once a size (the run a profiler wraps)")
+    ap.add_argument("--kernel-stats", default=None, help="--what encode: kernel statistics csv of such a run, quoted in the output")
     args = ap.parse_args()
     if args.sizes is None:
-        args.sizes = "16,20" if args.what in ("nizk_many", "gens") else "16,20,22"
+        args.sizes = "16,20" if args.what in ("nizk_many", "gens", "encode") else "16,20,22"
     orc = load_oracle()
     orc.orc_set_threads(ctypes.c_int(16))
     if args.what != "nizk":
-        return finish(args, {"snark": snark, "msm": msm, "snark_many": snark_many, "nizk_many": nizk_many, "gens": gens_session}[args.what](args, orc))
+        return finish(args, {"snark": snark, "msm": msm, "snark_many": snark_many, "nizk_many": nizk_many, "gens": gens_session, "encode": encode_session}[args.what](args, orc))
     lines = ["NIZK::verify on the device against the oracle's verifier on the host (bench/verify_probe.py; host CPU: %s)" % cpu_model(),
              "(a): median of %d warm calls, host clock; msm_var: HIP events around its launch chain, runs of their own; (c): median of 3, 16 threads" % REPS,
              "generators of the timed verifications: %s" % gens_kind(args),

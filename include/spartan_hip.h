@@ -108,7 +108,8 @@ int sp_msm_window_bits(void);
  * FIXED PUBLIC BASES: every multi-scalar multiplication of the PROVER (sp_commit_rows*, sp_msm_indexed, the inner-product argument) runs
  * over the points of a sp_gens through its precomputed tables (every base on the prover's path is a public generator).
  * The multiplications over points that are NOT a sp_gens are the verifiers': sp_msm_var (device) and sp_host_msm_var (calling thread) over points
- * that arrive with a proof, sp_msm_points (device) over a resident set of points that were given once (sp_points), all below. */
+ * that arrive with a proof, sp_msm_points (device) over a resident set of points that were given once (sp_points), and sp_commit_rows_points,
+ * the row commitments of a device table over such a set (a verifier that computes a circuit's commitment itself), all below. */
 /* A caller-supplied list may hold points with known relations between them (repeats, torsion shifts): the inner-product argument over such a
  * set always uses the COMPLETE addition formula in its trees; sets the library derives itself (sp_gens_from_uniform) use the faster dedicated one,
  * whose exceptional pairs cannot occur between sums over independent hash-to-curve points. */
@@ -241,6 +242,17 @@ int32_t sp_msm_points_many(sp_ctx* ctx, const sp_points* pts, const uint64_t* S 
 int32_t sp_msm_points_range(sp_ctx* ctx, const sp_points* pts, size_t off, size_t n, const uint64_t* S /*4*n, Montgomery*/, uint8_t out[32]);
 int32_t sp_msm_points_range_many(sp_ctx* ctx, const sp_points* pts, size_t off, size_t n, const uint64_t* S /*4*n*K, Montgomery*/, size_t K,
                                  uint8_t* out /*32*K*/);
+/* Row commitments of a DEVICE table over a range of the set (a verifier that holds a generator stream as a resident set and commits to a
+ * circuit itself: the two commitments of SNARK::encode, lib.rs:325-336, without the prover's window tables):
+ *   out[r] = compress( sum_{j<cols} Z[z_off + r*cols + j] * P[off + j] ),  r < rows
+ * DensePolynomial::commit_inner without blinds (dense_mlpoly.rs:164-177, as multi_commit uses it, sparse_mlpoly.rs:483-503) over cols
+ * consecutive points. One lane per scalar walks its signed 4-bit digits from the low end and adds one table entry per non-zero digit — complete
+ * additions, the points are untrusted as in every call above — and stops where the scalar ends: a 20-bit address or timestamp costs 5 or 6
+ * additions, not 64. No doublings, nothing per scalar is written to memory, the encodings come back through a device buffer (msm_var.hip).
+ * Synchronous, one round trip. SP_EINVAL, before anything is launched or allocated (out is not written): a null pointer, rows = 0,
+ * cols = 0, rows > 65536, off + cols > the set's size, z_off + rows*cols > sp_table_len(Z), a set or a table on another device than ctx. */
+int32_t sp_commit_rows_points(sp_ctx* ctx, const sp_points* pts, size_t off, const sp_table* Z, size_t z_off, size_t rows, size_t cols,
+                              uint8_t* out /*32*rows*/);
 /* Look-ahead for the zero-knowledge sum-checks. Inside their round loop nothing but DotProductProof::prove draws from the
  * random tape (d_vec, r_delta, r_beta: nizk/mod.rs:330-334), so a caller can take the draws of all rounds up front, in the
  * reference's order, and have a helper thread compute everything that depends on the tape alone while the rounds run:

@@ -4,7 +4,8 @@
 #include "internal.hpp"
 
 const char* kProfNames[PF_COUNT] = {"gens_table_build", "msm_rows_fixed", "msm_windows_fixed", "msm_reduce_pass", "msm_reduce_compress", "eq_expand", "sumcheck_eval",
-                                    "table_bind", "sumcheck_bind_eval", "vecmat", "dot", "fq_reduce", "sparse", "ipa", "spark", "misc", "msm_var", "msm_points"};
+                                    "table_bind", "sumcheck_bind_eval", "vecmat", "dot", "fq_reduce", "sparse", "ipa", "spark", "misc", "msm_var", "msm_points",
+                                    "commit_rows_points"};
 
 int32_t ensure(void** p, size_t* cap, size_t need) {
   if (*cap >= need) return SP_OK;

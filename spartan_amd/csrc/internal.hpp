@@ -37,6 +37,7 @@ enum ProfFamily {
   PF_MISC,
   PF_MSM_VAR,
   PF_MSM_POINTS,
+  PF_COMMIT_POINTS,
   PF_COUNT
 };
 extern const char* kProfNames[PF_COUNT];

@@ -224,6 +224,55 @@ __global__ void __launch_bounds__(256) k_msmp_finish(const Pt* __restrict__ part
   signal_done(sig);
 }
 
+// ---- row commitments of a DEVICE table over a range of a resident set (sp_commit_rows_points): out[r] = sum_j Z[r cols + j] P[off + j], the
+// unblinded DensePolynomial::commit_inner of a verifier that holds a generator stream as a resident set and commits to a circuit itself. The
+// table is as large as the prover's (4096 x 4096 scalars at 2^20), so nothing per scalar is written out: no digit array, no per-window grid.
+//   k_rowp_sum      one lane per (row, column), a block per (row, slice of 256 columns), rows and slices flattened on gridDim.x: the scalar out
+//                   of Montgomery form, its signed 4-bit digits recoded on the fly from the low end (fq_signed_digits4's carry chain over a
+//                   shifted copy of the limbs: no runtime-indexed array), +-table entry added into the lane's accumulator for every non-zero
+//                   digit, and the loop LEFT once what remains of the scalar and the carry are zero — an address or a timestamp of 20 bits costs
+//                   5..6 additions, not 64, and rows of such scalars (12 of the 15 slots of SPARK's comb_ops) leave together. Then the block sum;
+//   k_rowp_finish   one lane per row: the row's slices added up, the encode, 32 bytes into a device buffer the host fetches.
+__global__ void __launch_bounds__(MV_BLOCK) k_rowp_sum(const Pt* __restrict__ table, size_t stride, size_t off, const Fq* __restrict__ Z, size_t cols, size_t nslices,
+                                                       Pt* __restrict__ partial /*[rows][nslices]*/) {
+  __shared__ Pt sm[MV_BLOCK / 64];
+  const size_t b = blockIdx.x, row = b / nslices, j = (b - row * nslices) * MV_BLOCK + threadIdx.x;
+  Pt acc = pt_identity();
+  if (j < cols) {  // lanes past the row's end keep the identity: every lane reaches the block sum
+    const Fq k = fq_from_mont(ld_fq(Z + row * cols + j));
+    uint64_t l0 = k.l[0], l1 = k.l[1], l2 = k.l[2], l3 = k.l[3];
+    const Pt* tp = table + (off + j) * SP_VAR_TABLE;  // window w of point off + j: tp + w stride 8
+    int carry = 0;
+#pragma unroll 1
+    for (int w = 0; w < SP_VAR_WINDOWS && ((l0 | l1 | l2 | l3) != 0 || carry); w++) {  // k < q < 2^253: the last carry fits window 63
+      const int v = (int)(l0 & 15) + carry;
+      carry = v > 8;
+      const int d = carry ? v - 16 : v;
+      l0 = (l0 >> 4) | (l1 << 60); l1 = (l1 >> 4) | (l2 << 60); l2 = (l2 >> 4) | (l3 << 60); l3 >>= 4;
+      if (d != 0) {
+        Pt p = tp[(size_t)w * stride * SP_VAR_TABLE + ((d < 0 ? -d : d) - 1)];
+        if (d < 0) p = pt_neg(p);
+        acc = pt_add(acc, p);
+      }
+    }
+  }
+  msmv_block_sum(acc, sm, &partial[b]);
+}
+__global__ void __launch_bounds__(64) k_rowp_finish(const Pt* __restrict__ partial, size_t rows, size_t nslices, uint8_t* __restrict__ out /*32 rows*/) {
+  const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (r >= rows) return;
+  const Pt* part = partial + r * nslices;
+  Pt acc = part[0];
+#pragma unroll 1
+  for (size_t s = 1; s < nslices; s++) acc = pt_add(acc, part[s]);
+  uint8_t c[32];
+  Pt10 r10 = pt10_load(acc);
+  fe10_pin(r10.X); fe10_pin(r10.Y); fe10_pin(r10.Z); fe10_pin(r10.T);
+  pt10_compress(r10, c);
+  uint8_t* o = out + 32 * r;
+  for (int i = 0; i < 32; i++) o[i] = c[i];
+}
+
 bool many_args_ok(size_t n, size_t K) { return n != 0 && K != 0 && n <= MV_MAX_N && K <= MVM_MAX_K && n * K <= MVM_MAX_TERMS; }
 
 // the call's host inputs, back to back, where the kernels read them: the host-mapped page while they fit, else the device staging buffer
@@ -315,6 +364,29 @@ int32_t msm_points_run(sp_ctx* c, const sp_points* pts, size_t off, size_t n, co
   memcpy(out, res, 32 * K);
   return SP_OK;
 }
+
+// rows x cols scalars of a device table over the points [off, off + cols) of pts (arguments checked by the caller): out[r], 32 rows bytes through
+// a device buffer (they do not fit the host result page). One launch chain, one round trip; no threshold but the slices of 256 columns.
+int32_t commit_points_run(sp_ctx* c, const sp_points* pts, size_t off, const Fq* dZ, size_t rows, size_t cols, uint8_t* out) {
+  HIPCHK(hipSetDevice(c->dev));
+  const size_t nslices = (cols + MV_BLOCK - 1) / MV_BLOCK, nparts = rows * nslices;
+  // device buffer: [partial rows x nslices Pt][32 rows bytes of encodings]
+  const size_t off_out = nparts * sizeof(Pt), total = off_out + 32 * rows;
+  void* buf = nullptr;
+  SPCHK(pool_alloc(c, total, &buf));
+  Pt* partial = (Pt*)buf;
+  uint8_t* d_out = (uint8_t*)buf + off_out;
+  {
+    const double terms = (double)rows * (double)cols;
+    ProfScope ps(c, PF_COMMIT_POINTS, 32.0 * terms + 32.0 * (double)rows, nullptr, (double)SP_VAR_WINDOWS * terms + (double)nparts);
+    hipLaunchKernelGGL(k_rowp_sum, dim3((unsigned)nparts), dim3(MV_BLOCK), 0, c->stream, (const Pt*)pts->table, pts->n, off, dZ, cols, nslices, partial);
+    hipLaunchKernelGGL(k_rowp_finish, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, c->stream, (const Pt*)partial, rows, nslices, d_out);
+  }
+  int32_t rc = hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;  // a refused launch: out is not written
+  if (rc == SP_OK) rc = fetch_out(c, d_out, out, 32 * rows);
+  pool_release(c, buf, total);
+  return rc;
+}
 }  // namespace
 
 extern "C" int32_t sp_msm_var(sp_ctx* c, const uint8_t* points, const uint64_t* S, size_t n, uint8_t out[32]) {
@@ -404,4 +476,11 @@ extern "C" int32_t sp_msm_points(sp_ctx* c, const sp_points* pts, const uint64_t
 extern "C" int32_t sp_msm_points_many(sp_ctx* c, const sp_points* pts, const uint64_t* S, size_t n, size_t K, uint8_t* out) {
   if (!pts || n != pts->n) return SP_EINVAL;
   return sp_msm_points_range_many(c, pts, 0, n, S, K, out);
+}
+extern "C" int32_t sp_commit_rows_points(sp_ctx* c, const sp_points* pts, size_t off, const sp_table* Z, size_t z_off, size_t rows, size_t cols, uint8_t* out) {
+  constexpr size_t MAX_ROWS = 65536;
+  if (!c || !pts || !Z || !out || rows == 0 || rows > MAX_ROWS || !range_ok(pts, off, cols)) return SP_EINVAL;
+  // cols <= 65536 (the set's size) and rows <= 65536: rows * cols does not wrap
+  if (z_off > Z->len || rows * cols > Z->len - z_off || pts->dev != c->dev || !Z->ctx || Z->ctx->dev != c->dev) return SP_EINVAL;
+  return commit_points_run(c, pts, off, Z->d + z_off, rows, cols, out);
 }

@@ -510,6 +510,35 @@ void* spz_commitment_load(void* ctx, const uint8_t* bytes, size_t len) {
     return h.release();
   });
 }
+// The same handle computed from the instance itself (SNARK::encode_commitment, libspartan.hpp): the verifier runs the public preprocessing
+// instead of trusting bytes. `gens` of either kind — under verifier-only generators the two commitments are sums over the resident point
+// sets (verifier.cc) and no window table is ever built. No decommitment is kept. NULL with spz_last_error() on failure.
+void* spz_commitment_encode(void* ctx, void* inst, void* gens) {
+  return guard([&]() -> void* {
+    if (!ctx || !inst || !gens) throw Error("spz_commitment_encode: bad arguments");
+    std::unique_ptr<CommH> h(new CommH);
+    h->comm = SNARK::encode_commitment(*(Ctx*)ctx, *(Instance*)inst, *(SNARKGens*)gens);
+    auto upload = [&](const PolyCommitment& pc, sp_points** out) {
+      int32_t rc = sp_points_upload(((Ctx*)ctx)->h, pc.C[0].data(), pc.C.size(), out);
+      if (rc != SP_OK) throw Error(std::string("spz_commitment_encode: sp_points_upload failed: ") + sp_strerror(rc));
+    };
+    upload(h->comm.comm.comm_comb_ops, &h->ops);
+    upload(h->comm.comm.comm_comb_mem, &h->mem);
+    return h.release();
+  });
+}
+// bincode(ComputationCommitment) of a handle, however it was made: returns the size; fills out when cap suffices
+size_t spz_commitment_serialize(void* comm, uint8_t* out, size_t cap) {
+  if (!comm) return 0;
+  std::vector<uint8_t> b = ((CommH*)comm)->comm.serialize();
+  if (out && cap >= b.size()) memcpy(out, b.data(), b.size());
+  return b.size();
+}
+// HBM held by the handle's two resident point sets: 65536 bytes a share
+size_t spz_commitment_resident_bytes(void* comm) {
+  const CommH* h = (const CommH*)comm;
+  return h ? sp_points_table_bytes(h->ops) + sp_points_table_bytes(h->mem) : 0;
+}
 void spz_commitment_free(void* comm) { delete (CommH*)comm; }
 // SNARK::verify (lib.rs:423-466) of untrusted proof bytes against a loaded commitment: 1 accept, 0 reject, -1 malformed bytes (SNARK::deserialize),
 // -2 error (spz_last_error(): "InvalidNumberOfInputs", or a device failure). Nothing throws across the boundary.

@@ -326,6 +326,13 @@ struct ComputationDecommitment {  // lib.rs:50-54 -> r1cs.rs:67-70
   std::vector<uint8_t> serialize() const;
 };
 
+// The two halves of SNARK::encode (lib.rs:325-336), defined in the prover's sources (spark.inc, prover.cc) and shared with
+// SNARK::encode_commitment (verifier.cc): the dense representation of the instance's matrices built on the device
+// (MultiSparseMatPolynomialAsDense, sparse_mlpoly.rs:367-427 — no generators involved), and DensePolynomial::commit over the fixed-base tables
+// of the prover's generators (dense_mlpoly.rs:179-204).
+void encode_dense(Ctx& ctx, const Instance& inst, MultiSparseMatPolynomialAsDense* dense);
+PolyCommitment poly_commit(sp_ctx* c, const DevTable& Z, size_t num_vars, const PolyCommitmentGens& gens, const FqVec* blinds);
+
 struct ProveTimes {  // span names follow src/timer.rs call sites
   double polycommit = 0, sc_phase_one = 0, sc_phase_two = 0, polyeval = 0, r1cs_sat = 0, eval_sparse_polys = 0, commit_nondet_witness = 0,
          build_layered_network = 0, evalproof_layered_network = 0, total = 0;
@@ -337,6 +344,12 @@ struct SNARK {  // lib.rs:311-467
   SparseMatPolyEvalProof r1cs_eval_proof;
   // SNARK::encode (lib.rs:325-336)
   static void encode(Ctx& ctx, const Instance& inst, const SNARKGens& gens, ComputationCommitment* comm, ComputationDecommitment* decomm);
+  // The commitment half of encode alone, under EITHER kind of generators (verifier.cc): the dense representation is built, comb_ops and comb_mem
+  // are committed and the tables are let go — no decommitment is kept. What a process that only verifies runs to obtain the commitment of
+  // the circuit it verifies against, instead of trusting bytes handed to it: under verifier-only generators the row commitments are flat sums
+  // over gens_ops' / gens_mem's range of stream_eval's resident point set, under the prover's they go through the window tables as in
+  // encode. The same bytes either way, and encode's.
+  static ComputationCommitment encode_commitment(Ctx& ctx, const Instance& inst, const SNARKGens& gens);
   // SNARK::prove (lib.rs:339-420). tape_seed == nullptr: the RandomTape is seeded from OS entropy like RandomTape::new
   // (random.rs:13-15) — the production setting. A non-null seed is the `new_with_seed` test hook: it determines every blind,
   // so it must be secret, >= 256 bits of entropy and single-use, or the proof is no longer zero-knowledge.

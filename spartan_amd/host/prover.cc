@@ -384,7 +384,7 @@ static CP commit_scalar(sp_ctx* c, const Fq& x, const Fq& blind, const MultiComm
   return msm_rows(c, g1.g, {g1.G[0], g1.h}, {x, blind}, 1)[0];
 }
 // DensePolynomial::commit (dense_mlpoly.rs:179-204): L row commitments of the R-wide rows of a device table
-static PolyCommitment poly_commit(sp_ctx* c, const DevTable& Z, size_t num_vars, const PolyCommitmentGens& gens, const FqVec* blinds) { HSPAN("poly_commit");
+PolyCommitment poly_commit(sp_ctx* c, const DevTable& Z, size_t num_vars, const PolyCommitmentGens& gens, const FqVec* blinds) { HSPAN("poly_commit");
   size_t Ls = pow2(num_vars / 2), Rs = pow2(num_vars - num_vars / 2);
   const MultiCommitGens& g = gens.gens.gens_n;
   REQUIRE(g.n() == Rs && Z.len() == Ls * Rs);

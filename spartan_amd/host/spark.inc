@@ -4,15 +4,16 @@
 
 // ------------------------------------------------------------------ encode: dense representation (sparse_mlpoly.rs:367-427)
 
-void SNARK::encode(Ctx& ctx, const Instance& inst, const SNARKGens& gens, ComputationCommitment* comm, ComputationDecommitment* decomm) {
-  if (gens.is_verifier_only()) throw Error("SNARK::encode: verifier-only generators have no fixed-base tables");
+// MultiSparseMatPolynomialAsDense of the instance's three matrices, built on the device: what SNARK::encode commits to and keeps as the
+// decommitment, and what SNARK::encode_commitment (verifier.cc) commits to and lets go. No generators are involved.
+void encode_dense(Ctx& ctx, const Instance& inst, MultiSparseMatPolynomialAsDense* dense) {
   sp_ctx* c = ctx.h;
   const std::vector<SparseEntry>* mats[3] = {&inst.A, &inst.B, &inst.C};
   size_t N = 0;
   for (auto m : mats) N = std::max(N, next_pow2(m->size()));  // num_nz_entries (:349-351)
   size_t nvx = log_2(inst.num_cons), nvy = log_2(2 * inst.num_vars);
   size_t cells = nvx > nvy ? pow2(nvx) : pow2(nvy);
-  MultiSparseMatPolynomialAsDense& d = decomm->dense;
+  MultiSparseMatPolynomialAsDense& d = *dense;
   d.batch_size = 3; d.num_ops = N; d.num_mem_cells = cells;
   // comb_ops = merge(row.ops_addr x3, row.read_ts x3, col.ops_addr x3, col.read_ts x3, val x3) padded to a power of two (:414-419)
   d.comb_ops = tab_alloc(c, next_pow2(15 * N));
@@ -47,9 +48,16 @@ void SNARK::encode(Ctx& ctx, const Instance& inst, const SNARKGens& gens, Comput
     SPX(sp_sparse_entry_values(c, dmats[k], d.comb_ops.h, (12 + k) * N, N));
     d.val.push_back(tab_view(c, d.comb_ops, (12 + k) * N, N));
   }
+}
+
+void SNARK::encode(Ctx& ctx, const Instance& inst, const SNARKGens& gens, ComputationCommitment* comm, ComputationDecommitment* decomm) {
+  if (gens.is_verifier_only()) throw Error("SNARK::encode: verifier-only generators have no fixed-base tables");
+  sp_ctx* c = ctx.h;
+  encode_dense(ctx, inst, &decomm->dense);
+  const MultiSparseMatPolynomialAsDense& d = decomm->dense;
   // multi_commit (:483-503): comb_ops and comb_mem committed without blinds
   comm->num_cons = inst.num_cons; comm->num_vars = inst.num_vars; comm->num_inputs = inst.num_inputs;
-  comm->comm.batch_size = 3; comm->comm.num_ops = N; comm->comm.num_mem_cells = cells;
+  comm->comm.batch_size = d.batch_size; comm->comm.num_ops = d.num_ops; comm->comm.num_mem_cells = d.num_mem_cells;
   comm->comm.comm_comb_ops = poly_commit(c, d.comb_ops, log_2(d.comb_ops.len()), gens.gens_r1cs_eval.gens_ops, nullptr);
   comm->comm.comm_comb_mem = poly_commit(c, d.comb_mem, log_2(d.comb_mem.len()), gens.gens_r1cs_eval.gens_mem, nullptr);
 }

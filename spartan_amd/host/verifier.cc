@@ -10,6 +10,9 @@
 //   G_hat = <s, G>                  device: sp_commit_rows, one row over the fixed-base tables of gens_n; under VERIFIER-ONLY generators
 //                                   (GensStream::verifier_only, below: a stream is a resident point set there and no sp_gens exists)          
 //                                   sp_msm_points_range over gens_n's range of the stream's set. dev_commit_row is the one place that chooses
+//   the circuit's commitment        SNARK::encode_commitment (below): the dense representation of the prover's encode, then comb_ops and comb_mem
+//                                   committed over the window tables (poly_commit) or, under verifier-only generators, over gens_n's range of the
+//                                   stream's resident set: sp_commit_rows_points, one call a polynomial. No decommitment is kept
 //   everything with <= 64 terms     calling thread: sp_host_msm_var (proof points, generators by their encodings), sp_host_commit_small when
 //                                   every base is a generator (sp_host_commit_small_points under verifier-only generators: commit_gens)
 //   the SPARK sum-checks            calling thread: field arithmetic over the proof's scalars and the transcript, no groups (SumcheckInstanceProof,
@@ -693,6 +696,35 @@ SNARKGens SNARKGens::verifier_only(Ctx& ctx, size_t num_cons, size_t num_vars, s
 static size_t stream_resident_bytes(const GensStream& s) { return s.g ? sp_gens_table_bytes(s.g) : sp_points_table_bytes(s.pts.get()); }
 size_t NIZKGens::resident_bytes() const { return stream_resident_bytes(stream_sat); }
 size_t SNARKGens::resident_bytes() const { return stream_resident_bytes(stream_sat) + stream_resident_bytes(stream_eval); }
+
+// ---- the commitment of a circuit, computed by the verifier: SNARK::encode (lib.rs:325-336) is public preprocessing both parties may run. The
+// dense representation is the prover's (encode_dense), multi_commit (sparse_mlpoly.rs:483-503) commits comb_ops and comb_mem without blinds, and
+// the tables go when this returns. DensePolynomial::commit's L rows of R scalars (dense_mlpoly.rs:179-204) over gens_n: the window tables of the
+// prover's generators (poly_commit), or, under verifier-only ones, gens_n's range of the stream's resident set — sp_commit_rows_points.
+ComputationCommitment SNARK::encode_commitment(Ctx& ctx, const Instance& inst, const SNARKGens& gens) {
+  MultiSparseMatPolynomialAsDense d;
+  encode_dense(ctx, inst, &d);
+  auto commit = [&](const DevTable& Z, const PolyCommitmentGens& pg) {
+    const size_t num_vars = log_2(Z.len());
+    if (!gens.is_verifier_only()) return poly_commit(ctx.h, Z, num_vars, pg, nullptr);
+    const size_t Ls = (size_t)1 << (num_vars / 2), Rs = (size_t)1 << (num_vars - num_vars / 2);
+    const MultiCommitGens& g = pg.gens.gens_n;
+    if (g.n() != Rs || Z.len() != Ls * Rs) throw Error("SNARK::encode_commitment: the generators were made for another instance shape");
+    std::vector<uint8_t> out(32 * Ls);
+    const int32_t rc = sp_commit_rows_points(ctx.h, g.p, g.G[0], Z.h, 0, Ls, Rs, out.data());
+    if (rc != SP_OK) throw dev_error("sp_commit_rows_points", rc);
+    PolyCommitment pc;
+    pc.C.resize(Ls);
+    for (size_t i = 0; i < Ls; i++) memcpy(pc.C[i].data(), &out[32 * i], 32);
+    return pc;
+  };
+  ComputationCommitment comm;
+  comm.num_cons = inst.num_cons; comm.num_vars = inst.num_vars; comm.num_inputs = inst.num_inputs;
+  comm.comm.batch_size = d.batch_size; comm.comm.num_ops = d.num_ops; comm.comm.num_mem_cells = d.num_mem_cells;
+  comm.comm.comm_comb_ops = commit(d.comb_ops, gens.gens_r1cs_eval.gens_ops);
+  comm.comm.comm_comb_mem = commit(d.comb_mem, gens.gens_r1cs_eval.gens_mem);
+  return comm;
+}
 
 bool SNARK::deserialize(const uint8_t* bytes, size_t len, SNARK* out) {
   if (!bytes || !out) return false;

@@ -11,10 +11,12 @@ ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
 H = ctypes.CDLL(HOST_PATH)
 for f in ("spz_ctx_new", "spz_instance_new", "spz_instance_synthetic", "spz_snark_gens_new", "spz_nizk_gens_new", "spz_snark_encode",
           "spz_snark_prove", "spz_nizk_prove", "spz_ctx_raw", "spz_vars_assignment_new", "spz_snark_prove_resident", "spz_nizk_prove_resident",
-          "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load", "spz_snark_verifier_gens_new", "spz_nizk_verifier_gens_new"):
+          "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load", "spz_snark_verifier_gens_new", "spz_nizk_verifier_gens_new",
+          "spz_commitment_encode"):
     getattr(H, f).restype = vp
 for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode",
-          "spz_snark_gens_resident_bytes", "spz_nizk_gens_resident_bytes", "spz_snark_gens_table_bytes"):
+          "spz_snark_gens_resident_bytes", "spz_nizk_gens_resident_bytes", "spz_snark_gens_table_bytes", "spz_commitment_serialize",
+          "spz_commitment_resident_bytes"):
     getattr(H, f).restype = sz
 H.spz_last_error.restype = ctypes.c_char_p
 for f in ("spz_nizk_parse_probe", "spz_snark_reserialize", "spz_commitment_reserialize"):
@@ -339,7 +341,8 @@ class SNARK:
 
 
 class Commitment:
-    """the verifier's handle of a circuit: a ComputationCommitment parsed from its (untrusted) bincode bytes"""
+    """the verifier's handle of a circuit: a ComputationCommitment parsed from its (untrusted) bincode bytes (load), or computed from the
+    instance itself (encode)"""
     def __init__(self, h):
         self.h = h
 
@@ -347,6 +350,23 @@ class Commitment:
     def load(ctx, comm_bytes):
         """raises SpartanHipError for bytes that are not one commitment (ComputationCommitment::deserialize, libspartan.hpp)"""
         return Commitment(_chk(H.spz_commitment_load(ctx.h, bytes(comm_bytes), sz(len(comm_bytes))), "Commitment.load"))
+
+    @staticmethod
+    def encode(ctx, inst, gens):
+        """the commitment half of SNARK::encode (lib.rs:325-336: public preprocessing) run by the verifier, under either kind of SNARKGens:
+        with SNARKGens.verifier_only the two commitments are computed over the resident point sets and no window table is built. The dense
+        representation is dropped; no decommitment is kept. serialize() gives the bytes SNARK.encode(...).serialize_commitment() gives."""
+        return Commitment(_chk(H.spz_commitment_encode(ctx.h, inst.h, gens.h), "Commitment.encode"))
+
+    def serialize(self):
+        """bincode(ComputationCommitment) of the handle, however it was made"""
+        n = H.spz_commitment_serialize(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
+        H.spz_commitment_serialize(self.h, b, sz(n))
+        return bytes(b)
+
+    def resident_bytes(self):
+        """HBM held by the two share vectors as resident point sets: 65536 bytes a share"""
+        return int(H.spz_commitment_resident_bytes(self.h))
 
     def free(self):
         if self.h:
