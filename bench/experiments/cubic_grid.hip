@@ -1,4 +1,4 @@
-// EXPERIMENT RECORD (not compiled into the product; needs spartan_amd/csrc/spark.hip's Triple2 / block helpers around it): the
+// EXPERIMENT RECORD (not compiled into the product; needs spartan_amd/csrc/spark.hip's Triple, called Triple2 here, / block helpers around it): the
 // three-rounds-per-trip "grid" form of the batched cubic sum-check (round 3). 329 instead of 356 trips per 2^20 proof, 27.99 against
 // 27.69 ms: 64 products per entry group cost more than the trip they save. Removed from the library in round 5
 // with its entry point sp_sumcheck_grid_batched; the host half is cubic_grid_host.inc.

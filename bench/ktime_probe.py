@@ -56,10 +56,10 @@ for ni, n0 in ((16, 512), (16, 64), (4, 512)):
     host0.sort(); host2.sort()
     print("==== k_cubic_bind2_eval, %d instances, tables of %d entries" % (ni, n0))
     print("   host time of the call: no bind %.1f us, two binds %.1f us (medians)" % (host0[len(host0) // 2], host2[len(host2) // 2]))
-    lab0 = [(0, 3, "start -> table entries loaded (Triple2 from the host page, then HBM)"), (3, 4, "18 triple products (lines, 2 multiplications)"),
+    lab0 = [(0, 3, "start -> table entries loaded (Triple from the host page, then HBM)"), (3, 4, "18 triple products (lines, 2 multiplications)"),
             (4, 5, "weight (from the host page) x product"), (5, 6, "block reduction + stores to the host page"), (6, 7, "signal_done (fence, counter, flag)"), (0, 7, "whole workgroup")]
     show("  no bind (sp_sumcheck_eval_coeffs_batched):", rows0, lab0)
-    lab2 = [(0, 1, "start -> first loads back (Triple2 from the host page, then HBM)"), (1, 2, "bind at r0 (1 multiplication)"), (2, 3, "sync + bind at r1 + stores"),
+    lab2 = [(0, 1, "start -> first loads back (Triple from the host page, then HBM)"), (1, 2, "bind at r0 (1 multiplication)"), (2, 3, "sync + bind at r1 + stores"),
             (3, 4, "18 triple products"), (4, 5, "weight x product"), (5, 6, "block reduction + stores to the host page"), (6, 7, "signal_done"), (0, 7, "whole workgroup")]
     show("  two binds (sp_sumcheck_bind2_eval_batched):", rows2, lab2)
 

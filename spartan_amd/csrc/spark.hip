@@ -111,16 +111,43 @@ struct Triple {
   Fq* c_out;  // where this instance writes the bound C (non-null for exactly one instance per distinct C table)
 };
 struct TripleInline { Triple t[24]; };  // up to 24 instances in the kernel arguments (T == null) instead of the host-mapped page: see Bind2Inline
-__device__ __forceinline__ void cubic_point(const Fq& a0, const Fq& a1, const Fq& b0, const Fq& b1, const Fq& c0, const Fq& c1, Fq (&e)[3]) {
+// K = 3: e += the products at t = 0, 2, 3; K = 4: at t = 0, 1, 2, 3 (the factored forms' generic instances: e(1) splits the claim)
+template <int K>
+__device__ __forceinline__ void cubic_point(const Fq& a0, const Fq& a1, const Fq& b0, const Fq& b1, const Fq& c0, const Fq& c1, Fq (&e)[K]) {
   // the line through (0, x0), (1, x1) at 2 and 3: x1 + d, x1 + 2d with d = x1 - x0 (three modular additions per table)
   Fq da = fq_sub(a1, a0), db = fq_sub(b1, b0), dc = fq_sub(c1, c0);
   Fq a2 = fq_add(a1, da), b2 = fq_add(b1, db), c2 = fq_add(c1, dc);
   Fq a3 = fq_add(a2, da), b3 = fq_add(b2, db), c3 = fq_add(c2, dc);
   e[0] = fq_add(e[0], fq_mul(fq_mul(a0, b0), c0));
-  e[1] = fq_add(e[1], fq_mul(fq_mul(a2, b2), c2));
-  e[2] = fq_add(e[2], fq_mul(fq_mul(a3, b3), c3));
+  if (K == 4) e[1] = fq_add(e[1], fq_mul(fq_mul(a1, b1), c1));
+  e[K - 2] = fq_add(e[K - 2], fq_mul(fq_mul(a2, b2), c2));
+  e[K - 1] = fq_add(e[K - 1], fq_mul(fq_mul(a3, b3), c3));
 }
-// grid (nblk, ninst): partials[(inst*nblk + blk)*3 + {0,1,2}]
+// The fused bind of one entry quadruple (i, i + q, i + 2q, i + 3q), q = a quarter of the table: the bound table's pair (i, i + q) is
+// lo = x0 + r (x2 - x0), hi = x1 + r (x3 - x1). bound_quad computes it, store_quad writes it, bind_quad does both in place.
+__device__ __forceinline__ void bound_quad(const Fq* ptr, size_t i, size_t quarter, const Fq& r, Fq& lo, Fq& hi) {
+  Fq x0 = ld_fq(ptr + i), x1 = ld_fq(ptr + quarter + i), x2 = ld_fq(ptr + 2 * quarter + i), x3 = ld_fq(ptr + 3 * quarter + i);
+  lo = fq_add(x0, fq_mul(r, fq_sub(x2, x0)));
+  hi = fq_add(x1, fq_mul(r, fq_sub(x3, x1)));
+}
+__device__ __forceinline__ void store_quad(Fq* dst, size_t i, size_t quarter, const Fq& lo, const Fq& hi) {
+  st_fq(dst + i, lo);
+  st_fq(dst + quarter + i, hi);
+}
+__device__ __forceinline__ void bind_quad(Fq* ptr, size_t i, size_t quarter, const Fq& r, Fq& lo, Fq& hi) {
+  bound_quad(ptr, i, quarter, r, lo, hi);
+  store_quad(ptr, i, quarter, lo, hi);
+}
+// a workgroup's K sums of instance `inst`: partials[(inst * nblk + blk) * K + {0 .. K-1}]
+template <int K>
+__device__ __forceinline__ void store_partials(Fq* partials, unsigned inst, const Fq (&e)[K]) {
+  if (threadIdx.x == 0) {
+    Fq* p = partials + ((size_t)inst * gridDim.x + blockIdx.x) * K;
+#pragma unroll
+    for (int k = 0; k < K; k++) st_fq(p + k, e[k]);
+  }
+}
+// grid (nblk, ninst)
 __global__ void __launch_bounds__(256) k_cubic_eval_batched(const Triple* __restrict__ T, TripleInline IN, size_t half, Fq* __restrict__ partials) { SP_FG_PRIO();
   __shared__ Fq sm[256];
   Triple t = T ? T[blockIdx.y] : IN.t[blockIdx.y];
@@ -128,10 +155,7 @@ __global__ void __launch_bounds__(256) k_cubic_eval_batched(const Triple* __rest
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += (size_t)gridDim.x * blockDim.x)
     cubic_point(ld_fq(t.a + i), ld_fq(t.a + half + i), ld_fq(t.b + i), ld_fq(t.b + half + i), ld_fq(t.c + i), ld_fq(t.c + half + i), e);
   block_sum_fq<3>(e, sm);
-  if (threadIdx.x == 0) {
-    Fq* p = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
-    st_fq(p, e[0]); st_fq(p + 1, e[1]); st_fq(p + 2, e[2]);
-  }
+  store_partials(partials, blockIdx.y, e);
 }
 __global__ void __launch_bounds__(256) k_cubic_bind_eval_batched(const Triple* __restrict__ T, TripleInline IN, size_t quarter, Fq r, Fq* __restrict__ partials) { SP_FG_PRIO();
   __shared__ Fq sm[256];
@@ -142,24 +166,14 @@ __global__ void __launch_bounds__(256) k_cubic_bind_eval_batched(const Triple* _
     Fq* ptr[3] = {t.a, t.b, t.c};
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      Fq x0 = ld_fq(ptr[k] + i), x1 = ld_fq(ptr[k] + quarter + i), x2 = ld_fq(ptr[k] + 2 * quarter + i), x3 = ld_fq(ptr[k] + 3 * quarter + i);
-      lo[k] = fq_add(x0, fq_mul(r, fq_sub(x2, x0)));
-      hi[k] = fq_add(x1, fq_mul(r, fq_sub(x3, x1)));
-      if (k < 2) {
-        st_fq(ptr[k] + i, lo[k]);
-        st_fq(ptr[k] + quarter + i, hi[k]);
-      } else if (t.c_out) {  // C may be shared between instances: bound out of place, once
-        st_fq(t.c_out + i, lo[k]);
-        st_fq(t.c_out + quarter + i, hi[k]);
-      }
+      bound_quad(ptr[k], i, quarter, r, lo[k], hi[k]);
+      if (k < 2) store_quad(ptr[k], i, quarter, lo[k], hi[k]);
+      else if (t.c_out) store_quad(t.c_out, i, quarter, lo[k], hi[k]);  // C may be shared between instances: bound out of place, once
     }
     cubic_point(lo[0], hi[0], lo[1], hi[1], lo[2], hi[2], e);
   }
   block_sum_fq<3>(e, sm);
-  if (threadIdx.x == 0) {
-    Fq* p = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
-    st_fq(p, e[0]); st_fq(p + 1, e[1]); st_fq(p + 2, e[2]);
-  }
+  store_partials(partials, blockIdx.y, e);
 }
 // ---- the eq table as a FACTOR (round 4): the throughput-sized rounds of the product-circuit instances -------------------------------
 // In prove_cubic_batched under ProductCircuitEvalProofBatched::prove (product_tree.rs:259-383) the third table of every product-circuit
@@ -179,14 +193,15 @@ __device__ __forceinline__ void quad_point_eq(const Fq& a0, const Fq& a1, const 
   e[0] = fq_add(e[0], fq_mul(fq_mul(a0, b0), c));
   e[1] = fq_add(e[1], fq_mul(fq_mul(a2, b2), c));
 }
-__device__ __forceinline__ void cubic_point4(const Fq& a0, const Fq& a1, const Fq& b0, const Fq& b1, const Fq& c0, const Fq& c1, Fq (&e)[4]) {
-  Fq da = fq_sub(a1, a0), db = fq_sub(b1, b0), dc = fq_sub(c1, c0);
-  Fq a2 = fq_add(a1, da), b2 = fq_add(b1, db), c2 = fq_add(c1, dc);
-  Fq a3 = fq_add(a2, da), b3 = fq_add(b2, db), c3 = fq_add(c2, dc);
-  e[0] = fq_add(e[0], fq_mul(fq_mul(a0, b0), c0));
-  e[1] = fq_add(e[1], fq_mul(fq_mul(a1, b1), c1));
-  e[2] = fq_add(e[2], fq_mul(fq_mul(a2, b2), c2));
-  e[3] = fq_add(e[3], fq_mul(fq_mul(a3, b3), c3));
+// the workgroup's sums of a factored kernel: four of a generic instance, the two that are not zero of a factored one
+template <bool GEN>
+__device__ __forceinline__ void block_sum_eq(Fq (&e)[4], Fq* sm) {
+  if (GEN) block_sum_fq<4>(e, sm);
+  else {
+    Fq q[2] = {e[0], e[1]};
+    block_sum_fq<2>(q, sm);
+    e[0] = q[0]; e[1] = q[1];
+  }
 }
 // GEN selects the arithmetic at compile time (one launch for the product-circuit instances, one for the generic ones when there are any):
 // a kernel holding both bodies is allocated for the larger one (205 registers, two waves per SIMD instead of three)
@@ -201,18 +216,10 @@ __global__ void __launch_bounds__(256) k_cubic_eval_batched_eq(TripleInline IN, 
       quad_point_eq(ld_fq(t.a + i), ld_fq(t.a + half + i), ld_fq(t.b + i), ld_fq(t.b + half + i), ld_fq(t.c + i), e);
   } else {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += (size_t)gridDim.x * blockDim.x)
-      cubic_point4(ld_fq(t.a + i), ld_fq(t.a + half + i), ld_fq(t.b + i), ld_fq(t.b + half + i), ld_fq(t.c + i), ld_fq(t.c + half + i), e);
+      cubic_point(ld_fq(t.a + i), ld_fq(t.a + half + i), ld_fq(t.b + i), ld_fq(t.b + half + i), ld_fq(t.c + i), ld_fq(t.c + half + i), e);
   }
-  if (GEN) block_sum_fq<4>(e, sm);
-  else {
-    Fq q[2] = {e[0], e[1]};
-    block_sum_fq<2>(q, sm);
-    e[0] = q[0]; e[1] = q[1];
-  }
-  if (threadIdx.x == 0) {
-    Fq* p = partials + ((size_t)inst * gridDim.x + blockIdx.x) * 4;
-    st_fq(p, e[0]); st_fq(p + 1, e[1]); st_fq(p + 2, e[2]); st_fq(p + 3, e[3]);
-  }
+  block_sum_eq<GEN>(e, sm);
+  store_partials(partials, inst, e);
 }
 template <bool GEN>
 __global__ void __launch_bounds__(256) k_cubic_bind_eval_batched_eq(TripleInline IN, unsigned inst0, size_t quarter, Fq r, Fq* __restrict__ partials) { SP_FG_PRIO();
@@ -222,38 +229,18 @@ __global__ void __launch_bounds__(256) k_cubic_bind_eval_batched_eq(TripleInline
   Fq e[4] = {fq_zero(), fq_zero(), fq_zero(), fq_zero()};
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < quarter; i += (size_t)gridDim.x * blockDim.x) {
     Fq lo[3], hi[3];
-    Fq* ptr[3] = {t.a, t.b, t.c};
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      Fq x0 = ld_fq(ptr[k] + i), x1 = ld_fq(ptr[k] + quarter + i), x2 = ld_fq(ptr[k] + 2 * quarter + i), x3 = ld_fq(ptr[k] + 3 * quarter + i);
-      lo[k] = fq_add(x0, fq_mul(r, fq_sub(x2, x0)));
-      hi[k] = fq_add(x1, fq_mul(r, fq_sub(x3, x1)));
-      st_fq(ptr[k] + i, lo[k]);
-      st_fq(ptr[k] + quarter + i, hi[k]);
-    }
+    bind_quad(t.a, i, quarter, r, lo[0], hi[0]);
+    bind_quad(t.b, i, quarter, r, lo[1], hi[1]);
     if (!GEN) {
       quad_point_eq(lo[0], hi[0], lo[1], hi[1], ld_fq(t.c + i), e);  // the eq table is read, never bound
     } else {
-      Fq x0 = ld_fq(ptr[2] + i), x1 = ld_fq(ptr[2] + quarter + i), x2 = ld_fq(ptr[2] + 2 * quarter + i), x3 = ld_fq(ptr[2] + 3 * quarter + i);
-      lo[2] = fq_add(x0, fq_mul(r, fq_sub(x2, x0)));
-      hi[2] = fq_add(x1, fq_mul(r, fq_sub(x3, x1)));
-      if (t.c_out) {
-        st_fq(t.c_out + i, lo[2]);
-        st_fq(t.c_out + quarter + i, hi[2]);
-      }
-      cubic_point4(lo[0], hi[0], lo[1], hi[1], lo[2], hi[2], e);
+      bound_quad(t.c, i, quarter, r, lo[2], hi[2]);
+      if (t.c_out) store_quad(t.c_out, i, quarter, lo[2], hi[2]);
+      cubic_point(lo[0], hi[0], lo[1], hi[1], lo[2], hi[2], e);
     }
   }
-  if (GEN) block_sum_fq<4>(e, sm);
-  else {
-    Fq q[2] = {e[0], e[1]};
-    block_sum_fq<2>(q, sm);
-    e[0] = q[0]; e[1] = q[1];
-  }
-  if (threadIdx.x == 0) {
-    Fq* p = partials + ((size_t)inst * gridDim.x + blockIdx.x) * 4;
-    st_fq(p, e[0]); st_fq(p + 1, e[1]); st_fq(p + 2, e[2]); st_fq(p + 3, e[3]);
-  }
+  block_sum_eq<GEN>(e, sm);
+  store_partials(partials, inst, e);
 }
 // t[i] *= k for i < n (the hand-over from the factored rounds: the bound eq table the generic kernels continue with)
 __global__ void __launch_bounds__(256) k_scale_prefix(Fq* __restrict__ t, size_t n, Fq k) { SP_FG_PRIO();
@@ -346,10 +333,6 @@ __global__ void __launch_bounds__(256) k_cubic_eval_tiny(const Triple* __restric
 // Block = 8 groups x 32 lanes; group g holds the (up to) four entries z = g + p*ng, p = 0..3, of each bound table.
 // partials[(inst*nblk + blk)*18 + {0..2: evaluations at t = 0, 2, 3 | 3 + 4 t' + {0,1,2,3}: M0, M3, T1, T2 | 15..17: the entries
 // of A, B, C when the bound tables have length 1}]
-struct Triple2 {
-  Fq *a, *b, *c;
-  Fq* c_out;
-};
 __device__ __forceinline__ Fq line_at(const Fq& u, const Fq& v, int t) {  // the line through (0, u), (1, v) at t = 0, 2, 3
   Fq x2 = fq_sub(fq_dbl(v), u), x3 = fq_sub(fq_add(x2, v), u), r;
 #pragma unroll
@@ -361,10 +344,10 @@ __device__ __forceinline__ Fq line_at(const Fq& u, const Fq& v, int t) {  // the
 // Up to 24 instances travel in the kernel arguments (T == null): the table pointers and the weights are then scalar loads from the
 // kernarg segment instead of a read of the host-mapped page over PCIe at the head of every workgroup.
 struct Bind2Inline {
-  Triple2 t[24];
+  Triple t[24];
   Fq w[24];
 };
-__global__ void __launch_bounds__(256) k_cubic_bind2_eval(const Triple2* __restrict__ T, Bind2Inline IN, const Fq* __restrict__ weights, size_t len, int nbind, Fq r0, Fq r1,
+__global__ void __launch_bounds__(256) k_cubic_bind2_eval(const Triple* __restrict__ T, Bind2Inline IN, const Fq* __restrict__ weights, size_t len, int nbind, Fq r0, Fq r1,
                                                           Fq* __restrict__ partials, Fq* __restrict__ dump, DoneSig sig) { SP_FG_PRIO();
   __shared__ Fq first[8][12][2];  // [group][table*4 + position][half]: the entries bound at r0
   __shared__ Fq bnd[8][12];       // [group][table*4 + slot]: the entries bound at r0 and r1 (slots 0..3 = x0..x3)
@@ -372,7 +355,7 @@ __global__ void __launch_bounds__(256) k_cubic_bind2_eval(const Triple2* __restr
   __shared__ Fq lv[8][3][6][3];   // [group][table][line V, W, P, U, P + U, P - U][t = 0, 2, 3]
   DoneSig kt = sig; if (blockIdx.x != 0 || blockIdx.y != 0) kt.kt = nullptr;
   SP_KT(kt, 0);
-  const Triple2 t = T ? T[blockIdx.y] : IN.t[blockIdx.y];
+  const Triple t = T ? T[blockIdx.y] : IN.t[blockIdx.y];
   const Fq wv = !weights ? fq_zero() : (T ? ld_fq(weights + blockIdx.y) : IN.w[blockIdx.y]);  // from the host-mapped page (T != null): requested now, needed last
   const int grp = threadIdx.x >> 5, lane = threadIdx.x & 31;
   const size_t n2 = len >> nbind;                  // length of the tables the outputs describe (nbind = 0, 1 or 2 binds first)
@@ -647,123 +630,100 @@ int32_t sp_product_tree_many_from(sp_ctx* c, sp_table* const* stores, size_t cou
   return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
 }
 
-static int32_t batched_setup(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, size_t* len_out, bool bind_c, TripleInline* IN,
-                             const Triple** Tdev) {
-  if (!c || !A || !B || !C || ninst == 0 || ninst > 64) return SP_EINVAL;
-  size_t len = A[0] ? A[0]->len : 0;
-  std::vector<Triple> T(ninst);
+// ---- the batched cubic rounds: what all seven entry points share ------------------------------------------------------------------
+// T[ninst]: the instances' tables of `len` entries as the kernels take them. Every refusal comes before the first allocation, so a
+// refused call leaves the tables as they are. Instances below first_generic (the factored forms) share the eq table C[0], which
+// eq_form_check has looked at: it may be longer than len and is never bound. bind_len != 0: each distinct C at or after first_generic is
+// bound out of place, once, by the first instance that uses it, into its alternate buffer of bind_len entries. distinctC: those tables.
+static int32_t build_triples(sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, size_t len, size_t first_generic, size_t bind_len,
+                             Triple* T, std::vector<sp_table*>& distinctC) {
+  for (size_t k = 0; k < ninst; k++)
+    if (!A[k] || !B[k] || !C[k] || A[k]->len != len || B[k]->len != len || (k >= first_generic && C[k]->len != len)) return SP_EINVAL;
   for (size_t k = 0; k < ninst; k++) {
-    if (!A[k] || !B[k] || !C[k] || A[k]->len != len || B[k]->len != len || C[k]->len != len) return SP_EINVAL;
     T[k] = Triple{A[k]->d, B[k]->d, C[k]->d, nullptr};
-  }
-  if (len < 2 || !is_pow2(len)) return SP_EINVAL;
-  if (bind_c) {
-    for (size_t k = 0; k < ninst; k++) {
-      bool first = true;
-      for (size_t m = 0; m < k; m++) first = first && C[m] != C[k];
-      if (first) {
-        SPCHK(table_ensure_alt(C[k], len / 2));
-        T[k].c_out = C[k]->alt;
-      }
+    bool first = k >= first_generic;
+    for (size_t m = first_generic; m < k; m++) first = first && C[m] != C[k];
+    if (!first) continue;
+    distinctC.push_back(C[k]);
+    if (bind_len) {
+      SPCHK(table_ensure_alt(C[k], bind_len));
+      T[k].c_out = C[k]->alt;
     }
   }
-  const bool inline_args = c->opt.v[OPT_SUMCHECK_INLINE_ARGS] != 0;  // A/B switch
-  if (inline_args && ninst <= 24) {
-    memcpy(IN->t, T.data(), sizeof(Triple) * ninst);
-    *Tdev = nullptr;
-  } else {
-    stage_small(c, 0, T.data(), sizeof(Triple) * ninst);
-    *Tdev = (const Triple*)c->hmap;
-  }
-  *len_out = len;
   return SP_OK;
+}
+// Up to 24 instances travel in the kernel arguments (`inl`; returns null), more are staged in the host-mapped page (returns its device
+// address). may_stage = false: the factored kernels take the kernel arguments only (eq_form_check has capped the instances).
+static const Triple* place_triples(sp_ctx* c, const Triple* T, size_t ninst, Triple* inl, bool may_stage = true) {
+  const bool inline_args = c->opt.v[OPT_SUMCHECK_INLINE_ARGS] != 0;  // A/B switch
+  if (!may_stage || (inline_args && ninst <= 24)) {
+    memcpy(inl, T, sizeof(Triple) * ninst);
+    return nullptr;
+  }
+  stage_small(c, 0, T, sizeof(Triple) * ninst);
+  return (const Triple*)c->hmap;
+}
+// A, B and each distinct C after a bind that left `new_len` entries: A_k and B_k were bound in place (distinct tables assumed), each
+// distinct C into its alternate buffer, which becomes current (host bookkeeping: the kernels are stream-ordered)
+static void finish_bind(sp_table* const* A, sp_table* const* B, const std::vector<sp_table*>& distinctC, size_t ninst, size_t new_len) {
+  for (size_t k = 0; k < ninst; k++) { A[k]->len = new_len; B[k]->len = new_len; }
+  for (sp_table* t : distinctC) table_swap_to_alt(t, new_len);
 }
 // Few partials per instance (the late rounds of every layer: most of the ~400 rounds of a proof): the blocks write them
 // straight into the host-mapped result page and the calling thread adds them — F_q additions are nanoseconds there,
 // while a second launch to add them costs ~10 us on the critical path.
 static bool host_sums(size_t nblk, size_t ninst) { return nblk == 1 || 96 * nblk * ninst <= HOST_SUM_BYTES; }
-// sig: the completion signal of the trip — already raised by the evaluation kernel when it wrote its partials into the
-// host page (on_host), raised by the reduction kernel launched here otherwise. K sums per instance: 3, or the 4 of the factored forms,
-// whose partials are never in the host page
-static int32_t batched_finish(sp_ctx* c, Fq* partials, size_t nblk, size_t ninst, int K, uint64_t* out, const DoneSig& sig) {
-  if (partials != (Fq*)hres(c)) {
-    {
-      ProfScope ps(c, PF_REDUCE, 32.0 * K * (double)(nblk * ninst));
-      hipLaunchKernelGGL(k_reduce_partials_batched, dim3((unsigned)ninst), dim3(256), 0, c->stream, (const Fq*)partials, nblk, K, (Fq*)hres(c), sig);
-    }
-    SPCHK(sig_wait(c, sig));
-    memcpy(out, hres(c), 32 * K * ninst);
-    return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
-  }
-  SPCHK(sig_wait(c, sig));
-  if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  const Fq* p = (const Fq*)hres(c);  // [inst][blk][K]
-  Fq* o = (Fq*)out;
+static void sum_partials_on_host(const Fq* p, size_t nblk, size_t ninst, int K, Fq* out) {  // p[inst][blk][K] -> out[inst][K]
   for (size_t i = 0; i < ninst; i++)
     for (int k = 0; k < K; k++) {
       Fq acc = p[(i * nblk) * K + k];
       for (size_t b = 1; b < nblk; b++) acc = fq_add(acc, p[(i * nblk + b) * K + k]);
-      o[K * i + k] = acc;
+      out[K * i + k] = acc;
     }
+}
+// The geometry of a one-round trip over tables of `len` entries (the two-round trip's: bind2_shape)
+enum BatchedForm { FORM_EVAL = 0, FORM_BIND_EVAL = 1, FORM_EQ_EVAL = 2, FORM_EQ_BIND_EVAL = 3 };  // bit 0: binds first; bit 1: factored
+struct BatchedPlan {
+  size_t work;    // indices per instance: the pairs of an evaluation, the quadruples of a fused bind
+  bool tiny;      // the latency kernels: one index per 4 lanes (64 per block), per 8 lanes when it binds (32 per block)
+  size_t nblk;
+  int K;          // sums per instance: 3, or the 4 of the factored forms
+  bool on_host;   // the blocks write their partials into the host-mapped result page and raise the signal themselves
+  Fq* partials;
+  size_t scratch_bytes, sig_count;
+};
+static int32_t batched_plan(sp_ctx* c, BatchedForm form, size_t len, size_t ninst, BatchedPlan* p) {
+  const bool bind = form & 1, eq = form & 2;
+  p->work = bind ? len / 4 : len / 2;
+  // bind: one index per 8 lanes while the round is latency-bound (512 / 2048 / 8192 / 32768 measured: 45.3 / 45.0 / 44.8 / 45.6 ms per proof)
+  p->tiny = !eq && p->work <= 8192;
+  const size_t per_block = bind ? 32 : 64;
+  p->nblk = p->tiny ? (p->work + per_block - 1) / per_block : grid_for(p->work, 256);
+  p->K = eq ? 4 : 3;
+  p->on_host = host_sums(p->nblk, ninst) && p->tiny;
+  p->scratch_bytes = 32 * p->K * (p->nblk + 1) * ninst;
+  p->sig_count = p->on_host ? p->nblk * ninst : ninst;
+  SPCHK(ensure(&c->scratch, &c->scratch_cap, p->scratch_bytes));
+  p->partials = p->on_host ? (Fq*)hres(c) : (Fq*)c->scratch;
   return SP_OK;
 }
-int32_t sp_sumcheck_eval_batched(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, uint64_t* out) {
-  if (!out) return SP_EINVAL;
-  size_t len;
-  HIPCHK(hipSetDevice(c ? c->dev : 0));
-  TripleInline IN;
-  const Triple* Tdev = nullptr;
-  SPCHK(batched_setup(c, A, B, C, ninst, &len, false, &IN, &Tdev));
-  size_t half = len / 2;
-  bool tiny = half <= 8192;
-  size_t nblk = tiny ? (half + 63) / 64 : grid_for(half, 256);
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * 3 * (nblk + 1) * ninst));
-  bool on_host = host_sums(nblk, ninst) && tiny;
-  Fq* partials = on_host ? (Fq*)hres(c) : (Fq*)c->scratch;
-  DoneSig sig = sig_make(c, on_host ? nblk * ninst : ninst);
-  {
-    ProfScope ps(c, PF_SC_EVAL, 96.0 * (double)len * (double)ninst, nullptr, 6.0 * (double)half * (double)ninst);
-    if (tiny) hipLaunchKernelGGL(k_cubic_eval_tiny, dim3((unsigned)nblk, (unsigned)ninst), dim3(256), 0, c->stream, Tdev, IN, half, partials, on_host ? sig : sig_none());
-    else hipLaunchKernelGGL(k_cubic_eval_batched, dim3((unsigned)nblk, (unsigned)ninst), dim3(256), 0, c->stream, Tdev, IN, half, partials);
+// sig: the completion signal of the trip — already raised by the evaluation kernel when it wrote its partials into the
+// host page (on_host), raised by the reduction kernel launched here otherwise
+static int32_t batched_finish(sp_ctx* c, const BatchedPlan& p, size_t ninst, uint64_t* out, const DoneSig& sig) {
+  if (!p.on_host) {
+    {
+      ProfScope ps(c, PF_REDUCE, 32.0 * p.K * (double)(p.nblk * ninst));
+      hipLaunchKernelGGL(k_reduce_partials_batched, dim3((unsigned)ninst), dim3(256), 0, c->stream, (const Fq*)p.partials, p.nblk, p.K, (Fq*)hres(c), sig);
+    }
+    SPCHK(sig_wait(c, sig));
+    memcpy(out, hres(c), 32 * p.K * ninst);
+    return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
   }
-  return batched_finish(c, partials, nblk, ninst, 3, out, sig);
+  SPCHK(sig_wait(c, sig));
+  if (hipGetLastError() != hipSuccess) return SP_EHIP;
+  sum_partials_on_host(p.partials, p.nblk, ninst, p.K, (Fq*)out);
+  return SP_OK;
 }
-int32_t sp_sumcheck_bind_eval_batched(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, const uint64_t r[4],
-                                      uint64_t* out) {
-  if (!out || !r) return SP_EINVAL;
-  size_t len;
-  HIPCHK(hipSetDevice(c ? c->dev : 0));
-  if (!c) return SP_EINVAL;
-  for (size_t k = 0; k < ninst && C; k++)
-    if (C[k] && C[k]->len < 4) return SP_EINVAL;
-  TripleInline IN;
-  const Triple* Tdev = nullptr;
-  SPCHK(batched_setup(c, A, B, C, ninst, &len, true, &IN, &Tdev));
-  if (len < 4) return SP_EINVAL;
-  size_t quarter = len / 4;
-  bool tiny = quarter <= 8192;  // one index per 8 lanes while the round is latency-bound (512 / 2048 / 8192 / 32768 measured: 45.3 / 45.0 / 44.8 / 45.6 ms per proof)
-  size_t nblk = tiny ? (quarter + 31) / 32 : grid_for(quarter, 256);
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * 3 * (nblk + 1) * ninst));
-  bool on_host = host_sums(nblk, ninst) && tiny;
-  Fq* partials = on_host ? (Fq*)hres(c) : (Fq*)c->scratch;
-  DoneSig sig = sig_make(c, on_host ? nblk * ninst : ninst);
-  {
-    ProfScope ps(c, PF_SC_BIND_EVAL, (96.0 + 32.0) * (double)len * (double)ninst, nullptr, 12.0 * (double)quarter * (double)ninst);
-    if (tiny)
-      hipLaunchKernelGGL(k_cubic_bind_eval_tiny, dim3((unsigned)nblk, (unsigned)ninst), dim3(256), 0, c->stream, Tdev, IN, quarter,
-                         limbs(r), partials, on_host ? sig : sig_none());
-    else
-      hipLaunchKernelGGL(k_cubic_bind_eval_batched, dim3((unsigned)nblk, (unsigned)ninst), dim3(256), 0, c->stream, Tdev, IN, quarter,
-                         limbs(r), partials);
-  }
-  // A_k and B_k are now bound in place (distinct tables assumed for A and B); each distinct C was bound into its
-  // alternate buffer by the first instance that uses it: make that buffer current
-  for (size_t k = 0; k < ninst; k++) { A[k]->len = len / 2; B[k]->len = len / 2; }
-  for (size_t k = 0; k < ninst; k++)
-    if (C[k]->len == len) table_swap_to_alt(C[k], len / 2);
-  return batched_finish(c, partials, nblk, ninst, 3, out, sig);
-}
-
 // ---- the factored forms (kernels above): instances [0, neq) are product-circuit instances sharing the eq table C[0] (never bound, its
 // length stays what it was: the rounds read its leading entries), instances [neq, ninst) are generic. out[4 * ninst]: {q(0), q(2), 0, 0} for
 // the former, {e(0), e(1), e(2), e(3)} for the latter. Throughput-sized tables only (the latency forms have no factored twin): SP_EINVAL
@@ -777,70 +737,74 @@ static int32_t eq_form_check(sp_table* const* C, size_t ninst, size_t neq, size_
     if (!C[k] || C[k]->len != len || C[k] == C[0]) return SP_EINVAL;
   return SP_OK;
 }
-// batched_setup wants every C at the tables' length: the shared eq table keeps its original length, so the triples are built here
-static int32_t eq_form_setup(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, size_t neq, bool bind_c, size_t* len_out,
-                             TripleInline* IN) {
-  if (!c || !A || !B || !C || ninst == 0) return SP_EINVAL;
+// One trip of one round, for the four entry points below (theirs: the null checks of out and r, and the device): the checks, the triples,
+// the plan, the launch of its form under one profile record, the tables' new lengths after a bind, the K sums per instance brought back.
+// sp_sumcheck_bind_eval_batched refuses tables below 4 entries (C[k] too: each has the tables' length) before anything is allocated.
+static int32_t batched_round(sp_ctx* c, BatchedForm form, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, size_t neq, const uint64_t* r,
+                             uint64_t* out) {
+  const bool bind = form & 1, eq = form & 2;
+  if (!c || !A || !B || !C || ninst == 0 || ninst > 64) return SP_EINVAL;
   const size_t len = A[0] ? A[0]->len : 0;
-  if (len < 65536 || !is_pow2(len)) return SP_EINVAL;
-  SPCHK(eq_form_check(C, ninst, neq, len));
-  for (size_t k = 0; k < ninst; k++) {
-    if (!A[k] || !B[k] || A[k]->len != len || B[k]->len != len) return SP_EINVAL;
-    IN->t[k] = Triple{A[k]->d, B[k]->d, C[k]->d, nullptr};
-    if (bind_c && k >= neq) {
-      bool first = true;
-      for (size_t m = neq; m < k; m++) first = first && C[m] != C[k];
-      if (first) {
-        SPCHK(table_ensure_alt(C[k], len / 2));
-        IN->t[k].c_out = C[k]->alt;
-      }
+  if (len < (eq ? 65536 : bind ? 4 : 2) || !is_pow2(len)) return SP_EINVAL;
+  if (eq) SPCHK(eq_form_check(C, ninst, neq, len));
+  Triple T[64];
+  std::vector<sp_table*> distinctC;
+  SPCHK(build_triples(A, B, C, ninst, len, neq, bind ? len / 2 : 0, T, distinctC));
+  TripleInline IN;
+  const Triple* Tdev = place_triples(c, T, ninst, IN.t, !eq);
+  BatchedPlan p;
+  SPCHK(batched_plan(c, form, len, ninst, &p));
+  const DoneSig sig = sig_make(c, p.sig_count);
+  {
+    const double n = (double)ninst, ne = (double)neq, ng = (double)(ninst - neq);
+    const double bytes = eq ? 32.0 * (double)len * (bind ? 3.25 * ne + 4.0 * ng : 2.5 * ne + 3.0 * ng) : (bind ? 96.0 + 32.0 : 96.0) * (double)len * n;
+    const double muls = eq ? (double)p.work * (bind ? 8.0 * ne + 14.0 * ng : 4.0 * ne + 8.0 * ng) : (bind ? 12.0 : 6.0) * (double)p.work * n;
+    ProfScope ps(c, bind ? PF_SC_BIND_EVAL : PF_SC_EVAL, bytes, nullptr, muls);
+    const dim3 grid((unsigned)p.nblk, (unsigned)(eq ? neq : ninst)), gen((unsigned)p.nblk, (unsigned)(ninst - neq)), blk(256);
+    const DoneSig ksig = p.on_host ? sig : sig_none();
+    switch (form) {
+      case FORM_EVAL:
+        if (p.tiny) hipLaunchKernelGGL(k_cubic_eval_tiny, grid, blk, 0, c->stream, Tdev, IN, p.work, p.partials, ksig);
+        else hipLaunchKernelGGL(k_cubic_eval_batched, grid, blk, 0, c->stream, Tdev, IN, p.work, p.partials);
+        break;
+      case FORM_BIND_EVAL:
+        if (p.tiny) hipLaunchKernelGGL(k_cubic_bind_eval_tiny, grid, blk, 0, c->stream, Tdev, IN, p.work, limbs(r), p.partials, ksig);
+        else hipLaunchKernelGGL(k_cubic_bind_eval_batched, grid, blk, 0, c->stream, Tdev, IN, p.work, limbs(r), p.partials);
+        break;
+      case FORM_EQ_EVAL:
+        hipLaunchKernelGGL(k_cubic_eval_batched_eq<false>, grid, blk, 0, c->stream, IN, 0u, p.work, p.partials);
+        if (ninst > neq) hipLaunchKernelGGL(k_cubic_eval_batched_eq<true>, gen, blk, 0, c->stream, IN, (unsigned)neq, p.work, p.partials);
+        break;
+      case FORM_EQ_BIND_EVAL:
+        hipLaunchKernelGGL(k_cubic_bind_eval_batched_eq<false>, grid, blk, 0, c->stream, IN, 0u, p.work, limbs(r), p.partials);
+        if (ninst > neq) hipLaunchKernelGGL(k_cubic_bind_eval_batched_eq<true>, gen, blk, 0, c->stream, IN, (unsigned)neq, p.work, limbs(r), p.partials);
+        break;
     }
   }
-  *len_out = len;
-  return SP_OK;
+  if (bind) finish_bind(A, B, distinctC, ninst, len / 2);
+  return batched_finish(c, p, ninst, out, sig);
+}
+int32_t sp_sumcheck_eval_batched(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, uint64_t* out) {
+  if (!out) return SP_EINVAL;
+  HIPCHK(hipSetDevice(c ? c->dev : 0));
+  return batched_round(c, FORM_EVAL, A, B, C, ninst, 0, nullptr, out);
+}
+int32_t sp_sumcheck_bind_eval_batched(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, const uint64_t r[4],
+                                      uint64_t* out) {
+  if (!out || !r) return SP_EINVAL;
+  HIPCHK(hipSetDevice(c ? c->dev : 0));
+  return batched_round(c, FORM_BIND_EVAL, A, B, C, ninst, 0, r, out);
 }
 int32_t sp_sumcheck_eval_batched_eq(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, size_t neq, uint64_t* out) {
   if (!c || !out) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
-  size_t len;
-  TripleInline IN;
-  SPCHK(eq_form_setup(c, A, B, C, ninst, neq, false, &len, &IN));
-  const size_t half = len / 2, nblk = grid_for(half, 256);
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * 4 * (nblk + 1) * ninst));
-  Fq* partials = (Fq*)c->scratch;
-  DoneSig sig = sig_make(c, ninst);
-  {
-    ProfScope ps(c, PF_SC_EVAL, 32.0 * (double)len * (2.5 * (double)neq + 3.0 * (double)(ninst - neq)), nullptr,
-                 (double)half * (4.0 * (double)neq + 8.0 * (double)(ninst - neq)));
-    hipLaunchKernelGGL(k_cubic_eval_batched_eq<false>, dim3((unsigned)nblk, (unsigned)neq), dim3(256), 0, c->stream, IN, 0u, half, partials);
-    if (ninst > neq)
-      hipLaunchKernelGGL(k_cubic_eval_batched_eq<true>, dim3((unsigned)nblk, (unsigned)(ninst - neq)), dim3(256), 0, c->stream, IN, (unsigned)neq, half, partials);
-  }
-  return batched_finish(c, partials, nblk, ninst, 4, out, sig);
+  return batched_round(c, FORM_EQ_EVAL, A, B, C, ninst, neq, nullptr, out);
 }
 int32_t sp_sumcheck_bind_eval_batched_eq(sp_ctx* c, sp_table* const* A, sp_table* const* B, sp_table* const* C, size_t ninst, size_t neq, const uint64_t r[4],
                                          uint64_t* out) {
   if (!c || !out || !r) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
-  size_t len;
-  TripleInline IN;
-  SPCHK(eq_form_setup(c, A, B, C, ninst, neq, true, &len, &IN));
-  const size_t quarter = len / 4, nblk = grid_for(quarter, 256);
-  SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * 4 * (nblk + 1) * ninst));
-  Fq* partials = (Fq*)c->scratch;
-  DoneSig sig = sig_make(c, ninst);
-  {
-    ProfScope ps(c, PF_SC_BIND_EVAL, 32.0 * (double)len * (3.25 * (double)neq + 4.0 * (double)(ninst - neq)), nullptr,
-                 (double)quarter * (8.0 * (double)neq + 14.0 * (double)(ninst - neq)));
-    hipLaunchKernelGGL(k_cubic_bind_eval_batched_eq<false>, dim3((unsigned)nblk, (unsigned)neq), dim3(256), 0, c->stream, IN, 0u, quarter, limbs(r), partials);
-    if (ninst > neq)
-      hipLaunchKernelGGL(k_cubic_bind_eval_batched_eq<true>, dim3((unsigned)nblk, (unsigned)(ninst - neq)), dim3(256), 0, c->stream, IN, (unsigned)neq, quarter,
-                         limbs(r), partials);
-  }
-  for (size_t k = 0; k < ninst; k++) { A[k]->len = len / 2; B[k]->len = len / 2; }
-  for (size_t k = neq; k < ninst; k++)
-    if (C[k]->len == len) table_swap_to_alt(C[k], len / 2);
-  return batched_finish(c, partials, nblk, ninst, 4, out, sig);
+  return batched_round(c, FORM_EQ_BIND_EVAL, A, B, C, ninst, neq, r, out);
 }
 // t[i] *= k for i < n, and n becomes the table's length: the hand-over from the factored rounds to the generic ones (queued, not waited for)
 int32_t sp_table_scale_prefix(sp_ctx* c, sp_table* t, size_t n, const uint64_t k[4]) {
@@ -876,30 +840,30 @@ __global__ void __launch_bounds__(256) k_reduce_partials18(const Fq* __restrict_
 constexpr size_t TAIL_OFF = 12288, TAIL_MAX_INST = 21;  // the <= 8-entry tables of <= 21 instances behind the 18 sums per instance in the result page
 // The geometry of one k_cubic_bind2_eval trip over tables of length `len` (before its binds)
 struct Bind2Shape {
-  size_t n2, nblk;
+  size_t n2, np, ng, nblk;  // length of the tables the outputs describe; entries per group, groups (as the kernel derives them)
   bool host, tail;
   bool spill;  // reduced by kernel and 18 sums x ninst exceed the result area (ninst > 56): they stay in the scratch buffer, behind the partials
 };
 static Bind2Shape bind2_shape(size_t len, int nbind, size_t ninst, bool want_tables) {
   Bind2Shape s;
   s.n2 = len >> nbind;
-  const size_t np = s.n2 < 4 ? s.n2 : 4, ng = s.n2 / np;
-  s.nblk = (ng + 7) / 8;
+  s.np = s.n2 < 4 ? s.n2 : 4;
+  s.ng = s.n2 / s.np;
+  s.nblk = (s.ng + 7) / 8;
   s.host = 32 * 18 * s.nblk * ninst <= HOST_SUM_BYTES;
   s.tail = want_tables && s.n2 >= 2 && s.n2 <= 8 && ninst <= TAIL_MAX_INST && s.host && s.nblk == 1;
   s.spill = !s.host && 32 * 18 * ninst > HMAP_SIZE - HMAP_IN;
   return s;
 }
 // enqueue the kernel(s) of one trip on the main stream
-static void bind2_enqueue(sp_ctx* c, const Bind2Inline& IN, bool inl, const Fq* dweights, size_t len, int nbind, const Fq& r0, const Fq& r1, size_t ninst,
+static void bind2_enqueue(sp_ctx* c, const Bind2Inline& IN, const Triple* Tdev, const Fq* dweights, size_t len, int nbind, const Fq& r0, const Fq& r1, size_t ninst,
                           const Bind2Shape& sh, const DoneSig& sig) {
-  const size_t ng = sh.n2 / (sh.n2 < 4 ? sh.n2 : 4);
   Fq* partials = sh.host ? (Fq*)hres(c) : (Fq*)c->scratch;
   Fq* dump = sh.tail ? (Fq*)(hres(c) + TAIL_OFF) : nullptr;
   {
-    ProfScope ps(c, nbind ? PF_SC_BIND_EVAL : PF_SC_EVAL, 96.0 * (double)len * (double)ninst, nullptr, (nbind ? 36.0 + 36.0 : 36.0) * (double)ng * (double)ninst);
-    hipLaunchKernelGGL(k_cubic_bind2_eval, dim3((unsigned)sh.nblk, (unsigned)ninst), dim3(256), 0, c->stream, inl ? (const Triple2*)nullptr : (const Triple2*)c->hmap, IN, dweights, len,
-                       nbind, r0, r1, partials, dump, sh.host ? sig : sig_none());
+    ProfScope ps(c, nbind ? PF_SC_BIND_EVAL : PF_SC_EVAL, 96.0 * (double)len * (double)ninst, nullptr, (nbind ? 36.0 + 36.0 : 36.0) * (double)sh.ng * (double)ninst);
+    hipLaunchKernelGGL(k_cubic_bind2_eval, dim3((unsigned)sh.nblk, (unsigned)ninst), dim3(256), 0, c->stream, Tdev, IN, dweights, len, nbind, r0, r1, partials, dump,
+                       sh.host ? sig : sig_none());
   }
   if (!sh.host) {
     ProfScope ps(c, PF_REDUCE, 32.0 * 18 * (double)(sh.nblk * ninst));
@@ -914,62 +878,29 @@ static int32_t bind2_launch(sp_ctx* c, sp_table* const* A, sp_table* const* B, s
   HIPCHK(hipSetDevice(c->dev));
   size_t len = A[0] ? A[0]->len : 0;
   if (len < ((size_t)1 << nbind) || len < 2 || !is_pow2(len)) return SP_EINVAL;
-  const int do_bind = nbind;
   const size_t n2 = len >> nbind;
   if ((n2 >= 2 && !out_evals) || (n2 >= 4 && !out_coeffs) || (n2 == 1 && !out_heads)) return SP_EINVAL;
-  for (size_t k = 0; k < ninst; k++)
-    if (!A[k] || !B[k] || !C[k] || A[k]->len != len || B[k]->len != len || C[k]->len != len) return SP_EINVAL;
-  // the instances' tables; a C shared between instances is bound once, out of place
-  std::vector<Triple2> T(ninst);
+  Triple T[64];
   std::vector<sp_table*> distinctC;
-  for (size_t k = 0; k < ninst; k++) {
-    T[k] = Triple2{A[k]->d, B[k]->d, C[k]->d, nullptr};
-    bool first = true;
-    for (size_t m = 0; m < k; m++) first = first && C[m] != C[k];
-    if (first) {
-      distinctC.push_back(C[k]);
-      if (do_bind) {
-        SPCHK(table_ensure_alt(C[k], n2));
-        T[k].c_out = C[k]->alt;
-      }
-    }
-  }
-  const bool inline_args = c->opt.v[OPT_SUMCHECK_INLINE_ARGS] != 0;  // A/B switch
-  const bool inl = inline_args && ninst <= 24;
+  SPCHK(build_triples(A, B, C, ninst, len, 0, nbind ? n2 : 0, T, distinctC));
   Bind2Inline IN;
-  const Fq* dweights = nullptr;
-  if (inl) {
-    memcpy(IN.t, T.data(), sizeof(Triple2) * ninst);
-    if (weights) { memcpy(IN.w, weights, 32 * ninst); dweights = (const Fq*)c->hmap; }  // non-null: "weighted"; the values come from IN.w
-  } else {
-    stage_small(c, 0, T.data(), sizeof(Triple2) * ninst);
-    dweights = weights ? (const Fq*)stage_small(c, sizeof(Triple2) * 64, weights, 32 * ninst) : nullptr;
-  }
+  const Triple* Tdev = place_triples(c, T, ninst, IN.t);
+  const Fq* dweights = nullptr;  // non-null: "weighted"
+  if (weights && !Tdev) { memcpy(IN.w, weights, 32 * ninst); dweights = (const Fq*)c->hmap; }  // a marker: the values come from IN.w
+  else if (weights) dweights = (const Fq*)stage_small(c, sizeof(Triple) * 64, weights, 32 * ninst);
   const Bind2Shape sh = bind2_shape(len, nbind, ninst, out_tables != nullptr);
   const Fq z = fq_zero();
   SPCHK(ensure(&c->scratch, &c->scratch_cap, 32 * 18 * (sh.nblk + 1) * ninst));
   const DoneSig sig = sh.spill ? sig_none() : sig_make(c, sh.host ? sh.nblk * ninst : ninst);  // raised by the last kernel of the trip
-  bind2_enqueue(c, IN, inl, dweights, len, nbind, r0 ? limbs(r0) : z, r1 ? limbs(r1) : z, ninst, sh, sig);
-  // the tables as this trip leaves them (host bookkeeping: the kernels are stream-ordered)
-  if (do_bind) {
-    for (size_t k = 0; k < ninst; k++) { A[k]->len = n2; B[k]->len = n2; }
-    for (sp_table* t : distinctC) table_swap_to_alt(t, n2);
-  }
+  bind2_enqueue(c, IN, Tdev, dweights, len, nbind, r0 ? limbs(r0) : z, r1 ? limbs(r1) : z, ninst, sh, sig);
+  if (nbind) finish_bind(A, B, distinctC, ninst, n2);
   std::vector<Fq> sums(18 * ninst);
   if (sh.spill) {  // more than the result area holds: from the slot behind the partials (scratch has nblk + 1 per instance)
     SPCHK(fetch_out(c, (const Fq*)c->scratch + 18 * sh.nblk * ninst, sums.data(), 32 * 18 * ninst));
-  } else if (!sh.host) {
-    SPCHK(sig_wait(c, sig));
-    memcpy(sums.data(), hres(c), 32 * 18 * ninst);
   } else {
     SPCHK(sig_wait(c, sig));
-    const Fq* p = (const Fq*)hres(c);
-    for (size_t i = 0; i < ninst; i++)
-      for (int k = 0; k < 18; k++) {
-        Fq acc = p[(i * sh.nblk) * 18 + k];
-        for (size_t b = 1; b < sh.nblk; b++) acc = fq_add(acc, p[(i * sh.nblk + b) * 18 + k]);
-        sums[18 * i + k] = acc;
-      }
+    if (sh.host) sum_partials_on_host((const Fq*)hres(c), sh.nblk, ninst, 18, sums.data());
+    else memcpy(sums.data(), hres(c), 32 * 18 * ninst);
   }
   if (hipGetLastError() != hipSuccess) return SP_EHIP;
   if (out_tables) {  // [ninst][3][n2], or nothing (first word all ones) when the tables are longer than 8 or there are too many instances

@@ -73,7 +73,7 @@ def _sum3(a, b, c):
 
 
 def cubic_evals4(A, B, C):
-    """sum_i A(t) B(t) C(t) at t = 0, 1, 2, 3 over the top-variable pairs (i, i + len/2) (sumcheck.rs:290-357; cubic_point4)"""
+    """sum_i A(t) B(t) C(t) at t = 0, 1, 2, 3 over the top-variable pairs (i, i + len/2) (sumcheck.rs:290-357; cubic_point<4>)"""
     return [_sum3(a, b, c) for a, b, c in zip(_lines(A), _lines(B), _lines(C))]
 
 
@@ -208,15 +208,31 @@ def _grid_for(work, maxblocks=2048):
     return max(1, min(maxblocks, (work + 255) // 256))     # internal.hpp, grid_for
 
 
-TINY_MAX = 8192          # spark.hip:723 `tiny = half <= 8192` (eval), :749 `tiny = quarter <= 8192` (bind_eval)
-INLINE_MAX_INST = 24     # spark.hip:677 `inline_args && ninst <= 24` (batched_setup), and the same test in bind2_launch; struct TripleInline / Bind2Inline
-TREE_TAIL_MAX = 2048     # spark.hip:636 `if (len <= 2048)`: the remaining layers in one launch
-TREE_TWO_MIN = 8192      # spark.hip:642 `len <= l2max && len >= 8192`: two layers per launch
+TINY_MAX = 8192          # spark.hip, batched_plan: `p->work <= 8192`, work = half (eval) or quarter (bind_eval)
+INLINE_MAX_INST = 24     # spark.hip, place_triples: `inline_args && ninst <= 24`, for the one-round and the two-round calls; struct TripleInline / Bind2Inline
+TREE_TAIL_MAX = 2048     # spark.hip, sp_product_tree_many_from: `if (len <= 2048)`: the remaining layers in one launch
+TREE_TWO_MIN = 8192      # spark.hip, sp_product_tree_many_from: `len <= l2max && len >= 8192`: two layers per launch
 TREE_TWO_MAX_LOG2 = 18   # options.hpp:50 spark.prod_layer2_max_log2, default 18
-TREE_CHUNK = 16          # spark.hip:627 `for (k0 = 0; k0 < count; k0 += 16)`, struct Stores16
-EQ_MIN_LEN = 65536       # spark.hip:799 `len < 65536` (eq_form_setup)
-EQ_MAX_INST = 24         # spark.hip:786 `ninst > 24` (eq_form_check)
-MAX_INST = 64            # spark.hip:658 `ninst > 64`
+TREE_CHUNK = 16          # spark.hip, sp_product_tree_many_from: `for (k0 = 0; k0 < count; k0 += 16)`, struct Stores16
+EQ_MIN_LEN = 65536       # spark.hip, batched_round: `len < (eq ? 65536 : ..)`
+EQ_MAX_INST = 24         # spark.hip, eq_form_check: `ninst > 24`
+MAX_INST = 64            # spark.hip, batched_round and bind2_launch: `ninst > 64`
+# the dispatch of a batched round is decided in ONE place each (batched_plan, place_triples, build_triples, sum_partials_on_host): the tiny
+# threshold, the inline-arguments test, the first-user-of-a-distinct-C scan and the host-side sum of the per-block partials. A second copy of
+# one of them could drift unnoticed (tests/test_spark_reference.py counts them)
+SOURCE_TEXT_ONCE = [
+    "p->tiny = !eq && p->work <= 8192;",
+    "inline_args && ninst <= 24",
+    "first = first && C[m] != C[k];",
+    "acc = fq_add(acc, p[(i * nblk + b) * K + k]);",
+]
+SOURCE_FRAGMENT_ONCE = ["tiny = ", "ninst <= 24", "first && C[", "nblk + b) *"]
+
+
+def source_text_counts():
+    """how often spark.hip contains each entry of SOURCE_TEXT_ONCE and its distinctive fragment (a copy under other variable names)"""
+    src = open(os.path.join(ROOT, "spartan_amd", "csrc", "spark.hip")).read()
+    return {t: src.count(t) for t in SOURCE_TEXT_ONCE + SOURCE_FRAGMENT_ONCE}
 
 
 def plan(call, length=0, ninst=1, nbind=0, want_tables=False, count=1, neq=0):

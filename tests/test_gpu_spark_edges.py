@@ -55,6 +55,10 @@ EQ_CASES = [(1, 1), (24, 24), (3, 24)]
 # d. (n, count) of sp_product_tree_many_from(.., 0), and n of sp_product_tree
 TREE_CASES = [(2, 3), (2048, 16), (2048, 17), (4096, 33), (8192, 2), (16384, 2)]
 TREE_SINGLE = [2, 4, 2048, 4096]
+# f. the shapes of test_records_and_round_trips_of_every_batched_round_call: the smallest case of the lists above on each side of each branch
+RECORD_CHAIN = [(128, 3), (256, 64), (1024, 41), (1 << 15, 5)]      # (len0, ninst) of a.
+RECORD_EQ = [(1, 1), (3, 24)]                                       # (neq, ninst) of c.
+RECORD_TWO = [(3, 21), (3, 22), (9, 25), (4, 64)]                   # (ell, ninst) of b., weighted as there
 # e.
 DOT_MANY_CASES = [(nt, n, "edge") for nt in (1, 64) for n in (1, 255, 256, 257, 3000)] + [(64, 257, "minus_one")]
 
@@ -384,6 +388,110 @@ def test_eq_factored_form_at_its_limits(ctx, neq, ninst, which):
             _same_table("c", tCeq, Ceq, "sp_table_scale_prefix k=%#x n=%d" % (k, m))
     for t in tA + tB + tCg + [tCeq]:
         t.free()
+
+
+# ------------------------------------------------------------------ f. what a batched round call leaves behind
+# (call, shape...) -> (round trips by sp_ctx_trips, {profile family: (records, alg_bytes)} of every family the call left a record in).
+# MEASURED, not derived from the code under test: this test printed the table on the library as it stood before the batched rounds were
+# given one plan and one launch path, and it was written down here as literals. The calls must go on leaving exactly this behind.
+CALL_RECORDS = {
+    ('eval', 128, 3): (1, {'sumcheck_eval': (1, 36864.0)}),
+    ('bind_eval', 128, 3): (1, {'sumcheck_bind_eval': (1, 49152.0)}),
+    ('eval', 256, 64): (1, {'sumcheck_eval': (1, 1572864.0)}),
+    ('bind_eval', 256, 64): (1, {'sumcheck_bind_eval': (1, 2097152.0)}),
+    ('eval', 1024, 41): (1, {'sumcheck_eval': (1, 4030464.0), 'fq_reduce': (1, 31488.0)}),
+    ('bind_eval', 1024, 41): (1, {'sumcheck_bind_eval': (1, 5373952.0), 'fq_reduce': (1, 31488.0)}),
+    ('eval', 32768, 5): (1, {'sumcheck_eval': (1, 15728640.0), 'fq_reduce': (1, 30720.0)}),
+    ('bind_eval', 32768, 5): (1, {'sumcheck_bind_eval': (1, 20971520.0), 'fq_reduce': (1, 122880.0)}),
+    ('eq_eval', 65536, 1, 1): (1, {'sumcheck_eval': (1, 5242880.0), 'fq_reduce': (1, 16384.0)}),
+    ('eq_bind_eval', 65536, 1, 1): (1, {'sumcheck_bind_eval': (1, 6815744.0), 'fq_reduce': (1, 8192.0)}),
+    ('eq_eval', 65536, 3, 24): (1, {'sumcheck_eval': (1, 147849216.0), 'fq_reduce': (1, 393216.0)}),
+    ('eq_bind_eval', 65536, 3, 24): (1, {'sumcheck_bind_eval': (1, 196608000.0), 'fq_reduce': (1, 196608.0)}),
+    ('eval_coeffs', 3, 21): (1, {'sumcheck_eval': (1, 16128.0)}),
+    ('tables, no bind', 3, 21): (1, {'sumcheck_eval': (1, 16128.0)}),
+    ('bind2_eval', 3, 21): (1, {'sumcheck_bind_eval': (1, 16128.0)}),
+    ('tables', 3, 21): (1, {'sumcheck_bind_eval': (1, 16128.0)}),
+    ('eval_coeffs', 3, 22): (1, {'sumcheck_eval': (1, 16896.0)}),
+    ('tables, no bind', 3, 22): (1, {'sumcheck_eval': (1, 16896.0)}),
+    ('bind2_eval', 3, 22): (1, {'sumcheck_bind_eval': (1, 16896.0)}),
+    ('tables', 3, 22): (1, {'sumcheck_bind_eval': (1, 16896.0)}),
+    ('eval_coeffs', 9, 25): (1, {'sumcheck_eval': (1, 1228800.0), 'fq_reduce': (1, 230400.0)}),
+    ('tables, no bind', 9, 25): (1, {'sumcheck_eval': (1, 1228800.0), 'fq_reduce': (1, 230400.0)}),
+    ('bind2_eval', 9, 25): (1, {'sumcheck_bind_eval': (1, 1228800.0), 'fq_reduce': (1, 57600.0)}),
+    ('tables', 9, 25): (1, {'sumcheck_bind_eval': (1, 1228800.0), 'fq_reduce': (1, 57600.0)}),
+    ('eval_coeffs', 4, 64): (1, {'sumcheck_eval': (1, 98304.0), 'fq_reduce': (1, 36864.0)}),
+    ('tables, no bind', 4, 64): (1, {'sumcheck_eval': (1, 98304.0), 'fq_reduce': (1, 36864.0)}),
+    ('bind2_eval', 4, 64): (1, {'sumcheck_bind_eval': (1, 98304.0), 'fq_reduce': (1, 36864.0)}),
+    ('tables', 4, 64): (1, {'sumcheck_bind_eval': (1, 98304.0), 'fq_reduce': (1, 36864.0)}),
+}
+
+
+@_flags_device_errors
+def test_records_and_round_trips_of_every_batched_round_call(ctx):
+    """Every entry point of the batched cubic family at the shapes of RECORD_CHAIN / RECORD_EQ / RECORD_TWO, each on freshly uploaded
+    tables: the round trips the call makes and the profile records it leaves (how many per family, and their algorithmic bytes) are
+    those of CALL_RECORDS - one trip per call, one sumcheck record per round, one fq_reduce record exactly where the sums are added on
+    the device. The values the calls return are the other tests' business: every table here holds the same edge values."""
+    from spartan_amd import capi
+    L = capi.lib
+    got = {}
+
+    def fresh(n, ninst, nd):
+        """A_k, B_k and nd distinct C (all but the last instance share the first; nd = 1: all share it), as handle arrays"""
+        arr = _packed("a", n, 0)[1]
+        tabs = [capi.Table.upload(ctx, arr, n) for _ in range(2 * ninst + nd)]
+        tC = tabs[2 * ninst:]
+        return tabs, _handles(tabs[:ninst]), _handles(tabs[ninst:2 * ninst]), _handles([tC[0]] * (ninst - 1) + [tC[-1]])
+
+    def record(key, call, tabs):
+        ctx.prof_reset()
+        t0 = L.sp_ctx_trips(ctx.h)
+        _ok(call(), repr(key))
+        trips = L.sp_ctx_trips(ctx.h) - t0
+        got[key] = (trips, {n: (v["launches"], v["alg_bytes"]) for n, v in ctx.prof_read().items() if v["launches"] or v["alg_bytes"]})
+        for t in tabs:
+            t.free()
+
+    r0, r1 = _arr([S.edge_challenges(1)[3]]), _arr([S.edge_challenges(2)[3]])
+    ctx.prof_enable(True)
+    try:
+        for n, ninst in RECORD_CHAIN:
+            out = (ctypes.c_uint64 * (12 * ninst))()
+            tabs, hA, hB, hC = fresh(n, ninst, 2)
+            record(("eval", n, ninst), lambda: L.sp_sumcheck_eval_batched(ctx.h, hA, hB, hC, sz(ninst), out), tabs)
+            tabs, hA, hB, hC = fresh(n, ninst, 2)
+            record(("bind_eval", n, ninst), lambda: L.sp_sumcheck_bind_eval_batched(ctx.h, hA, hB, hC, sz(ninst), r0, out), tabs)
+        for neq, ninst in RECORD_EQ:
+            out = (ctypes.c_uint64 * (16 * ninst))()
+            for call in ("eq_eval", "eq_bind_eval"):
+                arr = _packed("a", EQ_LEN, 0)[1]
+                tabs = [capi.Table.upload(ctx, arr, EQ_LEN) for _ in range(2 * ninst + 1 + ninst - neq)]
+                hA, hB, hC = _handles(tabs[:ninst]), _handles(tabs[ninst:2 * ninst]), _handles([tabs[2 * ninst]] * neq + tabs[2 * ninst + 1:])
+                if call == "eq_eval":
+                    record((call, EQ_LEN, neq, ninst), lambda: L.sp_sumcheck_eval_batched_eq(ctx.h, hA, hB, hC, sz(ninst), sz(neq), out), tabs)
+                else:
+                    record((call, EQ_LEN, neq, ninst), lambda: L.sp_sumcheck_bind_eval_batched_eq(ctx.h, hA, hB, hC, sz(ninst), sz(neq), r0, out), tabs)
+        for ell, ninst in RECORD_TWO:
+            n = 1 << ell
+            wstart = [w for e, i, w, _ in TWO_ROUND_CASES if (e, i) == (ell, ninst)][0]
+            wm = None if wstart is None else _arr([S.edge_challenges(ell)[(wstart + k) % 4] for k in range(ninst)])
+            nout = 1 if wm else ninst
+            ev = (ctypes.c_uint64 * (12 * nout))(); co = (ctypes.c_uint64 * (48 * nout))()
+            heads = (ctypes.c_uint64 * (4 * (2 * ninst + 2)))(); tables = (ctypes.c_uint64 * (4 * ninst * 3 * 8))()
+            pc = co if (n >> 2) >= 4 else None      # the coefficients exist for bound tables of 4 entries and more
+            tabs, hA, hB, hC = fresh(n, ninst, 2)
+            record(("eval_coeffs", ell, ninst), lambda: L.sp_sumcheck_eval_coeffs_batched(ctx.h, hA, hB, hC, sz(ninst), wm, ev, co), tabs)
+            tabs, hA, hB, hC = fresh(n, ninst, 2)
+            record(("tables, no bind", ell, ninst), lambda: L.sp_sumcheck_bind2_eval_tables_batched(ctx.h, hA, hB, hC, sz(ninst), None, None, wm, ev, co, None, tables), tabs)
+            tabs, hA, hB, hC = fresh(n, ninst, 2)
+            record(("bind2_eval", ell, ninst), lambda: L.sp_sumcheck_bind2_eval_batched(ctx.h, hA, hB, hC, sz(ninst), r0, r1, wm, ev, pc, heads), tabs)
+            tabs, hA, hB, hC = fresh(n, ninst, 2)
+            record(("tables", ell, ninst), lambda: L.sp_sumcheck_bind2_eval_tables_batched(ctx.h, hA, hB, hC, sz(ninst), r0, r1, wm, ev, pc, heads, tables), tabs)
+    finally:
+        ctx.prof_enable(False)
+    for key in got:
+        print("    %r: %r," % (key, got[key]))
+    assert got == CALL_RECORDS
 
 
 # ------------------------------------------------------------------ d. product trees and hash layers

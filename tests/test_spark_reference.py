@@ -133,6 +133,31 @@ def test_the_named_constants_are_read_from_the_source():
         S._constant("spark.hip", "A_CONSTANT_THAT_IS_NOT_THERE")
 
 
+def test_the_dispatch_of_a_batched_round_is_written_once():
+    """the tiny threshold, the inline-arguments test, the scan for the first user of a distinct C and the host-side sum of the per-block partials
+    each occur exactly once in spark.hip - the text itself, and its distinctive fragment under any variable names"""
+    counts = S.source_text_counts()
+    assert len(S.SOURCE_TEXT_ONCE) == 4 and len(counts) == 8 and "<= 8192" in S.SOURCE_TEXT_ONCE[0] and "ninst <= 24" in S.SOURCE_TEXT_ONCE[1]
+    assert all(f in t for f, t in zip(S.SOURCE_FRAGMENT_ONCE, S.SOURCE_TEXT_ONCE))
+    assert counts == {t: 1 for t in counts}, {t: n for t, n in counts.items() if n != 1}
+
+
+def test_the_record_shapes_sit_on_each_side_of_each_branch():
+    """the shapes of test_records_and_round_trips_of_every_batched_round_call come from the case lists, and plan() says which branch each takes"""
+    assert set(G.RECORD_CHAIN) <= {(n, i) for n, i, _, _ in G.CHAIN_CASES} and set(G.RECORD_EQ) <= set(G.EQ_CASES)
+    assert set(G.RECORD_TWO) <= {(e, i) for e, i, _, _ in G.TWO_ROUND_CASES}
+    one = {(c, n, i): S.plan(c, n, i) for n, i in G.RECORD_CHAIN for c in ("eval", "bind_eval")}
+    key = lambda p: (p["form"], p["sums"], p["args"])
+    assert [key(one["eval", n, i]) for n, i in G.RECORD_CHAIN] == [("tiny", "host", "inline"), ("tiny", "host", "staged"), ("tiny", "kernel", "staged"),
+                                                                    ("streaming", "kernel", "inline")]
+    assert key(one["bind_eval", 1 << 15, 5]) == ("tiny", "kernel", "inline") and key(one["bind_eval", 256, 64]) == ("tiny", "host", "staged")
+    assert [S.plan("eq", G.EQ_LEN, ninst=i, neq=e)["generic_launch"] for e, i in G.RECORD_EQ] == [False, True]
+    two = {(e, i, nb, wt): S.plan("bind2", 1 << e, i, nb, wt) for e, i in G.RECORD_TWO for nb in (0, 2) for wt in (False, True)}
+    assert two[3, 21, 2, True]["tail"] and two[3, 21, 0, True]["tail"] and not two[3, 22, 2, True]["tail"] and not two[3, 21, 2, False]["tail"]
+    assert all(p["sums"] == "host" for (e, _, _, _), p in two.items() if e == 3) and all(p["sums"] == "kernel" for (e, _, _, _), p in two.items() if e != 3)
+    assert {p["args"] for (e, i, _, _), p in two.items() if i <= 22} == {"inline"} and {p["args"] for (e, i, _, _), p in two.items() if i >= 25} == {"staged"}
+
+
 def _one_round_calls(cases):
     for len0, ninst, _, _ in cases:
         ln = len0
