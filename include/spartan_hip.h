@@ -29,7 +29,8 @@ typedef enum sp_status {
   SP_EINVAL = -1, /* size mismatch, non power of two, null pointer, index out of range */
   SP_ENOMEM = -2, /* hipMalloc failed */
   SP_EHIP = -3,   /* HIP runtime error / no device */
-  SP_EPOINT = -4  /* a 32-byte string is not a valid ristretto255 encoding */
+  SP_EPOINT = -4, /* a 32-byte string is not a valid ristretto255 encoding */
+  SP_ESCALAR = -5 /* a 32-byte string is not a canonical scalar (its value is >= q) */
 } sp_status;
 
 typedef struct sp_ctx sp_ctx;     /* one GPU, one stream, scratch buffers */
@@ -278,6 +279,26 @@ int32_t sp_table_clone(sp_ctx* ctx, const sp_table* t, sp_table** out);
 int32_t sp_table_copy(sp_ctx* ctx, sp_table* dst, size_t dst_off, const sp_table* src, size_t src_off, size_t len);
 size_t sp_table_len(const sp_table* t); /* current (bound) length */
 void sp_table_free(sp_table* t);
+/* ---- canonical scalar bytes <-> device tables (Assignment::new, src/lib.rs:62-88; Scalar::from_bytes / to_bytes, ristretto255.rs:390-431) ----
+ * The one place where scalars cross as CANONICAL bytes instead of Montgomery limbs: a caller that holds a witness as 32-byte little-endian
+ * values (a circuit front end, a file, another process, a kernel of its own) gets a resident table without field arithmetic of its own. The
+ * bytes are copied into the table's own allocation and converted there in place, one lane per scalar (assign.hip); a value >= q is refused, as
+ * Scalar::from_bytes refuses it. Every call is synchronous and one round trip. report (may be NULL) follows sp_r1cs_check: report[0] = the
+ * number of entries >= q, report[1] = the lowest such index (UINT64_MAX when there is none), whatever the launch geometry.
+ * SP_EINVAL, before anything is allocated or launched (neither *out nor report is written): a null pointer other than report, n = 0 or
+ * len = 0, off + len > sp_table_len(t), a table on another device than ctx. */
+/* Assignment::new on the device: n canonical little-endian scalars -> a table of n Montgomery elements. SP_ESCALAR when report[0] > 0: *out is
+ * NULL, nothing stays allocated, and the context is usable as before. */
+int32_t sp_table_from_bytes(sp_ctx* ctx, const uint8_t* bytes /*32*n, host*/, size_t n, sp_table** out, uint64_t* report /*2*/);
+/* The same from device memory of ctx's device (any byte alignment: nothing is read in place). The caller has completed the writes to
+ * dev_bytes before the call: the copy is queued on the context's stream, which knows nothing of the stream that produced them. */
+int32_t sp_table_from_bytes_dev(sp_ctx* ctx, const uint8_t* dev_bytes /*32*n, device*/, size_t n, sp_table** out, uint64_t* report /*2*/);
+/* Scalar::to_bytes of entries [off, off+len): canonical little-endian, 32 bytes each, into host memory (converted into a scratch table, then
+ * downloaded; t is not changed). The entries must be reduced, as every table the library fills is. */
+int32_t sp_table_to_bytes(sp_ctx* ctx, const sp_table* t, size_t off, size_t len, uint8_t* out /*32*len*/);
+/* Are the stored limbs of [off, off+len) all < q (what a table uploaded with sp_table_upload is trusted to hold)? The same report, its index
+ * counted from the start of the table; SP_OK either way: the report is the answer. */
+int32_t sp_table_check_reduced(sp_ctx* ctx, const sp_table* t, size_t off, size_t len, uint64_t* report /*2*/);
 
 /* EqPolynomial::evals (dense_mlpoly.rs:68-84): chi_b(r) for all b in {0,1}^ell, r[0] <-> MSB. 1 <= ell <= 32 (a long table is the outer
  * product of two short ones of at most 16 variables each); any other ell is SP_EINVAL, returned before anything is allocated. */

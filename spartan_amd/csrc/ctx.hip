@@ -182,6 +182,7 @@ const char* sp_strerror(int32_t s) {
     case SP_ENOMEM: return "out of device memory";
     case SP_EHIP: return "HIP runtime error or no gfx950 device";
     case SP_EPOINT: return "invalid ristretto255 encoding";
+    case SP_ESCALAR: return "not a canonical scalar (value >= q)";
     default: return "unknown";
   }
 }

@@ -43,6 +43,22 @@ auto guard(F f) -> decltype(f()) {
     return nullptr;
   }
 }
+// guard for the parsers of canonical scalar bytes: the report of the check goes out on success ((0, UINT64_MAX)) and on InvalidScalar alike
+template <typename F>
+auto scalar_guard(uint64_t* report, F f) -> decltype(f()) {
+  try {
+    g_err.clear();
+    auto r = f();
+    if (report) { report[0] = 0; report[1] = UINT64_MAX; }
+    return r;
+  } catch (const InvalidScalar& e) {
+    if (report) { report[0] = e.count; report[1] = e.first; }
+    g_err = e.what();
+  } catch (const std::exception& e) {
+    g_err = e.what();
+  }
+  return decltype(f())();
+}
 }  // namespace
 
 extern "C" {
@@ -351,6 +367,66 @@ void* spz_vars_assignment_new(void* ctx, const uint64_t* vars, size_t nvars) {
   return guard([&]() -> void* { return new VarsAssignment(*(Ctx*)ctx, (const sp::Fq*)vars, nvars); });
 }
 void spz_vars_assignment_free(void* a) { delete (VarsAssignment*)a; }
+// Assignment::new (lib.rs:62-88) as the reference takes it: 32 * n canonical little-endian bytes, in host memory (_from_bytes) or in the memory of
+// the context's device (_from_device_bytes: the caller has completed the writes), parsed on the device into an ordinary resident assignment.
+// NULL with spz_last_error() beginning "InvalidScalar" when an entry is >= q. report (may be NULL), on success and on that failure alike:
+// report[0] = entries >= q, report[1] = the lowest such index (UINT64_MAX when none).
+void* spz_vars_assignment_from_bytes(void* ctx, const uint8_t* bytes, size_t n, uint64_t report[2]) {
+  return scalar_guard(report, [&]() -> void* {
+    if (!ctx) throw Error("spz_vars_assignment_from_bytes: bad arguments");
+    return new VarsAssignment(VarsAssignment::from_bytes(*(Ctx*)ctx, bytes, n));
+  });
+}
+void* spz_vars_assignment_from_device_bytes(void* ctx, const uint8_t* dev, size_t n, uint64_t report[2]) {
+  return scalar_guard(report, [&]() -> void* {
+    if (!ctx) throw Error("spz_vars_assignment_from_device_bytes: bad arguments");
+    return new VarsAssignment(VarsAssignment::from_device_bytes(*(Ctx*)ctx, dev, n));
+  });
+}
+size_t spz_vars_assignment_len(void* a) { return a ? ((VarsAssignment*)a)->n : 0; }
+// Scalar::to_bytes of every entry: out receives 32 * spz_vars_assignment_len(a) bytes. 0 = ok, -1 = error (spz_last_error()).
+int spz_vars_assignment_to_bytes(void* a, uint8_t* out) {
+  try {
+    g_err.clear();
+    if (!a || !out) throw Error("spz_vars_assignment_to_bytes: bad arguments");
+    const std::vector<uint8_t> b = ((VarsAssignment*)a)->to_bytes();
+    memcpy(out, b.data(), b.size());
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+// Are the resident limbs all < q (an assignment made from Montgomery limbs is taken on trust)? report as above; 0 = checked, -1 = error.
+int spz_vars_assignment_check_reduced(void* a, uint64_t report[2]) {
+  g_err.clear();
+  const VarsAssignment* v = (const VarsAssignment*)a;
+  const int32_t rc = v && report ? sp_table_check_reduced(v->c, v->tab.h, 0, v->n, report) : SP_EINVAL;
+  if (rc != SP_OK) g_err = std::string("spz_vars_assignment_check_reduced: ") + sp_strerror(rc);
+  return rc == SP_OK ? 0 : -1;
+}
+// The same parse for inputs and other short vectors, on the calling thread, no context: limbs_out receives 4 * n Montgomery limbs.
+// 0 = ok; -1 with spz_last_error() beginning "InvalidScalar" when an entry is >= q (limbs_out is then not written). report as above.
+int spz_scalars_from_bytes(const uint8_t* bytes, size_t n, uint64_t* limbs_out, uint64_t report[2]) {
+  return scalar_guard(report, [&]() -> int {
+           if ((!bytes || !limbs_out) && n) throw Error("spz_scalars_from_bytes: bad arguments");
+           const FqVec v = scalars_from_bytes(bytes, n);
+           if (n) memcpy(limbs_out, v[0].l, 32 * n);
+           return 1;
+         }) == 1 ? 0 : -1;
+}
+int spz_scalars_to_bytes(const uint64_t* limbs, size_t n, uint8_t* out) {
+  try {
+    g_err.clear();
+    if ((!limbs || !out) && n) throw Error("spz_scalars_to_bytes: bad arguments");
+    const std::vector<uint8_t> b = scalars_to_bytes((const sp::Fq*)limbs, n);
+    if (n) memcpy(out, b.data(), b.size());
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // Instance::is_sat (lib.rs:230-259) with the report of the device check: 1 = satisfied, 0 = not, -1 = error (spz_last_error(): "InvalidNumberOfInputs"
 // as R1CSError). `assignment` (a spz_vars_assignment_new handle) or `vars` (host scalars). report[0] = violated constraints, report[1] = the first
 // (UINT64_MAX when none); rows_out (may be NULL) receives the min(report[0], rows_cap) lowest violated constraint numbers.

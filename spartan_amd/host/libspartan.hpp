@@ -225,7 +225,26 @@ struct VarsAssignment {
   DevTable tab;
   size_t n = 0;
   VarsAssignment(Ctx& ctx, const Fq* vars, size_t n);
+  // Assignment::new (lib.rs:62-88) as the reference takes it: n canonical little-endian scalars of 32 bytes. Only the bytes cross PCIe; they
+  // are checked against q and brought into Montgomery form on the device (sp_table_from_bytes). A value >= q throws InvalidScalar, where the
+  // reference returns R1CSError::InvalidScalar, and nothing stays allocated.
+  static VarsAssignment from_bytes(Ctx& ctx, const uint8_t* bytes, size_t n);
+  // The same from 32 n bytes in the memory of the context's device, at any alignment (a witness a kernel produced): they never visit the host.
+  // The caller has completed the work that wrote them (sp_table_from_bytes_dev).
+  static VarsAssignment from_device_bytes(Ctx& ctx, const uint8_t* dev, size_t n);
+  std::vector<uint8_t> to_bytes() const;  // Scalar::to_bytes of every entry (sp_table_to_bytes)
+ private:
+  VarsAssignment() {}
 };
+// R1CSError::InvalidScalar (lib.rs:75-79) with what the check found: "InvalidScalar: entry <first> (<count> of <n> entries are not canonical)"
+struct InvalidScalar : Error {
+  uint64_t first, count;
+  InvalidScalar(uint64_t first, uint64_t count, size_t n);
+};
+// Assignment::new for inputs and other short vectors, on the calling thread: the same check, the same exception. scalars_to_bytes is
+// Scalar::to_bytes of each.
+FqVec scalars_from_bytes(const uint8_t* bytes, size_t n);
+std::vector<uint8_t> scalars_to_bytes(const Fq* s, size_t n);
 // TEST/BENCH ONLY: from_bytes_wide(SHAKE256(domain || LE64(seed))[0..64]), the documented seed -> scalar map behind the
 // reproducible RandomTape seeds of tests/ and bench.py. 64 bits of entropy: never a production tape seed.
 Fq seed_scalar(const char* domain, uint64_t seed);

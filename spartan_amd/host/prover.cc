@@ -1184,6 +1184,65 @@ VarsAssignment::VarsAssignment(Ctx& ctx, const Fq* vars, size_t n_) : c(ctx.h), 
   SPX(sp_table_upload(c, vars[0].l, n_, &t));
   tab = DevTable(c, t);
 }
+InvalidScalar::InvalidScalar(uint64_t first_, uint64_t count_, size_t n)
+    : Error("InvalidScalar: entry " + std::to_string(first_) + " (" + std::to_string(count_) + " of " + std::to_string(n) + " entries are not canonical)"),
+      first(first_), count(count_) {}
+// Assignment::new (lib.rs:62-88) with Scalar::from_bytes on the device: SP_ESCALAR becomes the reference's InvalidScalar
+template <typename F>
+static VarsAssignment vars_from_bytes(VarsAssignment&& a, size_t n, F make) {
+  sp_table* t = nullptr;
+  uint64_t rep[2] = {0, UINT64_MAX};
+  const int32_t rc = make(&t, rep);
+  if (rc == SP_ESCALAR) throw InvalidScalar(rep[1], rep[0], n);
+  if (rc != SP_OK) throw Error(std::string("VarsAssignment::from_bytes failed: ") + sp_strerror(rc) + " (" + std::to_string(rc) + ")");
+  a.tab = DevTable(a.c, t);
+  a.n = n;
+  return std::move(a);
+}
+VarsAssignment VarsAssignment::from_bytes(Ctx& ctx, const uint8_t* bytes, size_t n) {
+  VarsAssignment a;
+  a.c = ctx.h;
+  return vars_from_bytes(std::move(a), n, [&](sp_table** t, uint64_t* rep) { return sp_table_from_bytes(ctx.h, bytes, n, t, rep); });
+}
+VarsAssignment VarsAssignment::from_device_bytes(Ctx& ctx, const uint8_t* dev, size_t n) {
+  VarsAssignment a;
+  a.c = ctx.h;
+  return vars_from_bytes(std::move(a), n, [&](sp_table** t, uint64_t* rep) { return sp_table_from_bytes_dev(ctx.h, dev, n, t, rep); });
+}
+std::vector<uint8_t> VarsAssignment::to_bytes() const {
+  std::vector<uint8_t> out(32 * n);
+  SPX(sp_table_to_bytes(c, tab.h, 0, n, out.data()));
+  return out;
+}
+FqVec scalars_from_bytes(const uint8_t* bytes, size_t n) {
+  REQUIRE(bytes || n == 0);
+  static const uint64_t Q[4] = {SP_Q0, SP_Q1, SP_Q2, SP_Q3};
+  FqVec v(n);
+  uint64_t first = UINT64_MAX, count = 0;
+  for (size_t i = 0; i < n; i++) {
+    Fq raw;
+    memcpy(raw.l, bytes + 32 * i, 32);  // little-endian host: the bytes are the limbs
+    bool lt = false;                    // Scalar::from_bytes (ristretto255.rs:390-416): below q, from the top limb down
+    for (int w = 3; w >= 0; w--)
+      if (raw.l[w] != Q[w]) { lt = raw.l[w] < Q[w]; break; }
+    if (!lt) {
+      if (!count++) first = i;
+      continue;
+    }
+    v[i] = fq_to_mont(raw);
+  }
+  if (count) throw InvalidScalar(first, count, n);
+  return v;
+}
+std::vector<uint8_t> scalars_to_bytes(const Fq* s, size_t n) {
+  REQUIRE(s || n == 0);
+  std::vector<uint8_t> out(32 * n);
+  for (size_t i = 0; i < n; i++) {
+    const Fq x = fq_from_mont(s[i]);
+    memcpy(out.data() + 32 * i, x.l, 32);
+  }
+  return out;
+}
 // Instance::is_sat (lib.rs:230-259). z = vars | 0... | 1 | inputs | 0... is built on the device the way r1cs_prove builds it.
 bool Instance::is_sat(const Fq* vars, size_t nvars_given, const FqVec& inputs, SatReport* report, size_t max_rows, const sp_table* vars_resident) const {
   if (nvars_given > num_vars || inputs.size() != num_inputs) throw Error("InvalidNumberOfInputs");  // lib.rs:235-241

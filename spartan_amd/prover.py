@@ -12,11 +12,11 @@ H = ctypes.CDLL(HOST_PATH)
 for f in ("spz_ctx_new", "spz_instance_new", "spz_instance_synthetic", "spz_snark_gens_new", "spz_nizk_gens_new", "spz_snark_encode",
           "spz_snark_prove", "spz_nizk_prove", "spz_ctx_raw", "spz_vars_assignment_new", "spz_snark_prove_resident", "spz_nizk_prove_resident",
           "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load", "spz_snark_verifier_gens_new", "spz_nizk_verifier_gens_new",
-          "spz_commitment_encode"):
+          "spz_commitment_encode", "spz_vars_assignment_from_bytes", "spz_vars_assignment_from_device_bytes"):
     getattr(H, f).restype = vp
 for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode",
           "spz_snark_gens_resident_bytes", "spz_nizk_gens_resident_bytes", "spz_snark_gens_table_bytes", "spz_commitment_serialize",
-          "spz_commitment_resident_bytes"):
+          "spz_commitment_resident_bytes", "spz_vars_assignment_len"):
     getattr(H, f).restype = sz
 H.spz_last_error.restype = ctypes.c_char_p
 for f in ("spz_nizk_parse_probe", "spz_snark_reserialize", "spz_commitment_reserialize"):
@@ -448,15 +448,123 @@ class NIZK:
         return _proof_bytes(p)
 
 
+class InvalidScalar(SpartanHipError):
+    """R1CSError::InvalidScalar (lib.rs:75-79): a 32-byte string of an assignment is not a canonical scalar (its value is >= q).
+    .first = the lowest index of such an entry, .count = how many there are."""
+    def __init__(self, what, first, count):
+        super().__init__(f"{what} failed: {H.spz_last_error().decode()}")
+        self.first, self.count = first, count
+
+
+def _byte_buffer(data, what):
+    """(object ctypes passes as a pointer, number of scalars) for any contiguous buffer of 32 n bytes; bytes and writable buffers are read in place"""
+    if not isinstance(data, bytes):
+        mv = memoryview(data)
+        if not mv.c_contiguous:
+            raise SpartanHipError(f"{what}: the buffer is not contiguous")
+        mv = mv.cast("B")
+        data = bytes(mv) if mv.readonly else (ctypes.c_uint8 * len(mv)).from_buffer(mv)
+    if len(data) % 32:
+        raise SpartanHipError(f"{what}: {len(data)} bytes are not a whole number of 32-byte scalars")
+    return data, len(data) // 32
+
+
+def _scalar_result(ok, rep, what):
+    if not ok:
+        if H.spz_last_error().startswith(b"InvalidScalar"):
+            raise InvalidScalar(what, int(rep[1]), int(rep[0]))
+        raise SpartanHipError(f"{what} failed: {H.spz_last_error().decode()}")
+
+
 class VarsAssignment:
     """VarsAssignment::new (lib.rs:56-105) with the scalars uploaded once: proofs over it start from the copy in HBM"""
     def __init__(self, ctx, vars_):
         self.n = len(vars_) // 4
         self.h = _chk(H.spz_vars_assignment_new(ctx.h, vars_, sz(self.n)), "VarsAssignment::new")
 
+    @classmethod
+    def _resident(cls, h):
+        a = cls.__new__(cls)
+        a.h = vp(h)
+        a.n = int(H.spz_vars_assignment_len(a.h))
+        return a
+
+    @classmethod
+    def from_bytes(cls, ctx, data):
+        """Assignment::new (lib.rs:62-88) as the reference takes it: `data` is any buffer of 32 n bytes (bytes, bytearray, memoryview, a NumPy
+        uint8 array), n canonical little-endian scalars. The bytes are uploaded as they are; the comparison with q and the conversion to
+        Montgomery form run on the device. Raises InvalidScalar when an entry is >= q."""
+        what = "VarsAssignment::from_bytes"
+        buf, n = _byte_buffer(data, what)
+        rep = (ctypes.c_uint64 * 2)()
+        h = H.spz_vars_assignment_from_bytes(ctx.h, buf, sz(n), rep)
+        _scalar_result(h, rep, what)
+        return cls._resident(h)
+
+    @classmethod
+    def from_tensor(cls, ctx, t):
+        """The same from a torch.uint8 tensor of 32 n elements on the context's device, read through its data_ptr(): the witness never visits
+        host memory. The tensor must be contiguous; it may be a view at any byte offset. THE CALLER SYNCHRONISES the stream that wrote the
+        tensor before the call (torch.cuda.synchronize(), or a synchronize of that stream): the library copies on its own stream, which is
+        not ordered against torch's. Raises InvalidScalar when an entry is >= q."""
+        import torch
+        from .capi import lib
+        what = "VarsAssignment::from_tensor"
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+            raise SpartanHipError(f"{what}: a torch.uint8 tensor on the GPU is required")
+        dev = int(lib.sp_ctx_device(ctx.raw()))
+        if t.device.index != dev:
+            raise SpartanHipError(f"{what}: the tensor is on device {t.device.index}, the context on device {dev}")
+        if not t.is_contiguous():
+            raise SpartanHipError(f"{what}: the tensor is not contiguous")
+        if t.numel() == 0 or t.numel() % 32:
+            raise SpartanHipError(f"{what}: {t.numel()} bytes are not a whole, non-zero number of 32-byte scalars")
+        rep = (ctypes.c_uint64 * 2)()
+        h = H.spz_vars_assignment_from_device_bytes(ctx.h, vp(t.data_ptr()), sz(t.numel() // 32), rep)
+        _scalar_result(h, rep, what)
+        return cls._resident(h)
+
+    def to_bytes(self):
+        """Scalar::to_bytes of every entry: 32 n canonical little-endian bytes"""
+        out = (ctypes.c_uint8 * (32 * self.n))()
+        if H.spz_vars_assignment_to_bytes(self.h, out) != 0:
+            raise SpartanHipError(f"VarsAssignment::to_bytes failed: {H.spz_last_error().decode()}")
+        return bytes(out)
+
+    def check_reduced(self):
+        """(count, first): how many of the resident entries have limbs >= q and the lowest such index (None when count is 0). An assignment made
+        from bytes is reduced by construction; one made from Montgomery limbs is taken on trust, and this is the check of that trust."""
+        rep = (ctypes.c_uint64 * 2)()
+        if H.spz_vars_assignment_check_reduced(self.h, rep) != 0:
+            raise SpartanHipError(f"VarsAssignment::check_reduced failed: {H.spz_last_error().decode()}")
+        return int(rep[0]), (int(rep[1]) if rep[0] else None)
+
     def free(self):
         if self.h:
             H.spz_vars_assignment_free(self.h); self.h = None
+
+
+class InputsAssignment:
+    """InputsAssignment::new (lib.rs:56-105) for the few public inputs: parsed on the calling thread, no context"""
+    @staticmethod
+    def from_bytes(data):
+        """32 n canonical little-endian bytes -> the ctypes uint64 array of Montgomery limbs that every `inputs` parameter takes.
+        Raises InvalidScalar when an entry is >= q."""
+        what = "InputsAssignment::from_bytes"
+        buf, n = _byte_buffer(data, what)
+        limbs = (ctypes.c_uint64 * (4 * n))()
+        rep = (ctypes.c_uint64 * 2)()
+        _scalar_result(H.spz_scalars_from_bytes(buf, sz(n), limbs, rep) == 0, rep, what)
+        return limbs
+
+    @staticmethod
+    def to_bytes(limbs):
+        """Scalar::to_bytes of each input: Montgomery limbs (a ctypes uint64 array) -> 32 n canonical little-endian bytes"""
+        n = len(limbs) // 4
+        out = (ctypes.c_uint8 * (32 * n))()
+        if H.spz_scalars_to_bytes(limbs, sz(n), out) != 0:
+            raise SpartanHipError(f"InputsAssignment::to_bytes failed: {H.spz_last_error().decode()}")
+        return bytes(out)
 
 
 class Encoded:
