@@ -30,7 +30,8 @@ typedef enum sp_status {
   SP_ENOMEM = -2, /* hipMalloc failed */
   SP_EHIP = -3,   /* HIP runtime error / no device */
   SP_EPOINT = -4, /* a 32-byte string is not a valid ristretto255 encoding */
-  SP_ESCALAR = -5 /* a 32-byte string is not a canonical scalar (its value is >= q) */
+  SP_ESCALAR = -5, /* a 32-byte string is not a canonical scalar (its value is >= q) */
+  SP_EINDEX = -6   /* an entry of a caller's matrix names a row or a column outside the declared shape (R1CSError::InvalidIndex) */
 } sp_status;
 
 typedef struct sp_ctx sp_ctx;     /* one GPU, one stream, scratch buffers */
@@ -374,6 +375,34 @@ typedef struct sp_sparse sp_sparse;
 int32_t sp_sparse_upload(sp_ctx* ctx, const uint64_t* rows, const uint64_t* cols, const uint64_t* vals /*4*nnz*/, size_t nnz,
                          size_t num_rows, size_t num_cols, sp_sparse** out);
 void sp_sparse_free(sp_sparse* m);
+/* Instance::new (src/lib.rs:121-227) for one matrix, on the device (sparse_build.hip): the entry list as the reference takes it — rows and cols
+ * as usize, vals as canonical little-endian scalars of 32 bytes at any alignment — becomes the same resident sp_sparse that sp_sparse_upload
+ * makes from entries a host loop has checked, shifted and converted. Only the indices and the bytes are copied; every call below works on the
+ * result unchanged. What Instance::new applies to an entry is given as plain numbers:
+ *   row_limit, col_limit   the caller's num_cons and num_vars + 1 + num_inputs: row >= row_limit or col >= col_limit is a bad index, tested in
+ *                          64 bits (lib.rs:164-172); only an entry with a good index has its scalar tested against q (lib.rs:175-186)
+ *   col_split, col_shift   a column >= col_split is stored as col + col_shift (lib.rs:178-182)
+ *   pad_count, pad_col     entries e in [nnz, nnz + pad_count) are (row = e, col = pad_col, val = 0): the explicit zero constraints of an
+ *                          instance with 0 or 1 constraints (lib.rs:191-195); 0 otherwise
+ *   num_rows, num_cols     the padded shape
+ * report (may be NULL; 4 words): [0] the number of entries with a bad index, [1] the lowest of them, [2] the number of entries with a good
+ * index and a value >= q, [3] the lowest of them; UINT64_MAX for an absent class; the same for any launch geometry. The status is that of the
+ * lowest failing entry, which is where the reference's loop returns: SP_EINDEX or SP_ESCALAR, *out is NULL, nothing stays allocated and the
+ * context is usable as before. Synchronous: the caller may reuse its arrays on return.
+ * SP_EINVAL, before anything is allocated or launched (neither *out nor report is written): a null ctx or out, a null array with nnz > 0 (with
+ * nnz = 0 the arrays may be null or not: a matrix may be empty), num_rows or num_cols of 0 or above 2^32 - 1, nnz + pad_count >= 2^32 - 1,
+ * row_limit > num_rows, col_limit + col_shift > num_cols, pad entries outside the shape (nnz + pad_count > num_rows or pad_col >= num_cols). */
+int32_t sp_sparse_from_entries(sp_ctx* ctx, const uint64_t* rows /*nnz, host*/, const uint64_t* cols /*nnz, host*/, const uint8_t* vals /*32*nnz, host*/,
+                               size_t nnz, uint64_t row_limit, uint64_t col_limit, uint64_t col_split, uint64_t col_shift, size_t pad_count,
+                               uint64_t pad_col, size_t num_rows, size_t num_cols, sp_sparse** out, uint64_t* report /*4*/);
+/* The same from memory of ctx's device (any byte alignment: the three arrays are copied before they are read). The caller has completed the
+ * writes to them before the call: the copies are queued on the context's stream, which knows nothing of the stream that produced them. */
+int32_t sp_sparse_from_entries_dev(sp_ctx* ctx, const uint64_t* dev_rows /*nnz*/, const uint64_t* dev_cols /*nnz*/, const uint8_t* dev_vals /*32*nnz*/,
+                                   size_t nnz, uint64_t row_limit, uint64_t col_limit, uint64_t col_split, uint64_t col_shift, size_t pad_count,
+                                   uint64_t pad_col, size_t num_rows, size_t num_cols, sp_sparse** out, uint64_t* report /*4*/);
+/* The entries of a matrix in the order they were given, as it keeps them: rows and cols of nnz elements, vals of 4 * nnz Montgomery limbs
+ * (an instance built on the device holds no host copy; its R1CSShape bincode is serialised from this download). */
+int32_t sp_sparse_download_entries(sp_ctx* ctx, const sp_sparse* m, uint32_t* rows /*nnz*/, uint32_t* cols /*nnz*/, uint64_t* vals /*4*nnz*/);
 /* multiply_vec (sparse_mlpoly.rs:454-464): out[row] = sum val * z[col]; out has num_rows elements. */
 int32_t sp_sparse_mulvec(sp_ctx* ctx, const sp_sparse* m, const sp_table* z, sp_table** out);
 /* compute_eval_table_sparse (sparse_mlpoly.rs:466-481) for nm matrices, combined as r1csproof.rs:275-283 does:

@@ -54,6 +54,62 @@ impl VarsAssignment {
 }
 
 impl Instance {
+  /// Instance::new (:121-227) with its per-entry work on the device, as an ADDITIVE constructor next to the reference's: the padding rules
+  /// (:129-156) stay here, and each matrix goes out as the caller gave it — (row, col, [u8; 32]) split into three arrays — with the limits,
+  /// the column shift and the pad entries as numbers (sp_sparse_from_entries). SP_EINDEX / SP_ESCALAR of the first matrix that fails are the
+  /// reference's InvalidIndex / InvalidScalar. The matrices are resident only; `entries` downloads them for the digest (R1CSShape::get_digest).
+  /// C++ rendering: spartan_amd/host/prover.cc, Instance::from_entries, Instance::shape_bincode.
+  #[cfg(feature = "gpu")]
+  pub fn new_gpu(
+    num_cons: usize, num_vars: usize, num_inputs: usize, A: &[(usize, usize, [u8; 32])], B: &[(usize, usize, [u8; 32])], C: &[(usize, usize, [u8; 32])],
+  ) -> Result<[gpu::Sparse; 3], R1CSError> {
+    let num_vars_padded = max(num_vars, num_inputs + 1).next_power_of_two();
+    let num_cons_padded = if num_cons.next_power_of_two() != num_cons { num_cons.next_power_of_two() } else { max(num_cons, 2) };  // :143-156, 1 for 0
+    let build = |tups: &[(usize, usize, [u8; 32])]| -> Result<gpu::Sparse, R1CSError> {
+      let rows: Vec<u64> = tups.iter().map(|t| t.0 as u64).collect();
+      let cols: Vec<u64> = tups.iter().map(|t| t.1 as u64).collect();
+      let vals: Vec<[u8; 32]> = tups.iter().map(|t| t.2).collect();
+      let pad = if num_cons < 2 && tups.len() < num_cons_padded { num_cons_padded - tups.len() } else { 0 };
+      let mut h = std::ptr::null_mut();
+      let rc = unsafe {
+        gpu::sp_sparse_from_entries(gpu::ctx(), rows.as_ptr(), cols.as_ptr(), vals.as_ptr() as *const u8, tups.len(), num_cons as u64,
+          (num_vars + 1 + num_inputs) as u64, num_vars as u64, (num_vars_padded - num_vars) as u64, pad, num_vars as u64, num_cons_padded,
+          2 * num_vars_padded, &mut h, std::ptr::null_mut())
+      };
+      Self::sparse_or_invalid(rc, h)
+    };
+    Ok([build(A)?, build(B)?, build(C)?])
+  }
+  /// One matrix of the same from three arrays in the memory of the context's device (a front end that produced the circuit there); the caller
+  /// has completed the writes. C++ rendering: Instance::from_device_entries.
+  #[cfg(feature = "gpu")]
+  pub unsafe fn matrix_from_device_gpu(
+    dev_rows: *const u64, dev_cols: *const u64, dev_vals: *const u8, nnz: usize, num_cons: usize, num_vars: usize, num_inputs: usize,
+  ) -> Result<gpu::Sparse, R1CSError> {
+    let num_vars_padded = max(num_vars, num_inputs + 1).next_power_of_two();
+    let num_cons_padded = if num_cons.next_power_of_two() != num_cons { num_cons.next_power_of_two() } else { max(num_cons, 2) };  // :143-156, 1 for 0
+    let pad = if num_cons < 2 && nnz < num_cons_padded { num_cons_padded - nnz } else { 0 };
+    let mut h = std::ptr::null_mut();
+    let rc = gpu::sp_sparse_from_entries_dev(gpu::ctx(), dev_rows, dev_cols, dev_vals, nnz, num_cons as u64, (num_vars + 1 + num_inputs) as u64,
+      num_vars as u64, (num_vars_padded - num_vars) as u64, pad, num_vars as u64, num_cons_padded, 2 * num_vars_padded, &mut h, std::ptr::null_mut());
+    Self::sparse_or_invalid(rc, h)
+  }
+  #[cfg(feature = "gpu")]
+  fn sparse_or_invalid(rc: i32, h: *mut gpu::sp_sparse) -> Result<gpu::Sparse, R1CSError> {
+    match rc {
+      gpu::SP_EINDEX => Err(R1CSError::InvalidIndex),
+      gpu::SP_ESCALAR => Err(R1CSError::InvalidScalar),
+      _ => { gpu::ok(rc); Ok(gpu::Sparse(h)) }
+    }
+  }
+  /// The entries of a resident matrix in the order they were given: what bincode(R1CSShape) serialises for the digest (r1cs.rs:154-158).
+  #[cfg(feature = "gpu")]
+  pub fn entries(m: &gpu::Sparse, nnz: usize) -> (Vec<u32>, Vec<u32>, Vec<Scalar>) {
+    let (mut rows, mut cols, mut vals) = (vec![0u32; nnz], vec![0u32; nnz], vec![Scalar::zero(); nnz]);
+    gpu::ok(unsafe { gpu::sp_sparse_download_entries(gpu::ctx(), m.0, rows.as_mut_ptr(), cols.as_mut_ptr(), vals.as_mut_ptr() as *mut u64) });
+    (rows, cols, vals)
+  }
+
   /// Instance::is_sat (:230-259) on the device, as an ADDITIVE method next to the reference's: the same length checks and zero padding, then
   /// one sp_r1cs_check over the resident matrices. Returns (satisfied, number of violated constraints, the smallest violated constraint).
   /// C++ rendering: spartan_amd/host/prover.cc, Instance::is_sat.

@@ -7,14 +7,6 @@
 
 constexpr unsigned ASSIGN_BLOCK = 256;  // threads of a workgroup; the grid is ceil(n / ASSIGN_BLOCK) workgroups, never capped: one lane per scalar
 
-// x < q, decided at the first limb from the top that differs (Scalar::from_bytes, ristretto255.rs:390-416, computes the same borrow)
-__device__ __forceinline__ bool fq_is_canonical(const Fq& x) {
-  const uint64_t q[4] = {SP_Q0, SP_Q1, SP_Q2, SP_Q3};
-#pragma unroll
-  for (int w = 3; w >= 0; w--)
-    if (x.l[w] != q[w]) return x.l[w] < q[w];
-  return false;  // x == q
-}
 // A wavefront owns 64 consecutive entries, a lane one of them. CONVERT: an entry below q is replaced by its Montgomery form (an entry >= q
 // is left as it came; the caller drops the table). res[0] += entries >= q, res[1] = min(res[1], idx_base + the lowest such index): one
 // atomicAdd and one atomicMin per wavefront that found any (the pattern of k_r1cs_check, sparse.hip), so the report does not depend on the

@@ -183,6 +183,7 @@ const char* sp_strerror(int32_t s) {
     case SP_EHIP: return "HIP runtime error or no gfx950 device";
     case SP_EPOINT: return "invalid ristretto255 encoding";
     case SP_ESCALAR: return "not a canonical scalar (value >= q)";
+    case SP_EINDEX: return "matrix entry outside the declared shape (row or column index too large)";
     default: return "unknown";
   }
 }

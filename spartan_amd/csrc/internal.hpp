@@ -378,6 +378,15 @@ __device__ __forceinline__ void st_fq(Fq* p, const Fq& v) {
   q[1] = make_ulonglong2(v.l[2], v.l[3]);
 }
 
+// x < q, decided at the first limb from the top that differs (Scalar::from_bytes, ristretto255.rs:390-416, computes the same borrow)
+__device__ __forceinline__ bool fq_is_canonical(const Fq& x) {
+  const uint64_t q[4] = {SP_Q0, SP_Q1, SP_Q2, SP_Q3};
+#pragma unroll
+  for (int w = 3; w >= 0; w--)
+    if (x.l[w] != q[w]) return x.l[w] < q[w];
+  return false;  // x == q
+}
+
 // block-wide sum of K Fq values per thread; result valid in thread 0. blockDim.x == 256.
 template <int K>
 __device__ __forceinline__ void block_sum_fq(Fq (&v)[K], Fq* smem /*256*/) {

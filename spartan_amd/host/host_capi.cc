@@ -59,6 +59,31 @@ auto scalar_guard(uint64_t* report, F f) -> decltype(f()) {
   }
   return decltype(f())();
 }
+// guard of the instance constructors that parse an entry list on the device: status, failing matrix and that matrix's report go out either way
+template <typename F>
+void* entries_guard(int32_t* status, int* matrix, uint64_t* report, F f) {
+  int32_t st = SP_EINVAL;
+  int mat = -1;
+  uint64_t rep[4] = {0, UINT64_MAX, 0, UINT64_MAX};
+  void* h = nullptr;
+  try {
+    g_err.clear();
+    h = f();
+    st = SP_OK;
+  } catch (const InvalidIndex& e) {
+    st = SP_EINDEX; mat = e.matrix; memcpy(rep, e.report, sizeof rep);
+    g_err = e.what();
+  } catch (const InvalidScalar& e) {
+    st = SP_ESCALAR; mat = e.matrix; memcpy(rep, e.report, sizeof rep);
+    g_err = e.what();
+  } catch (const std::exception& e) {
+    g_err = e.what();
+  }
+  if (status) *status = st;
+  if (matrix) *matrix = mat;
+  if (report) memcpy(report, rep, sizeof rep);
+  return h;
+}
 }  // namespace
 
 extern "C" {
@@ -122,6 +147,26 @@ void* spz_instance_new(void* ctx, size_t num_cons, size_t num_vars, size_t num_i
         m[k].push_back(e);
       }
     return new Instance(*(Ctx*)ctx, num_cons, num_vars, num_inputs, m[0], m[1], m[2]);
+  });
+}
+// Instance::new on the device (Instance::from_entries): the same arguments as spz_instance_new, and the same two errors, with what the check
+// found. NULL on failure; *status (may be NULL) = SP_OK, SP_EINDEX ("InvalidIndex: ..."), SP_ESCALAR ("InvalidScalar: ...") or SP_EINVAL for
+// anything else; *matrix (may be NULL) = 0, 1, 2 for the matrix that failed, -1 otherwise; report (may be NULL, 4 words) = that matrix's report as
+// sp_sparse_from_entries gives it, (0, UINT64_MAX, 0, UINT64_MAX) on success.
+void* spz_instance_from_entries(void* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const size_t nnz[3], const uint64_t* rows,
+                                const uint64_t* cols, const uint8_t* vals, int32_t* status, int* matrix, uint64_t report[4]) {
+  return entries_guard(status, matrix, report, [&]() -> void* {
+    if (!ctx || !nnz) throw Error("spz_instance_from_entries: bad arguments");
+    return Instance::from_entries(*(Ctx*)ctx, num_cons, num_vars, num_inputs, nnz, rows, cols, vals).release();
+  });
+}
+// The same from device memory: rows[k], cols[k], vals[k] are the three lists of matrix k in the memory of the context's device, written and
+// complete before the call.
+void* spz_instance_from_device_entries(void* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const size_t nnz[3], const uint64_t* const rows[3],
+                                       const uint64_t* const cols[3], const uint8_t* const vals[3], int32_t* status, int* matrix, uint64_t report[4]) {
+  return entries_guard(status, matrix, report, [&]() -> void* {
+    if (!ctx || !nnz || !rows || !cols || !vals) throw Error("spz_instance_from_device_entries: bad arguments");
+    return Instance::from_device_entries(*(Ctx*)ctx, num_cons, num_vars, num_inputs, nnz, rows, cols, vals).release();
   });
 }
 // Instance::produce_synthetic_r1cs with a seed; vars (num_vars) and inputs (num_inputs) are written out

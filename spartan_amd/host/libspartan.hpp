@@ -185,7 +185,9 @@ struct SatReport { uint64_t violated = 0, first_row = UINT64_MAX; std::vector<ui
 struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the matrices resident on the device
   sp_ctx* c = nullptr;
   size_t num_cons = 0, num_vars = 0, num_inputs = 0;
-  std::vector<SparseEntry> A, B, C;
+  std::vector<SparseEntry> A, B, C;  // the padded, shifted entries of an instance made on the host; empty for one made by from_entries
+  size_t nnz[3] = {0, 0, 0};         // entries of A, B, C after padding, whichever way the instance was made
+  bool resident_only = false;        // made by from_entries / from_device_entries: the entries live in dA, dB, dC alone
   sp_sparse *dA = nullptr, *dB = nullptr, *dC = nullptr;
   // R1CSShapeDigest bytes: zlib(level 6)(bincode(shape)) (r1cs.rs:154-158), absorbed by NIZK::prove (lib.rs:514). Computed on first
   // use by compute_digest() (deflate.cc: a restatement of miniz's level-6 tdefl, what flate2's rust_backend runs — byte-identical to the
@@ -205,6 +207,17 @@ struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the m
            const std::vector<SparseEntry>& B, const std::vector<SparseEntry>& C);
   ~Instance();
   Instance(const Instance&) = delete;
+  // Instance::new as the reference takes it, built on the device (sp_sparse_from_entries): the entries of A, B, C back to back, nnz[k] of
+  // each; rows and cols as usize, vals as canonical little-endian scalars of 32 bytes. Only the indices and the bytes cross PCIe: index test,
+  // comparison with q, Montgomery form, column shift, pad entries and the two sorted copies are made in HBM, and no host copy of the entries
+  // is kept (shape_bincode downloads them when the digest is computed). Throws InvalidIndex / InvalidScalar for the first matrix that fails
+  // and, within it, the lowest failing entry: where the reference's loops return.
+  static std::unique_ptr<Instance> from_entries(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const size_t nnz[3],
+                                                const uint64_t* rows, const uint64_t* cols, const uint8_t* vals);
+  // The same from three entry lists in the memory of the context's device, each (rows, cols, vals) of its own and at any alignment: nothing
+  // visits the host. The caller has completed the work that wrote them (sp_sparse_from_entries_dev).
+  static std::unique_ptr<Instance> from_device_entries(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const size_t nnz[3],
+                                                       const uint64_t* const rows[3], const uint64_t* const cols[3], const uint8_t* const vals[3]);
   // Instance::produce_synthetic_r1cs (lib.rs:262-273 -> r1cs.rs:160-238) with the OsRng replaced by a SHAKE256
   // stream keyed by `seed` ("spartan-synthetic-r1cs" || LE64(seed)); returns the satisfying assignment.
   static std::unique_ptr<Instance> produce_synthetic_r1cs(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, uint64_t seed,
@@ -215,6 +228,10 @@ struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the m
   bool is_sat(const Fq* vars, size_t num_vars_given, const FqVec& inputs, SatReport* report = nullptr, size_t max_rows = 0,
               const sp_table* vars_resident = nullptr) const;
   bool is_sat(const VarsAssignment& vars, const FqVec& inputs, SatReport* report = nullptr, size_t max_rows = 0) const;
+ private:
+  explicit Instance(sp_ctx* ctx) : c(ctx) {}
+  template <typename F>
+  static std::unique_ptr<Instance> build_resident(Ctx& ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const size_t nnz[3], F make);
 };
 // VarsAssignment (lib.rs:56-105, Assignment::new) with the scalars resident in HBM: the reference parses the caller's bytes
 // into Scalars in the constructor, outside prove; here the constructor also uploads them, once, and every proof over the
@@ -237,9 +254,22 @@ struct VarsAssignment {
   VarsAssignment() {}
 };
 // R1CSError::InvalidScalar (lib.rs:75-79) with what the check found: "InvalidScalar: entry <first> (<count> of <n> entries are not canonical)"
+// From Instance::from_entries: "InvalidScalar: matrix <A|B|C> entry <first> (...)", matrix = 0, 1, 2 (-1 for an assignment); the report of
+// that matrix is kept whole: report[0..1] = bad indices (count, lowest), report[2..3] = bad scalars among the entries with a good index.
 struct InvalidScalar : Error {
   uint64_t first, count;
+  int matrix = -1;
+  uint64_t report[4] = {0, UINT64_MAX, 0, UINT64_MAX};
   InvalidScalar(uint64_t first, uint64_t count, size_t n);
+  InvalidScalar(int matrix, const uint64_t report[4], size_t n);
+};
+// R1CSError::InvalidIndex (lib.rs:164-172) from Instance::from_entries: "InvalidIndex: matrix <A|B|C> entry <first> (<count> of <n> entries
+// name a row or a column outside the instance)"
+struct InvalidIndex : Error {
+  uint64_t first, count;
+  int matrix;
+  uint64_t report[4];
+  InvalidIndex(int matrix, const uint64_t report[4], size_t n);
 };
 // Assignment::new for inputs and other short vectors, on the calling thread: the same check, the same exception. scalars_to_bytes is
 // Scalar::to_bytes of each.

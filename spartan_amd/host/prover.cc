@@ -254,6 +254,7 @@ Instance::Instance(Ctx& ctx, size_t nc, size_t nv, size_t ni, const std::vector<
       for (size_t i = in.size(); i < ncp; i++) out.push_back(SparseEntry{i, nv, fq_zero()});
   };
   conv(A_, A); conv(B_, B); conv(C_, C);
+  nnz[0] = A.size(); nnz[1] = B.size(); nnz[2] = C.size();
   num_cons = ncp; num_vars = nvp; num_inputs = ni;
   auto up = [&](const std::vector<SparseEntry>& m, sp_sparse** d) {
     std::vector<uint64_t> r(m.size()), cc(m.size());
@@ -269,16 +270,76 @@ Instance::Instance(Ctx& ctx, size_t nc, size_t nv, size_t ni, const std::vector<
   }
 }
 Instance::~Instance() { sp_sparse_free(dA); sp_sparse_free(dB); sp_sparse_free(dC); }
+// Instance::new (lib.rs:121-227) on the device: the padding rules here, everything per entry in sp_sparse_from_entries. make(k, geometry..., out,
+// report) builds matrix k from host or from device memory.
+template <typename F>
+std::unique_ptr<Instance> Instance::build_resident(Ctx& ctx, size_t nc, size_t nv, size_t ni, const size_t nnz_in[3], F make) {
+  // padding rules: lib.rs:129-156
+  const size_t nvp = next_pow2(std::max(nv, ni + 1));
+  size_t ncp = nc;
+  if (nc == 0 || nc == 1) ncp = 2;
+  if (next_pow2(nc) != nc) ncp = next_pow2(nc);
+  std::unique_ptr<Instance> inst(new Instance(ctx.h));  // its destructor releases what was built when a later matrix throws
+  inst->resident_only = true;
+  inst->num_cons = ncp; inst->num_vars = nvp; inst->num_inputs = ni;
+  sp_sparse** d[3] = {&inst->dA, &inst->dB, &inst->dC};
+  for (int k = 0; k < 3; k++) {  // all of A, then B, then C: the error is that of the first matrix that fails
+    // lib.rs:191-195: explicit zero constraints (i, num_vars, 0) for i in tups.len()..num_cons_padded, only when num_cons is 0 or 1
+    const size_t pad = (nc == 0 || nc == 1) && nnz_in[k] < ncp ? ncp - nnz_in[k] : 0;
+    uint64_t rep[4] = {0, UINT64_MAX, 0, UINT64_MAX};
+    const int32_t rc = make(k, (uint64_t)nc, (uint64_t)(nv + 1 + ni), (uint64_t)nv, (uint64_t)(nvp - nv), pad, (uint64_t)nv, ncp, 2 * nvp, d[k], rep);
+    if (rc == SP_EINDEX) throw InvalidIndex(k, rep, nnz_in[k]);
+    if (rc == SP_ESCALAR) throw InvalidScalar(k, rep, nnz_in[k]);
+    if (rc != SP_OK) throw Error(std::string("Instance::from_entries failed: ") + sp_strerror(rc) + " (" + std::to_string(rc) + ")");
+    inst->nnz[k] = nnz_in[k] + pad;
+  }
+  return inst;
+}
+std::unique_ptr<Instance> Instance::from_entries(Ctx& ctx, size_t nc, size_t nv, size_t ni, const size_t nnz_in[3], const uint64_t* rows,
+                                                 const uint64_t* cols, const uint8_t* vals) {
+  REQUIRE(nnz_in && ((rows && cols && vals) || nnz_in[0] + nnz_in[1] + nnz_in[2] == 0));
+  const size_t off[3] = {0, nnz_in[0], nnz_in[0] + nnz_in[1]};
+  return build_resident(ctx, nc, nv, ni, nnz_in, [&](int k, uint64_t row_limit, uint64_t col_limit, uint64_t split, uint64_t shift, size_t pad,
+                                                     uint64_t pad_col, size_t nr, size_t ncols, sp_sparse** out, uint64_t* rep) {
+    const bool some = nnz_in[k] != 0;
+    return sp_sparse_from_entries(ctx.h, some ? rows + off[k] : nullptr, some ? cols + off[k] : nullptr, some ? vals + 32 * off[k] : nullptr, nnz_in[k],
+                                  row_limit, col_limit, split, shift, pad, pad_col, nr, ncols, out, rep);
+  });
+}
+std::unique_ptr<Instance> Instance::from_device_entries(Ctx& ctx, size_t nc, size_t nv, size_t ni, const size_t nnz_in[3], const uint64_t* const rows[3],
+                                                        const uint64_t* const cols[3], const uint8_t* const vals[3]) {
+  REQUIRE(nnz_in && rows && cols && vals);
+  return build_resident(ctx, nc, nv, ni, nnz_in, [&](int k, uint64_t row_limit, uint64_t col_limit, uint64_t split, uint64_t shift, size_t pad,
+                                                     uint64_t pad_col, size_t nr, size_t ncols, sp_sparse** out, uint64_t* rep) {
+    return sp_sparse_from_entries_dev(ctx.h, rows[k], cols[k], vals[k], nnz_in[k], row_limit, col_limit, split, shift, pad, pad_col, nr, ncols, out, rep);
+  });
+}
+static std::string matrix_entry(int matrix, uint64_t first) { return std::string("matrix ") + "ABC"[matrix] + " entry " + std::to_string(first); }
+InvalidIndex::InvalidIndex(int matrix_, const uint64_t rep[4], size_t n)
+    : Error("InvalidIndex: " + matrix_entry(matrix_, rep[1]) + " (" + std::to_string(rep[0]) + " of " + std::to_string(n) +
+            " entries name a row or a column outside the instance)"),
+      first(rep[1]), count(rep[0]), matrix(matrix_) { memcpy(report, rep, sizeof report); }
+InvalidScalar::InvalidScalar(int matrix_, const uint64_t rep[4], size_t n)
+    : Error("InvalidScalar: " + matrix_entry(matrix_, rep[3]) + " (" + std::to_string(rep[2]) + " of " + std::to_string(n) + " entries are not canonical)"),
+      first(rep[3]), count(rep[2]), matrix(matrix_) { memcpy(report, rep, sizeof report); }
 std::vector<uint8_t> Instance::shape_bincode() const {
   std::vector<uint8_t> b;
   auto u64 = [&](uint64_t x) { for (int i = 0; i < 8; i++) b.push_back((uint8_t)(x >> (8 * i))); };
-  size_t total = 24;
-  for (auto m : {&A, &B, &C}) total += 24 + 48 * m->size();
-  b.reserve(total);
+  b.reserve(24 + 3 * 24 + 48 * (nnz[0] + nnz[1] + nnz[2]));
   u64(num_cons); u64(num_vars); u64(num_inputs);
-  for (auto m : {&A, &B, &C}) {
-    u64(log_2(num_cons)); u64(log_2(2 * num_vars)); u64(m->size());  // SparseMatPolynomial { num_vars_x, num_vars_y, M } (r1cs.rs:104-112)
-    for (auto& e : *m) { u64(e.row); u64(e.col); for (int i = 0; i < 4; i++) u64(e.val.l[i]); }
+  const std::vector<SparseEntry>* host[3] = {&A, &B, &C};
+  const sp_sparse* dev[3] = {dA, dB, dC};
+  for (int k = 0; k < 3; k++) {
+    u64(log_2(num_cons)); u64(log_2(2 * num_vars)); u64(nnz[k]);  // SparseMatPolynomial { num_vars_x, num_vars_y, M } (r1cs.rs:104-112)
+    if (!resident_only) {
+      for (auto& e : *host[k]) { u64(e.row); u64(e.col); for (int i = 0; i < 4; i++) u64(e.val.l[i]); }
+      continue;
+    }
+    // an instance made on the device keeps its entries there: downloaded here, for the digest, and let go
+    std::vector<uint32_t> r(nnz[k]), cc(nnz[k]);
+    FqVec v(nnz[k]);
+    SPX(sp_sparse_download_entries(c, dev[k], r.data(), cc.data(), U(v)));
+    for (size_t i = 0; i < nnz[k]; i++) { u64(r[i]); u64(cc[i]); for (int j = 0; j < 4; j++) u64(v[i].l[j]); }
   }
   return b;
 }

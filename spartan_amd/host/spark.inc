@@ -8,9 +8,8 @@
 // decommitment, and what SNARK::encode_commitment (verifier.cc) commits to and lets go. No generators are involved.
 void encode_dense(Ctx& ctx, const Instance& inst, MultiSparseMatPolynomialAsDense* dense) {
   sp_ctx* c = ctx.h;
-  const std::vector<SparseEntry>* mats[3] = {&inst.A, &inst.B, &inst.C};
   size_t N = 0;
-  for (auto m : mats) N = std::max(N, next_pow2(m->size()));  // num_nz_entries (:349-351)
+  for (size_t n : inst.nnz) N = std::max(N, next_pow2(n));  // num_nz_entries (:349-351)
   size_t nvx = log_2(inst.num_cons), nvy = log_2(2 * inst.num_vars);
   size_t cells = nvx > nvy ? pow2(nvx) : pow2(nvy);
   MultiSparseMatPolynomialAsDense& d = *dense;

@@ -12,7 +12,8 @@ H = ctypes.CDLL(HOST_PATH)
 for f in ("spz_ctx_new", "spz_instance_new", "spz_instance_synthetic", "spz_snark_gens_new", "spz_nizk_gens_new", "spz_snark_encode",
           "spz_snark_prove", "spz_nizk_prove", "spz_ctx_raw", "spz_vars_assignment_new", "spz_snark_prove_resident", "spz_nizk_prove_resident",
           "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load", "spz_snark_verifier_gens_new", "spz_nizk_verifier_gens_new",
-          "spz_commitment_encode", "spz_vars_assignment_from_bytes", "spz_vars_assignment_from_device_bytes"):
+          "spz_commitment_encode", "spz_vars_assignment_from_bytes", "spz_vars_assignment_from_device_bytes", "spz_instance_from_entries",
+          "spz_instance_from_device_entries"):
     getattr(H, f).restype = vp
 for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode",
           "spz_snark_gens_resident_bytes", "spz_nizk_gens_resident_bytes", "spz_snark_gens_table_bytes", "spz_commitment_serialize",
@@ -90,6 +91,55 @@ class Instance:
         """Instance::new (lib.rs:121): entries of A, B, C back to back; vals = 32 canonical little-endian bytes each."""
         h = _chk(H.spz_instance_new(ctx.h, sz(num_cons), sz(num_vars), sz(num_inputs), (sz * 3)(*nnz), rows, cols, vals), "Instance::new")
         return Instance(h, num_cons, num_vars, num_inputs)
+
+    @staticmethod
+    def from_entries(ctx, num_cons, num_vars, num_inputs, nnz, rows, cols, vals):
+        """Instance::new (lib.rs:121) built on the device: the arguments of Instance.new (entries of A, B, C back to back, nnz = their three
+        counts, rows and cols as ctypes uint64 arrays), `vals` any buffer of 32 n bytes. Only the indices and the bytes cross PCIe: the index
+        test, the comparison with q, the Montgomery form, the column shift, the pad entries and the row- and column-sorted copies are made in
+        HBM (sp_sparse_from_entries), and the instance keeps no host copy of its entries. Raises InvalidIndex or InvalidScalar for the first
+        matrix that fails and, within it, the lowest failing entry, as the reference's loops return."""
+        what = "Instance::from_entries"
+        buf, n = _byte_buffer(vals, what)
+        nnz = [int(x) for x in nnz]
+        if len(nnz) != 3 or sum(nnz) != n or len(rows) < n or len(cols) < n:
+            raise SpartanHipError(f"{what}: {nnz} entries announced, {len(rows)} rows, {len(cols)} columns and {n} values given")
+        st, mat, rep = ctypes.c_int32(), ctypes.c_int(), (ctypes.c_uint64 * 4)()
+        h = H.spz_instance_from_entries(ctx.h, sz(num_cons), sz(num_vars), sz(num_inputs), (sz * 3)(*nnz), rows, cols, buf, ctypes.byref(st),
+                                        ctypes.byref(mat), rep)
+        _entries_result(h, st, mat, rep, what)
+        return Instance(vp(h), num_cons, num_vars, num_inputs)
+
+    @staticmethod
+    def from_tensors(ctx, num_cons, num_vars, num_inputs, A, B, C):
+        """The same from entry lists already on the context's GPU: each of A, B, C is (rows, cols, vals) with rows and cols torch.int64 tensors
+        of n elements, READ AS UNSIGNED (a negative value is an InvalidIndex), and vals a torch.uint8 tensor of 32 n elements; all contiguous,
+        views at any offset allowed, n = 0 allowed. Nothing visits host memory. THE CALLER SYNCHRONISES the stream that wrote the tensors
+        before the call (torch.cuda.synchronize(), or a synchronize of that stream): the library copies on its own stream, which is not
+        ordered against torch's. Raises InvalidIndex / InvalidScalar like from_entries."""
+        import torch
+        from .capi import lib
+        what = "Instance::from_tensors"
+        dev = int(lib.sp_ctx_device(ctx.raw()))
+        nnz, ptrs = [], ([], [], [])
+        for name, m in zip("ABC", (A, B, C)):
+            if len(m) != 3:
+                raise SpartanHipError(f"{what}: matrix {name} is not (rows, cols, vals)")
+            r, c, v = m
+            for t, dt in ((r, torch.int64), (c, torch.int64), (v, torch.uint8)):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or t.device.index != dev or not t.is_contiguous():
+                    raise SpartanHipError(f"{what}: matrix {name} needs contiguous torch.int64 rows and cols and torch.uint8 vals on device {dev}")
+            n = r.numel()
+            if c.numel() != n or v.numel() != 32 * n:
+                raise SpartanHipError(f"{what}: matrix {name} has {n} rows, {c.numel()} cols and {v.numel()} value bytes")
+            nnz.append(n)
+            for lst, t in zip(ptrs, (r, c, v)):
+                lst.append(t.data_ptr() if n else None)
+        st, mat, rep = ctypes.c_int32(), ctypes.c_int(), (ctypes.c_uint64 * 4)()
+        h = H.spz_instance_from_device_entries(ctx.h, sz(num_cons), sz(num_vars), sz(num_inputs), (sz * 3)(*nnz), (vp * 3)(*ptrs[0]), (vp * 3)(*ptrs[1]),
+                                               (vp * 3)(*ptrs[2]), ctypes.byref(st), ctypes.byref(mat), rep)
+        _entries_result(h, st, mat, rep, what)
+        return Instance(vp(h), num_cons, num_vars, num_inputs)
 
     @staticmethod
     def produce_synthetic_r1cs(ctx, num_cons, num_vars, num_inputs, seed=0):
@@ -449,11 +499,30 @@ class NIZK:
 
 
 class InvalidScalar(SpartanHipError):
-    """R1CSError::InvalidScalar (lib.rs:75-79): a 32-byte string of an assignment is not a canonical scalar (its value is >= q).
-    .first = the lowest index of such an entry, .count = how many there are."""
-    def __init__(self, what, first, count):
+    """R1CSError::InvalidScalar (lib.rs:75-79, 184-186): a 32-byte string of an assignment or of a matrix entry is not a canonical scalar (its
+    value is >= q). .first = the lowest index of such an entry, .count = how many there are; from Instance.from_entries / from_tensors also
+    .matrix = 0, 1, 2 for A, B, C (None for an assignment), and the count is taken among the entries whose index is good."""
+    def __init__(self, what, first, count, matrix=None):
         super().__init__(f"{what} failed: {H.spz_last_error().decode()}")
-        self.first, self.count = first, count
+        self.first, self.count, self.matrix = first, count, matrix
+
+
+class InvalidIndex(SpartanHipError):
+    """R1CSError::InvalidIndex (lib.rs:164-172) from Instance.from_entries / from_tensors: an entry names a row >= num_cons or a column >=
+    num_vars + 1 + num_inputs. .matrix = 0, 1, 2 for A, B, C, .first = the lowest such entry of that matrix, .count = how many it has."""
+    def __init__(self, what, first, count, matrix):
+        super().__init__(f"{what} failed: {H.spz_last_error().decode()}")
+        self.first, self.count, self.matrix = first, count, matrix
+
+
+def _entries_result(h, st, mat, rep, what):
+    if h:
+        return
+    if st.value == -6:    # SP_EINDEX
+        raise InvalidIndex(what, int(rep[1]), int(rep[0]), int(mat.value))
+    if st.value == -5:    # SP_ESCALAR
+        raise InvalidScalar(what, int(rep[3]), int(rep[2]), int(mat.value))
+    raise SpartanHipError(f"{what} failed: {H.spz_last_error().decode()}")
 
 
 def _byte_buffer(data, what):
