@@ -32,7 +32,6 @@ def entry_list(rng, nc, nv, ni, per_row=3):
 
 def shape_bincode(inst):
     H = P.H
-    H.spz_instance_shape_bincode.restype = sz
     n = H.spz_instance_shape_bincode(inst.h, None, sz(0))
     buf = (ctypes.c_uint8 * n)()
     H.spz_instance_shape_bincode(inst.h, buf, sz(n))

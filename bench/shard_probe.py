@@ -16,7 +16,6 @@ from tests.helpers import mont_bulk, fast_scalars, sz, vp, Q
 s = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 out = {}
 ctx = P.Ctx(0)
-P.H.spz_rccl_allgather_probe.restype = ctypes.c_double
 ctx.set_commit_shard_rccl(0, 1, P.rccl_unique_id())
 out["rccl_1rank_exchange_us"] = {str(b): round(P.H.spz_rccl_allgather_probe(ctx.h, sz(b), ctypes.c_int(2000)), 2) for b in (96, 4096, 65536)}
 ctx.set_commit_shard_virtual(1)

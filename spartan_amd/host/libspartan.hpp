@@ -18,7 +18,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/spartan_hip.h"
+#include "../../include/spartan_host.h"  // the driver's C boundary; brings spartan_hip.h
 #include "transcript.hpp"
 
 namespace spz {
@@ -64,7 +64,7 @@ void cubic_coeffs_probe(const Fq S[12], const Fq& r, Fq ev[3]);                 
 void cubic_tail_probe(FqVec& tab, size_t ni, size_t m, const FqVec& coeffs, const FqVec& challenges, FqVec* evs);  // test hook (spark.inc)
 bool eq_factor_probe(const FqVec& rho, size_t np, size_t ni, const FqVec& coeffs, const FqVec& claims, const FqVec& ev4, const FqVec& challenges, FqVec* evc_out,
                      FqVec* K_out);  // test hook (spark.inc)
-typedef int (*CommitGatherFn)(void* user, uint8_t* buf, size_t total, size_t off, size_t len);
+typedef spz_commit_gather_fn CommitGatherFn;  // spartan_host.h
 void set_commit_shard(Ctx& c, int rank, int world, CommitGatherFn gather, void* user);
 void rccl_unique_id(uint8_t out[128]);
 void set_commit_shard_rccl(Ctx& c, int rank, int world, const uint8_t unique_id[128]);
@@ -274,6 +274,14 @@ struct InvalidIndex : Error {
 // Assignment::new for inputs and other short vectors, on the calling thread: the same check, the same exception. scalars_to_bytes is
 // Scalar::to_bytes of each.
 FqVec scalars_from_bytes(const uint8_t* bytes, size_t n);
+// Scalar::from_bytes (ristretto255.rs:390-416) accepts 32 little-endian bytes, read as four limbs, only when their value is below q: the
+// host side's one statement of that test, from the top limb down
+inline bool limbs_below_q(const uint64_t l[4]) {
+  static const uint64_t Q[4] = {SP_Q0, SP_Q1, SP_Q2, SP_Q3};
+  for (int w = 3; w >= 0; w--)
+    if (l[w] != Q[w]) return l[w] < Q[w];
+  return false;
+}
 std::vector<uint8_t> scalars_to_bytes(const Fq* s, size_t n);
 // TEST/BENCH ONLY: from_bytes_wide(SHAKE256(domain || LE64(seed))[0..64]), the documented seed -> scalar map behind the
 // reproducible RandomTape seeds of tests/ and bench.py. 64 bits of entropy: never a production tape seed.

@@ -1277,16 +1277,12 @@ std::vector<uint8_t> VarsAssignment::to_bytes() const {
 }
 FqVec scalars_from_bytes(const uint8_t* bytes, size_t n) {
   REQUIRE(bytes || n == 0);
-  static const uint64_t Q[4] = {SP_Q0, SP_Q1, SP_Q2, SP_Q3};
   FqVec v(n);
   uint64_t first = UINT64_MAX, count = 0;
   for (size_t i = 0; i < n; i++) {
     Fq raw;
     memcpy(raw.l, bytes + 32 * i, 32);  // little-endian host: the bytes are the limbs
-    bool lt = false;                    // Scalar::from_bytes (ristretto255.rs:390-416): below q, from the top limb down
-    for (int w = 3; w >= 0; w--)
-      if (raw.l[w] != Q[w]) { lt = raw.l[w] < Q[w]; break; }
-    if (!lt) {
+    if (!limbs_below_q(raw.l)) {
       if (!count++) first = i;
       continue;
     }

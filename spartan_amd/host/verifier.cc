@@ -594,11 +594,7 @@ struct Rd {
     if (!ok || left() < 32) { ok = false; return x; }
     for (int w = 0; w < 4; w++) { uint64_t v = 0; for (int i = 0; i < 8; i++) v |= (uint64_t)p[o + 8 * w + i] << (8 * i); x.l[w] = v; }
     o += 32;
-    static const uint64_t Q[4] = {SP_Q0, SP_Q1, SP_Q2, SP_Q3};
-    bool lt = false;  // limbs >= q are not a Scalar
-    for (int w = 3; w >= 0; w--)
-      if (x.l[w] != Q[w]) { lt = x.l[w] < Q[w]; break; }
-    if (!lt) { ok = false; return fq_zero(); }
+    if (!limbs_below_q(x.l)) { ok = false; return fq_zero(); }  // limbs >= q are not a Scalar
     return x;
   }
   CP cp() {

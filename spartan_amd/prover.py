@@ -9,36 +9,101 @@ if not os.path.exists(HOST_PATH):
     raise SpartanHipError(f"{HOST_PATH} not built: run __graft_entry__.build()")
 ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
 H = ctypes.CDLL(HOST_PATH)
-for f in ("spz_ctx_new", "spz_instance_new", "spz_instance_synthetic", "spz_snark_gens_new", "spz_nizk_gens_new", "spz_snark_encode",
-          "spz_snark_prove", "spz_nizk_prove", "spz_ctx_raw", "spz_vars_assignment_new", "spz_snark_prove_resident", "spz_nizk_prove_resident",
-          "spz_snark_prove_t", "spz_nizk_prove_t", "spz_commitment_load", "spz_snark_verifier_gens_new", "spz_nizk_verifier_gens_new",
-          "spz_commitment_encode", "spz_vars_assignment_from_bytes", "spz_vars_assignment_from_device_bytes", "spz_instance_from_entries",
-          "spz_instance_from_device_entries"):
-    getattr(H, f).restype = vp
-for f in ("spz_proof_bytes", "spz_encode_comm", "spz_snark_gens_stream", "spz_merlin_script", "spz_snark_gens_bincode", "spz_commitment_bincode", "spz_decommitment_bincode",
-          "spz_snark_gens_resident_bytes", "spz_nizk_gens_resident_bytes", "spz_snark_gens_table_bytes", "spz_commitment_serialize",
-          "spz_commitment_resident_bytes", "spz_vars_assignment_len"):
-    getattr(H, f).restype = sz
-H.spz_last_error.restype = ctypes.c_char_p
-for f in ("spz_nizk_parse_probe", "spz_snark_reserialize", "spz_commitment_reserialize"):
-    getattr(H, f).restype = ctypes.c_longlong
-for f in ("spz_ctx_free", "spz_instance_free", "spz_snark_gens_free", "spz_nizk_gens_free", "spz_encode_free", "spz_proof_free", "spz_vars_assignment_free",
-          "spz_commitment_free"):
-    getattr(H, f).argtypes = [vp]
+_i, _u64, _s, _ll = ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_longlong
+_INST = [vp, sz, sz, sz, vp, vp, vp, vp]          # ctx, num_cons, num_vars, num_inputs, nnz, rows, cols, vals
+_BYTES = [vp, sz]                                 # out, cap of the size-then-fill idiom
+_TAIL = [vp, vp]                                  # tape_seed, times10
+_VERIFY = [vp, vp, vp, vp, sz, vp, sz]            # ctx, comm | inst, gens, proof, proof_len, inputs, n_inputs
+_MANY = [vp, vp, vp, vp, vp, vp, sz, sz, _s, vp]  # ctx, comm | inst, gens, proofs, proof_lens, inputs, n_inputs, K, label, status_out
+_SCRIPT = [_s, sz, vp, vp, vp, vp, vp]            # tlabel, nops, kinds, labels, datas, lens, out
+# name -> (restype, argtypes) of every entry point include/spartan_host.h declares (tests/test_host_abi.py compares the two): every pointer is
+# c_void_p (None, bytes, ctypes arrays, byref(), addresses and callbacks all pass), except the labels, which are c_char_p
+SIGNATURES = {
+    "spz_last_error": (_s, []),
+    "spz_ctx_new": (vp, [_i]), "spz_ctx_free": (None, [vp]), "spz_ctx_raw": (vp, [vp]), "spz_ctx_set_option": (_i, [vp, _s, _s]),
+    "spz_keccak_variant": (_s, []),
+    "spz_ctx_set_commit_shard": (_i, [vp, _i, _i, vp, vp]), "spz_rccl_unique_id": (_i, [vp]),
+    "spz_ctx_set_commit_shard_rccl": (_i, [vp, _i, _i, vp]), "spz_ctx_set_commit_shard_virtual": (_i, [vp, _i]),
+    "spz_ctx_shard_stats": (None, [vp, _i, vp]),
+    "spz_instance_new": (vp, _INST), "spz_instance_from_entries": (vp, _INST + [vp, vp, vp]),
+    "spz_instance_from_device_entries": (vp, _INST + [vp, vp, vp]), "spz_instance_synthetic": (vp, [vp, sz, sz, sz, _u64, vp, vp]),
+    "spz_instance_free": (None, [vp]), "spz_instance_digest": (sz, [vp] + _BYTES), "spz_instance_set_digest": (None, [vp, vp, sz]),
+    "spz_instance_set_digest_header": (_i, [vp, _i]), "spz_instance_is_sat": (_i, [vp, vp, vp, sz, vp, sz, vp, vp, sz]),
+    "spz_snark_gens_new": (vp, [vp, sz, sz, sz, sz]), "spz_nizk_gens_new": (vp, [vp, sz, sz, sz]),
+    "spz_snark_verifier_gens_new": (vp, [vp, sz, sz, sz, sz]), "spz_nizk_verifier_gens_new": (vp, [vp, sz, sz, sz]),
+    "spz_snark_gens_is_verifier_only": (_i, [vp]), "spz_nizk_gens_is_verifier_only": (_i, [vp]),
+    "spz_snark_gens_resident_bytes": (sz, [vp]), "spz_nizk_gens_resident_bytes": (sz, [vp]),
+    "spz_snark_gens_free": (None, [vp]), "spz_nizk_gens_free": (None, [vp]), "spz_snark_gens_stream": (sz, [vp, _i] + _BYTES),
+    "spz_snark_gens_window_bits": (_i, [vp, _i]), "spz_snark_gens_windows": (_i, [vp, _i]), "spz_snark_gens_table_bytes": (sz, [vp, _i]),
+    "spz_snark_gens_bincode": (sz, [vp] + _BYTES),
+    "spz_snark_encode": (vp, [vp, vp, vp]), "spz_encode_free": (None, [vp]), "spz_commitment_bincode": (sz, [vp] + _BYTES),
+    "spz_decommitment_bincode": (sz, [vp] + _BYTES), "spz_encode_comm": (sz, [vp, _i] + _BYTES),
+    "spz_commitment_load": (vp, [vp, vp, sz]), "spz_commitment_encode": (vp, [vp, vp, vp]), "spz_commitment_serialize": (sz, [vp] + _BYTES),
+    "spz_commitment_resident_bytes": (sz, [vp]), "spz_commitment_free": (None, [vp]),
+    "spz_vars_assignment_new": (vp, [vp, vp, sz]), "spz_vars_assignment_free": (None, [vp]),
+    "spz_vars_assignment_from_bytes": (vp, [vp, vp, sz, vp]), "spz_vars_assignment_from_device_bytes": (vp, [vp, vp, sz, vp]),
+    "spz_vars_assignment_len": (sz, [vp]), "spz_vars_assignment_to_bytes": (_i, [vp, vp]), "spz_vars_assignment_check_reduced": (_i, [vp, vp]),
+    "spz_scalars_from_bytes": (_i, [vp, sz, vp, vp]), "spz_scalars_to_bytes": (_i, [vp, sz, vp]),
+    "spz_snark_prove": (vp, [vp, vp, vp, vp, vp, sz, vp, sz, _s] + _TAIL),
+    "spz_snark_prove_resident": (vp, [vp, vp, vp, vp, vp, vp, sz, _s] + _TAIL),
+    "spz_snark_prove_t": (vp, [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp] + _TAIL),
+    "spz_nizk_prove": (vp, [vp, vp, vp, vp, sz, vp, sz, _s] + _TAIL),
+    "spz_nizk_prove_resident": (vp, [vp, vp, vp, vp, vp, sz, _s] + _TAIL),
+    "spz_nizk_prove_t": (vp, [vp, vp, vp, vp, vp, sz, vp, sz, vp] + _TAIL),
+    "spz_proof_bytes": (sz, [vp] + _BYTES), "spz_proof_free": (None, [vp]), "spz_transcript_probe": (None, [vp, vp]),
+    "spz_snark_verify": (_i, _VERIFY + [_s]), "spz_snark_verify_t": (_i, _VERIFY + [vp]),
+    "spz_nizk_verify": (_i, _VERIFY + [_s]), "spz_nizk_verify_t": (_i, _VERIFY + [vp]),
+    "spz_snark_verify_many": (_i, _MANY), "spz_nizk_verify_many": (_i, _MANY),
+    # test hooks
+    "spz_snark_reserialize": (_ll, [vp, sz] + _BYTES), "spz_nizk_parse_probe": (_ll, [vp, sz] + _BYTES),
+    "spz_commitment_reserialize": (_ll, [vp, sz] + _BYTES), "spz_instance_shape_bincode": (sz, [vp] + _BYTES),
+    "spz_zlib_level6": (sz, [vp, sz, _i] + _BYTES), "spz_zlib_probes": (sz, [vp, sz, ctypes.c_uint, _i] + _BYTES),
+    "spz_keccak_run_variant": (_i, [_s, vp]), "spz_shake256": (None, [vp, sz, vp, sz]),
+    "spz_merlin_script": (sz, _SCRIPT), "spz_merlin_state": (None, _SCRIPT), "spz_merlin_challenge_from_state": (None, [vp, _s, vp, sz]),
+    "spz_tape_draws": (None, [vp, _s, sz, vp]), "spz_seed_scalar": (None, [_s, _u64, vp]),
+    "spz_fq_invert_vartime": (None, [vp, vp]), "spz_unipoly_probe": (_i, [vp, sz, vp, vp, vp, vp]),
+    "spz_cubic_coeffs_probe": (None, [vp, vp, vp]), "spz_cubic_tail_probe": (_i, [vp, sz, sz, vp, vp, vp]),
+    "spz_eq_factor_probe": (_i, [vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp]),
+    "spz_rccl_allgather_probe": (ctypes.c_double, [vp, sz, _i]),
+}
+for _name, (_res, _args) in SIGNATURES.items():
+    _f = getattr(H, _name)
+    _f.restype, _f.argtypes = _res, _args
 u64p = ctypes.POINTER(ctypes.c_uint64)
 TIME_NAMES = ["polycommit", "prove_sc_phase_one", "prove_sc_phase_two", "polyeval", "R1CSProof::prove", "eval_sparse_polys",
               "commit_nondet_witness", "build_layered_network", "evalproof_layered_network", "total"]
 
 
+def _failed(what):
+    return f"{what} failed: {H.spz_last_error().decode()}"
+
+
 def _chk(h, what):
     if not h:
-        raise SpartanHipError(f"{what} failed: {H.spz_last_error().decode()}")
+        raise SpartanHipError(_failed(what))
     return vp(h)
+
+
+def _fill(fn, *head, unit=1):
+    """the size-then-fill idiom of spartan_host.h: ask for the size (in units of `unit` bytes), then for the bytes"""
+    n = unit * fn(*head, None, 0)
+    b = (ctypes.c_uint8 * n)()
+    fn(*head, b, n)
+    return bytes(b)
+
+
+def _limbs_or_handle(vars_):
+    """(assignment, vars, nvars) as the entries that take either take them: a VarsAssignment, or Montgomery limbs read in place"""
+    return (vars_.h, None, 0) if isinstance(vars_, VarsAssignment) else (None, vars_, len(vars_) // 4)
+
+
+def _n_inputs(inst, inputs):
+    return inst.num_inputs if inputs is inst.inputs else len(inputs) // 4   # the instance's own buffer holds one element when num_inputs is 0
 
 
 class Ctx:
     def __init__(self, device=0):
-        self.h = _chk(H.spz_ctx_new(ctypes.c_int(device)), "spz_ctx_new")
+        self.h = _chk(H.spz_ctx_new(device), "spz_ctx_new")
 
     def raw(self):
         """the underlying sp_ctx* (for profiling calls through spartan_amd.capi.lib)"""
@@ -55,26 +120,26 @@ class Ctx:
         (spartan_amd/shard.py; gloo in the CPU tests); None clears it. All ranks must then run identical prove() calls in lock-step."""
         from . import shard
         if dist is None or dist.get_world_size() == 1:
-            H.spz_ctx_set_commit_shard(self.h, ctypes.c_int(0), ctypes.c_int(1), None, None); self._gather = None
+            H.spz_ctx_set_commit_shard(self.h, 0, 1, None, None); self._gather = None
             return
         self._gather = shard.make_gather_callback(dist, device)
-        if H.spz_ctx_set_commit_shard(self.h, ctypes.c_int(dist.get_rank()), ctypes.c_int(dist.get_world_size()), self._gather, None) != 0:
+        if H.spz_ctx_set_commit_shard(self.h, dist.get_rank(), dist.get_world_size(), self._gather, None) != 0:
             raise SpartanHipError(f"set_commit_shard: {H.spz_last_error().decode()}")
 
     def set_commit_shard_rccl(self, rank, world, unique_id):
         """the same with RCCL inside the library: `unique_id` = the 128 bytes rank 0 got from rccl_unique_id(), handed to
         every rank by the caller (bench.py: one torch.distributed broadcast); ncclAllGather on device buffers per commit"""
-        if H.spz_ctx_set_commit_shard_rccl(self.h, ctypes.c_int(rank), ctypes.c_int(world), unique_id) != 0:
+        if H.spz_ctx_set_commit_shard_rccl(self.h, rank, world, unique_id) != 0:
             raise SpartanHipError(f"set_commit_shard_rccl: {H.spz_last_error().decode()}")
 
     def set_commit_shard_virtual(self, nshards):
         """nshards row shards on this one GPU (sub-contexts with their own streams, in-process gather); <= 1 clears it"""
-        if H.spz_ctx_set_commit_shard_virtual(self.h, ctypes.c_int(nshards)) != 0:
+        if H.spz_ctx_set_commit_shard_virtual(self.h, nshards) != 0:
             raise SpartanHipError(f"set_commit_shard_virtual: {H.spz_last_error().decode()}")
 
     def shard_stats(self, reset=False):
         out = (ctypes.c_uint64 * 2)()
-        H.spz_ctx_shard_stats(self.h, ctypes.c_int(1 if reset else 0), out)
+        H.spz_ctx_shard_stats(self.h, 1 if reset else 0, out)
         return {"gathers": int(out[0]), "bytes": int(out[1])}
 
     def close(self):
@@ -152,15 +217,11 @@ class Instance:
 
     def digest(self):
         """R1CSShapeDigest (src/r1cs.rs:154-158): the bytes set with set_digest, else computed by the host library (zlib level 6 of bincode(shape))"""
-        H.spz_instance_digest.restype = sz
-        n = H.spz_instance_digest(self.h, None, sz(0))
-        buf = (ctypes.c_uint8 * n)()
-        H.spz_instance_digest(self.h, buf, sz(n))
-        return bytes(buf)
+        return _fill(H.spz_instance_digest, self.h)
 
     def set_digest_header(self, old_header):
         """zlib header variant of the computed digest: False = 0x78 0x9C (miniz >= 2.2, miniz_oxide >= 0.4), True = 0x78 0x01"""
-        if H.spz_instance_set_digest_header(self.h, ctypes.c_int(1 if old_header else 0)) != 0:
+        if H.spz_instance_set_digest_header(self.h, 1 if old_header else 0) != 0:
             raise SpartanHipError("set_digest_header: " + H.spz_last_error().decode())
 
     def check(self, vars_, inputs, max_rows=16):
@@ -168,14 +229,11 @@ class Instance:
         .first_row = the smallest of them (None when satisfied), .rows = the lowest max_rows of them, ascending. vars_: Montgomery limbs
         (a ctypes uint64 array; fewer than num_vars are zero-padded) or a VarsAssignment. Raises SpartanHipError("InvalidNumberOfInputs")
         where the reference returns that R1CSError: too many variables, or a number of inputs other than num_inputs."""
-        res = isinstance(vars_, VarsAssignment)
         rep = (ctypes.c_uint64 * 2)()
         rows = (ctypes.c_uint64 * max(max_rows, 1))()
-        n_in = self.num_inputs if inputs is self.inputs else len(inputs) // 4   # the instance's own buffer holds one element when num_inputs is 0
-        rc = H.spz_instance_is_sat(self.h, vars_.h if res else None, None if res else vars_, sz(0 if res else len(vars_) // 4), inputs,
-                                   sz(n_in), rep, rows if max_rows > 0 else None, sz(max_rows))
+        rc = H.spz_instance_is_sat(self.h, *_limbs_or_handle(vars_), inputs, _n_inputs(self, inputs), rep, rows if max_rows > 0 else None, max_rows)
         if rc < 0:
-            raise SpartanHipError(f"Instance::is_sat failed: {H.spz_last_error().decode()}")
+            raise SpartanHipError(_failed("Instance::is_sat"))
         violated = int(rep[0])
         return SatReport(violated, int(rep[1]) if violated else None, [int(r) for r in rows[:min(violated, max_rows)]])
 
@@ -221,32 +279,27 @@ class SNARKGens:
         return int(H.spz_snark_gens_resident_bytes(self.h))
 
     def stream(self, which):
-        n = H.spz_snark_gens_stream(self.h, ctypes.c_int(which), None, sz(0))
-        b = (ctypes.c_uint8 * n)()
-        H.spz_snark_gens_stream(self.h, ctypes.c_int(which), b, sz(n))
-        return bytes(b)
+        return _fill(H.spz_snark_gens_stream, self.h, which)
 
     def window_bits(self, which):
         """signed window width of the fixed-base tables of generator stream `which` (0: gens_r1cs_sat, 1: gens_r1cs_eval)"""
-        return self._tables(H.spz_snark_gens_window_bits(self.h, ctypes.c_int(which)), "window_bits")
+        return self._tables(H.spz_snark_gens_window_bits(self.h, which), "window_bits")
 
     def _tables(self, value, what):
         if int(value) <= 0 and self.is_verifier_only:
-            raise SpartanHipError(f"SNARKGens::{what} failed: {H.spz_last_error().decode()}")
+            raise SpartanHipError(_failed(f"SNARKGens::{what}"))
         return int(value)
 
     def windows(self, which):
         """windows per scalar (= mixed additions per committed scalar) of the tables of generator stream `which`"""
-        return self._tables(H.spz_snark_gens_windows(self.h, ctypes.c_int(which)), "windows")
+        return self._tables(H.spz_snark_gens_windows(self.h, which), "windows")
 
     def table_bytes(self, which):
         """HBM held by the window tables of generator stream `which`"""
-        return self._tables(H.spz_snark_gens_table_bytes(self.h, ctypes.c_int(which)), "table_bytes")
+        return self._tables(H.spz_snark_gens_table_bytes(self.h, which), "table_bytes")
 
     def serialize(self):
-        n = H.spz_snark_gens_bincode(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
-        H.spz_snark_gens_bincode(self.h, b, sz(n))
-        return bytes(b)
+        return _fill(H.spz_snark_gens_bincode, self.h)
 
     def free(self):
         if self.h:
@@ -288,7 +341,6 @@ def rccl_unique_id():
 
 def keccak_variant():
     """which form of Keccak-f[1600] the host driver picked for this CPU (keccak.cc): plain | bmi2 | avx512"""
-    H.spz_keccak_variant.restype = ctypes.c_char_p
     return H.spz_keccak_variant().decode()
 
 
@@ -297,16 +349,51 @@ def seed_scalar(domain, seed):
     proof passes tape_seed=None (the tape is then seeded from OS entropy, like RandomTape::new, random.rs:13-15): a known or
     reused seed fixes every blind of the proof and gives up zero-knowledge."""
     out = (ctypes.c_uint64 * 4)()
-    H.spz_seed_scalar(domain, ctypes.c_uint64(seed), out)
+    H.spz_seed_scalar(domain, seed, out)
     return out
 
 
-def _proof_bytes(p):
-    n = H.spz_proof_bytes(p, None, sz(0))
-    b = (ctypes.c_uint8 * n)()
-    H.spz_proof_bytes(p, b, sz(n))
+def _prove(what, entry, head, inst, vars_, inputs, transcript, tape_seed, times=None):
+    """one proof. entry = (the entry for host limbs, the one for a VarsAssignment) of a proof on a fresh transcript, `transcript` its label; or
+    the one *_prove_t entry, which takes either assignment, `transcript` the caller's state. head = the handles in front of the assignment."""
+    tm = (ctypes.c_double * 10)()
+    if not isinstance(entry, tuple):
+        vars_args = _limbs_or_handle(vars_)
+    elif isinstance(vars_, VarsAssignment):
+        entry, vars_args = entry[1], (vars_.h,)
+    else:
+        entry, vars_args = entry[0], (vars_, len(vars_) // 4)
+    p = _chk(entry(*head, *vars_args, inputs, inst.num_inputs, transcript, tape_seed, tm), what)
+    if times is not None:
+        times.update(dict(zip(TIME_NAMES, list(tm))))
+    b = _fill(H.spz_proof_bytes, p)
     H.spz_proof_free(p)
-    return bytes(b)
+    return b
+
+
+def _verify_many(who, fn, ctx, subject, proofs, inputs, gens, transcript_label, count):
+    """the body of SNARK.verify_many and NIZK.verify_many: subject = the Commitment / the Instance, count(buffer) = its number of inputs"""
+    K = len(proofs)
+    per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * K
+    if len(per) != K:
+        raise SpartanHipError(f"{who}::verify_many failed: one inputs buffer per proof")
+    sizes = {count(x) for x in per}
+    if len(sizes) > 1:
+        raise SpartanHipError(f"{who}::verify_many failed: InvalidNumberOfInputs")
+    keep = [ctypes.create_string_buffer(bytes(p), max(len(p), 1)) for p in proofs]
+    pa = (vp * K)(*[ctypes.cast(b, vp) for b in keep])
+    la = (sz * K)(*[len(p) for p in proofs])
+    ia = (vp * K)(*[ctypes.cast(x, vp) for x in per])
+    st = (ctypes.c_int * K)()
+    if fn(ctx.h, subject.h, gens.h, pa, la, ia, sizes.pop() if K else 0, K, transcript_label, st) != 0:
+        raise SpartanHipError(_failed(f"{who}::verify_many"))
+    return [int(x) for x in st]
+
+
+def _verdict(rc, what):
+    if rc < -1:
+        raise SpartanHipError(_failed(what))
+    return int(rc)
 
 
 class SNARK:
@@ -317,39 +404,23 @@ class SNARK:
     @staticmethod
     def prove(ctx, inst, enc, vars_, inputs, gens, transcript_label, tape_seed, times=None):
         """vars_: the assignment as Montgomery limbs (a ctypes uint64 array, read in place) or a VarsAssignment (already in HBM)"""
-        tm = (ctypes.c_double * 10)()
-        if isinstance(vars_, VarsAssignment):
-            p = _chk(H.spz_snark_prove_resident(ctx.h, inst.h, gens.h, enc.h, vars_.h, inputs, sz(inst.num_inputs), transcript_label, tape_seed, tm),
-                     "SNARK::prove")
-        else:
-            p = _chk(H.spz_snark_prove(ctx.h, inst.h, gens.h, enc.h, vars_, sz(len(vars_) // 4), inputs, sz(inst.num_inputs), transcript_label,
-                                       tape_seed, tm), "SNARK::prove")
-        if times is not None:
-            times.update(dict(zip(TIME_NAMES, list(tm))))
-        return _proof_bytes(p)
-
+        return _prove("SNARK::prove", (H.spz_snark_prove, H.spz_snark_prove_resident), (ctx.h, inst.h, gens.h, enc.h), inst, vars_, inputs,
+                      transcript_label, tape_seed, times)
 
     @staticmethod
     def prove_t(ctx, inst, enc, vars_, inputs, gens, transcript_state, tape_seed):
         """SNARK::prove on a caller-owned transcript (lib.rs:339-347): `transcript_state` is a 203-byte ctypes array holding the
         merlin transcript (Strobe128 state, pos, pos_begin, cur_flags); it is continued by the proof and left in the state the
         proof ends in. Returns the proof bytes."""
-        tm = (ctypes.c_double * 10)()
-        res = isinstance(vars_, VarsAssignment)
-        p = _chk(H.spz_snark_prove_t(ctx.h, inst.h, gens.h, enc.h, vars_.h if res else None, None if res else vars_, sz(0 if res else len(vars_) // 4),
-                                     inputs, sz(inst.num_inputs), transcript_state, tape_seed, tm), "SNARK::prove")
-        return _proof_bytes(p)
-
+        return _prove("SNARK::prove", H.spz_snark_prove_t, (ctx.h, inst.h, gens.h, enc.h), inst, vars_, inputs, transcript_state, tape_seed)
 
     @staticmethod
     def verify_status(ctx, comm, proof_bytes, inputs, gens, transcript_label):
         """SNARK::verify (lib.rs:423-466) of untrusted proof bytes against a Commitment, on the device: 1 accept, 0 reject, -1 malformed bytes.
         `inputs`: Montgomery limbs (a ctypes uint64 array). Raises SpartanHipError("InvalidNumberOfInputs") when their number is not the
         commitment's num_inputs, as NIZK.verify_status does."""
-        rc = H.spz_snark_verify(ctx.h, comm.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(len(inputs) // 4), transcript_label)
-        if rc < -1:
-            raise SpartanHipError(f"SNARK::verify failed: {H.spz_last_error().decode()}")
-        return int(rc)
+        return _verdict(H.spz_snark_verify(ctx.h, comm.h, gens.h, bytes(proof_bytes), len(proof_bytes), inputs, len(inputs) // 4, transcript_label),
+                        "SNARK::verify")
 
     @staticmethod
     def verify(ctx, comm, proof_bytes, inputs, gens, transcript_label):
@@ -363,31 +434,14 @@ class SNARK:
         but the K verifications share their device round trips (8 for up to 64 proofs). `inputs`: one buffer of Montgomery limbs (a ctypes
         uint64 array) shared by all proofs, or a list with one buffer per proof. Raises SpartanHipError("InvalidNumberOfInputs") when a buffer's
         size is not the commitment's num_inputs, and for a device failure; no verdicts then."""
-        K = len(proofs)
-        per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * K
-        if len(per) != K:
-            raise SpartanHipError("SNARK::verify_many failed: one inputs buffer per proof")
-        if len({len(x) for x in per}) > 1:
-            raise SpartanHipError("SNARK::verify_many failed: InvalidNumberOfInputs")
-        n_in = len(per[0]) // 4 if K else 0
-        keep = [ctypes.create_string_buffer(bytes(p), max(len(p), 1)) for p in proofs]
-        pa = (vp * K)(*[ctypes.cast(b, vp) for b in keep])
-        la = (sz * K)(*[len(p) for p in proofs])
-        ia = (vp * K)(*[ctypes.cast(x, vp) for x in per])
-        st = (ctypes.c_int * K)()
-        rc = H.spz_snark_verify_many(ctx.h, comm.h, gens.h, pa, la, ia, sz(n_in), sz(K), transcript_label, st)
-        if rc != 0:
-            raise SpartanHipError(f"SNARK::verify_many failed: {H.spz_last_error().decode()}")
-        return [int(x) for x in st]
+        return _verify_many("SNARK", H.spz_snark_verify_many, ctx, comm, proofs, inputs, gens, transcript_label, lambda x: len(x) // 4)
 
     @staticmethod
     def verify_t(ctx, comm, proof_bytes, inputs, gens, transcript_state):
         """SNARK::verify on a caller-owned transcript: the 203-byte state (see prove_t) is continued by the verification and left in the state
         it ends in — after an accepted proof, the state SNARK.prove_t left on the prover's side. Returns the status of verify_status."""
-        rc = H.spz_snark_verify_t(ctx.h, comm.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(len(inputs) // 4), transcript_state)
-        if rc < -1:
-            raise SpartanHipError(f"SNARK::verify failed: {H.spz_last_error().decode()}")
-        return int(rc)
+        return _verdict(H.spz_snark_verify_t(ctx.h, comm.h, gens.h, bytes(proof_bytes), len(proof_bytes), inputs, len(inputs) // 4, transcript_state),
+                        "SNARK::verify")
 
 
 class Commitment:
@@ -399,7 +453,7 @@ class Commitment:
     @staticmethod
     def load(ctx, comm_bytes):
         """raises SpartanHipError for bytes that are not one commitment (ComputationCommitment::deserialize, libspartan.hpp)"""
-        return Commitment(_chk(H.spz_commitment_load(ctx.h, bytes(comm_bytes), sz(len(comm_bytes))), "Commitment.load"))
+        return Commitment(_chk(H.spz_commitment_load(ctx.h, bytes(comm_bytes), len(comm_bytes)), "Commitment.load"))
 
     @staticmethod
     def encode(ctx, inst, gens):
@@ -410,9 +464,7 @@ class Commitment:
 
     def serialize(self):
         """bincode(ComputationCommitment) of the handle, however it was made"""
-        n = H.spz_commitment_serialize(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
-        H.spz_commitment_serialize(self.h, b, sz(n))
-        return bytes(b)
+        return _fill(H.spz_commitment_serialize, self.h)
 
     def resident_bytes(self):
         """HBM held by the two share vectors as resident point sets: 65536 bytes a share"""
@@ -427,22 +479,15 @@ class NIZK:
     @staticmethod
     def prove_t(ctx, inst, vars_, inputs, gens, transcript_state, tape_seed):
         """NIZK::prove on a caller-owned transcript (lib.rs:501-509); see SNARK.prove_t"""
-        tm = (ctypes.c_double * 10)()
-        res = isinstance(vars_, VarsAssignment)
-        p = _chk(H.spz_nizk_prove_t(ctx.h, inst.h, gens.h, vars_.h if res else None, None if res else vars_, sz(0 if res else len(vars_) // 4),
-                                    inputs, sz(inst.num_inputs), transcript_state, tape_seed, tm), "NIZK::prove")
-        return _proof_bytes(p)
+        return _prove("NIZK::prove", H.spz_nizk_prove_t, (ctx.h, inst.h, gens.h), inst, vars_, inputs, transcript_state, tape_seed)
 
     @staticmethod
     def verify_status(ctx, inst, proof_bytes, inputs, gens, transcript_label):
         """NIZK::verify (lib.rs:549-587) of untrusted proof bytes on the device: 1 accept, 0 reject, -1 malformed bytes. `inputs`: Montgomery limbs
         (a ctypes uint64 array) or the instance's own. Raises SpartanHipError("InvalidNumberOfInputs") for a wrong number of inputs, as
         Instance.is_sat does."""
-        n_in = inst.num_inputs if inputs is inst.inputs else len(inputs) // 4
-        rc = H.spz_nizk_verify(ctx.h, inst.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(n_in), transcript_label)
-        if rc < -1:
-            raise SpartanHipError(f"NIZK::verify failed: {H.spz_last_error().decode()}")
-        return int(rc)
+        return _verdict(H.spz_nizk_verify(ctx.h, inst.h, gens.h, bytes(proof_bytes), len(proof_bytes), inputs, _n_inputs(inst, inputs), transcript_label),
+                        "NIZK::verify")
 
     @staticmethod
     def verify(ctx, inst, proof_bytes, inputs, gens, transcript_label):
@@ -457,45 +502,19 @@ class NIZK:
         `inputs`: one buffer of Montgomery limbs (a ctypes uint64 array, or the instance's own) shared by all proofs, or a list with one buffer
         per proof. Raises SpartanHipError("InvalidNumberOfInputs") when a buffer's size is not the instance's num_inputs, and for a device
         failure; no verdicts then."""
-        K = len(proofs)
-        per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * K
-        if len(per) != K:
-            raise SpartanHipError("NIZK::verify_many failed: one inputs buffer per proof")
-        sizes = {inst.num_inputs if x is inst.inputs else len(x) // 4 for x in per}
-        if len(sizes) > 1:
-            raise SpartanHipError("NIZK::verify_many failed: InvalidNumberOfInputs")
-        n_in = sizes.pop() if K else 0
-        keep = [ctypes.create_string_buffer(bytes(p), max(len(p), 1)) for p in proofs]
-        pa = (vp * K)(*[ctypes.cast(b, vp) for b in keep])
-        la = (sz * K)(*[len(p) for p in proofs])
-        ia = (vp * K)(*[ctypes.cast(x, vp) for x in per])
-        st = (ctypes.c_int * K)()
-        rc = H.spz_nizk_verify_many(ctx.h, inst.h, gens.h, pa, la, ia, sz(n_in), sz(K), transcript_label, st)
-        if rc != 0:
-            raise SpartanHipError(f"NIZK::verify_many failed: {H.spz_last_error().decode()}")
-        return [int(x) for x in st]
+        return _verify_many("NIZK", H.spz_nizk_verify_many, ctx, inst, proofs, inputs, gens, transcript_label, lambda x: _n_inputs(inst, x))
 
     @staticmethod
     def verify_t(ctx, inst, proof_bytes, inputs, gens, transcript_state):
         """NIZK::verify on a caller-owned transcript: the 203-byte state (see SNARK.prove_t) is continued by the verification and left in the
         state it ends in — after an accepted proof, the state NIZK.prove_t left on the prover's side. Returns the status of verify_status."""
-        n_in = inst.num_inputs if inputs is inst.inputs else len(inputs) // 4
-        rc = H.spz_nizk_verify_t(ctx.h, inst.h, gens.h, bytes(proof_bytes), sz(len(proof_bytes)), inputs, sz(n_in), transcript_state)
-        if rc < -1:
-            raise SpartanHipError(f"NIZK::verify failed: {H.spz_last_error().decode()}")
-        return int(rc)
+        return _verdict(H.spz_nizk_verify_t(ctx.h, inst.h, gens.h, bytes(proof_bytes), len(proof_bytes), inputs, _n_inputs(inst, inputs), transcript_state),
+                        "NIZK::verify")
 
     @staticmethod
     def prove(ctx, inst, vars_, inputs, gens, transcript_label, tape_seed, times=None):
-        tm = (ctypes.c_double * 10)()
-        if isinstance(vars_, VarsAssignment):
-            p = _chk(H.spz_nizk_prove_resident(ctx.h, inst.h, gens.h, vars_.h, inputs, sz(inst.num_inputs), transcript_label, tape_seed, tm), "NIZK::prove")
-        else:
-            p = _chk(H.spz_nizk_prove(ctx.h, inst.h, gens.h, vars_, sz(len(vars_) // 4), inputs, sz(inst.num_inputs), transcript_label, tape_seed, tm),
-                     "NIZK::prove")
-        if times is not None:
-            times.update(dict(zip(TIME_NAMES, list(tm))))
-        return _proof_bytes(p)
+        return _prove("NIZK::prove", (H.spz_nizk_prove, H.spz_nizk_prove_resident), (ctx.h, inst.h, gens.h), inst, vars_, inputs, transcript_label,
+                      tape_seed, times)
 
 
 class InvalidScalar(SpartanHipError):
@@ -503,7 +522,7 @@ class InvalidScalar(SpartanHipError):
     value is >= q). .first = the lowest index of such an entry, .count = how many there are; from Instance.from_entries / from_tensors also
     .matrix = 0, 1, 2 for A, B, C (None for an assignment), and the count is taken among the entries whose index is good."""
     def __init__(self, what, first, count, matrix=None):
-        super().__init__(f"{what} failed: {H.spz_last_error().decode()}")
+        super().__init__(_failed(what))
         self.first, self.count, self.matrix = first, count, matrix
 
 
@@ -511,7 +530,7 @@ class InvalidIndex(SpartanHipError):
     """R1CSError::InvalidIndex (lib.rs:164-172) from Instance.from_entries / from_tensors: an entry names a row >= num_cons or a column >=
     num_vars + 1 + num_inputs. .matrix = 0, 1, 2 for A, B, C, .first = the lowest such entry of that matrix, .count = how many it has."""
     def __init__(self, what, first, count, matrix):
-        super().__init__(f"{what} failed: {H.spz_last_error().decode()}")
+        super().__init__(_failed(what))
         self.first, self.count, self.matrix = first, count, matrix
 
 
@@ -522,7 +541,7 @@ def _entries_result(h, st, mat, rep, what):
         raise InvalidIndex(what, int(rep[1]), int(rep[0]), int(mat.value))
     if st.value == -5:    # SP_ESCALAR
         raise InvalidScalar(what, int(rep[3]), int(rep[2]), int(mat.value))
-    raise SpartanHipError(f"{what} failed: {H.spz_last_error().decode()}")
+    raise SpartanHipError(_failed(what))
 
 
 def _byte_buffer(data, what):
@@ -542,7 +561,7 @@ def _scalar_result(ok, rep, what):
     if not ok:
         if H.spz_last_error().startswith(b"InvalidScalar"):
             raise InvalidScalar(what, int(rep[1]), int(rep[0]))
-        raise SpartanHipError(f"{what} failed: {H.spz_last_error().decode()}")
+        raise SpartanHipError(_failed(what))
 
 
 class VarsAssignment:
@@ -597,7 +616,7 @@ class VarsAssignment:
         """Scalar::to_bytes of every entry: 32 n canonical little-endian bytes"""
         out = (ctypes.c_uint8 * (32 * self.n))()
         if H.spz_vars_assignment_to_bytes(self.h, out) != 0:
-            raise SpartanHipError(f"VarsAssignment::to_bytes failed: {H.spz_last_error().decode()}")
+            raise SpartanHipError(_failed("VarsAssignment::to_bytes"))
         return bytes(out)
 
     def check_reduced(self):
@@ -605,7 +624,7 @@ class VarsAssignment:
         from bytes is reduced by construction; one made from Montgomery limbs is taken on trust, and this is the check of that trust."""
         rep = (ctypes.c_uint64 * 2)()
         if H.spz_vars_assignment_check_reduced(self.h, rep) != 0:
-            raise SpartanHipError(f"VarsAssignment::check_reduced failed: {H.spz_last_error().decode()}")
+            raise SpartanHipError(_failed("VarsAssignment::check_reduced"))
         return int(rep[0]), (int(rep[1]) if rep[0] else None)
 
     def free(self):
@@ -632,7 +651,7 @@ class InputsAssignment:
         n = len(limbs) // 4
         out = (ctypes.c_uint8 * (32 * n))()
         if H.spz_scalars_to_bytes(limbs, sz(n), out) != 0:
-            raise SpartanHipError(f"InputsAssignment::to_bytes failed: {H.spz_last_error().decode()}")
+            raise SpartanHipError(_failed("InputsAssignment::to_bytes"))
         return bytes(out)
 
 
@@ -641,24 +660,17 @@ class Encoded:
         self.h = h
 
     def comm(self, which):
-        n = H.spz_encode_comm(self.h, ctypes.c_int(which), None, sz(0))
-        b = (ctypes.c_uint8 * (32 * n))()
-        H.spz_encode_comm(self.h, ctypes.c_int(which), b, sz(32 * n))
-        return bytes(b)
+        return _fill(H.spz_encode_comm, self.h, which, unit=32)   # this one counts points
 
     def serialize_commitment(self):
-        n = H.spz_commitment_bincode(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
-        H.spz_commitment_bincode(self.h, b, sz(n))
-        return bytes(b)
+        return _fill(H.spz_commitment_bincode, self.h)
 
     def commitment(self, ctx):
         """the Commitment a verifier would load from serialize_commitment()"""
         return Commitment.load(ctx, self.serialize_commitment())
 
     def serialize_decommitment(self):
-        n = H.spz_decommitment_bincode(self.h, None, sz(0)); b = (ctypes.c_uint8 * n)()
-        H.spz_decommitment_bincode(self.h, b, sz(n))
-        return bytes(b)
+        return _fill(H.spz_decommitment_bincode, self.h)
 
     def free(self):
         if self.h:

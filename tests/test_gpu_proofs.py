@@ -145,7 +145,6 @@ def test_nizk_binds_to_the_shape_digest_it_computes(P, ctx, orc):
     import zlib
     s, seed = 8, 5
     N = 1 << s
-    P.H.spz_instance_digest.restype = sz
     inst = P.Instance.produce_synthetic_r1cs(ctx, N, N, 10, seed=seed)
     n = P.H.spz_instance_digest(inst.h, None, sz(0)); buf = (ctypes.c_uint8 * n)(); P.H.spz_instance_digest(inst.h, buf, sz(n))
     digest = bytes(buf)

@@ -23,7 +23,6 @@ def test_shake256(H):
 def test_keccak_variants_agree(H):
     """keccak.cc compiles the permutation three ways (plain, BMI2, AVX-512 planes) and picks one per CPU by timing them: every form this
     CPU can run must give the same state as the plain one, and the FIPS 202 zero-state vector."""
-    H.spz_keccak_variant.restype = ctypes.c_char_p
     assert H.spz_keccak_variant() in (b"plain", b"bmi2", b"avx512")
     rng = random.Random(3)
     St = ctypes.c_uint64 * 25
@@ -137,7 +136,6 @@ def test_coarse_binding_probe_is_the_script_it_says(H, orc):
 
 
 def _zlib6(H, data, old=0):
-    H.spz_zlib_level6.restype = sz
     cap = 2 * len(data) + 1024
     out = (ctypes.c_uint8 * cap)()
     n = H.spz_zlib_level6(data, sz(len(data)), ctypes.c_int(old), out, sz(cap))
@@ -177,7 +175,6 @@ def test_shape_digest_deflater_round_trips_and_keeps_miniz_parameters(H, orc):
 
 
 def _zlib_probes(H, data, probes, old=0):
-    H.spz_zlib_probes.restype = sz
     cap = 2 * len(data) + 1024
     out = (ctypes.c_uint8 * cap)()
     n = H.spz_zlib_probes(data, sz(len(data)), ctypes.c_uint(probes), ctypes.c_int(old), out, sz(cap))
