@@ -403,6 +403,42 @@ int32_t sp_sparse_from_entries_dev(sp_ctx* ctx, const uint64_t* dev_rows /*nnz*/
 /* The entries of a matrix in the order they were given, as it keeps them: rows and cols of nnz elements, vals of 4 * nnz Montgomery limbs
  * (an instance built on the device holds no host copy; its R1CSShape bincode is serialised from this download). */
 int32_t sp_sparse_download_entries(sp_ctx* ctx, const sp_sparse* m, uint32_t* rows /*nnz*/, uint32_t* cols /*nnz*/, uint64_t* vals /*4*nnz*/);
+/* The matrices' part of bincode(R1CSShape) (r1cs.rs:18-26, sparse_mlpoly.rs:19-38), written by the device into dev_out (memory of ctx's
+ * device, 8-byte aligned, cap bytes): for each of the `count` matrices num_vars_x, num_vars_y and its entry count as u64, then every entry
+ * in the order it was given as (row: u64, col: u64, val: 4 limbs as kept) — 24 + 48 * nnz bytes a matrix, back to back. No host copy of the
+ * entries is made. Queued on the context's stream and waited for. SP_EINVAL: a null argument, a misaligned dev_out, cap too small. */
+int32_t sp_sparse_bincode(sp_ctx* ctx, const sp_sparse* const* ms, size_t count, uint64_t num_vars_x, uint64_t num_vars_y, uint8_t* dev_out,
+                          size_t cap);
+
+/* ---- the match search of miniz's tdefl for R1CSShape::get_digest (r1cs.rs:154-158), one input position per lane (deflate_match.hip) ----
+ * The digest is the zlib stream of bincode(shape) exactly as tdefl writes it at level 6. Its parser, block decisions and Huffman coding
+ * are sequential and stay on the host (spartan_amd/host/deflate.cc); what runs here is the hash-chain search, restated per position p of
+ * the input D[0, n) (a table entry is dist | len << 16, (0, init) when nothing was found):
+ *   L[p]  low 16 bits of the greatest q < p with the same 3-byte hash as p, 0 if there is none (p + 2 < n; 0 elsewhere)
+ *   A[p]  tdefl's find_match at p starting from nothing (init = 2)
+ *   B[p]  find_match at p that has to beat A[p - 1], where A[p - 1] leaves the parser's filter as a held match; 0 elsewhere
+ * The input is searched in segments of the option digest.segment positions, in order; device scratch is about 30 bytes a position of ONE
+ * segment, whatever n is: the last position of every hash, the last 32768 links and A[p - 1] are carried from segment to segment.
+ * Positions are 64-bit (only p mod 65536 and p mod 32768 enter the arithmetic, as in tdefl's wrapping unsigned), so n may exceed 4 GiB;
+ * no test runs an input that long.
+ *   sp_deflate_open           data: n bytes in host memory (on_device == 0: copied to the device) or in the memory of ctx's device
+ *                             (on_device != 0: read in place, complete before the call and unchanged until sp_deflate_close);
+ *                             probes: tdefl's probe count, 1..4095 (level 6 = 128)
+ *   sp_deflate_segments       how many segments the input has (0 for n == 0)
+ *   sp_deflate_segment_start  queue segment s — links, both searches, the copies of L, A, B and of the segment's bytes into pinned slot
+ *                             s & 1 — and return. Segments are started in order, each once, at most two ahead of the last one waited for.
+ *   sp_deflate_segment_wait   wait for segment s: its first position and count, and pointers into the pinned slot (bytes: D[first,
+ *                             min(n, first + count + 258)), any of them may be NULL), valid until segment s + 2 is started. ms (may be
+ *                             NULL; 4) receives the device time of links, search A, search B and the copies, in milliseconds. */
+typedef struct sp_deflate sp_deflate;
+int32_t sp_deflate_open(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, sp_deflate** out);
+size_t sp_deflate_segments(const sp_deflate* d);
+int32_t sp_deflate_segment_start(sp_deflate* d, size_t s);
+int32_t sp_deflate_segment_wait(sp_deflate* d, size_t s, size_t* first, size_t* count, const uint8_t** bytes, const uint16_t** L,
+                                const uint32_t** A, const uint32_t** B, double* ms /*4*/);
+void sp_deflate_close(sp_deflate* d);
+/* All segments in one call: L, A, B (host arrays of n elements; any may be NULL) filled for the whole input. */
+int32_t sp_deflate_matches(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, uint16_t* L, uint32_t* A, uint32_t* B);
 /* multiply_vec (sparse_mlpoly.rs:454-464): out[row] = sum val * z[col]; out has num_rows elements. */
 int32_t sp_sparse_mulvec(sp_ctx* ctx, const sp_sparse* m, const sp_table* z, sp_table** out);
 /* compute_eval_table_sparse (sparse_mlpoly.rs:466-481) for nm matrices, combined as r1csproof.rs:275-283 does:

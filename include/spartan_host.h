@@ -68,7 +68,9 @@ void* spz_instance_from_device_entries(void* ctx, size_t num_cons, size_t num_va
 void* spz_instance_synthetic(void* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, uint64_t seed, uint64_t* vars_out,
                              uint64_t* inputs_out);
 void spz_instance_free(void* inst);
-/* R1CSShape::get_digest (r1cs.rs:154-158): the zlib stream the proofs absorb, computed on first use. Size, then fill. */
+/* R1CSShape::get_digest (r1cs.rs:154-158): the zlib stream the proofs absorb, computed on first use (option digest.device: 1 = stream and match
+ * search on the device, parser and coding on the calling thread; 0 = all of it on the host; the same bytes). Size, then fill; 0 with
+ * spz_last_error() when the computation failed (a zlib stream is never empty). */
 size_t spz_instance_digest(void* inst, uint8_t* out, size_t cap);
 /* A caller that already holds the digest of a real libspartan Instance sets it instead. */
 void spz_instance_set_digest(void* inst, const uint8_t* digest, size_t n);
@@ -221,6 +223,26 @@ size_t spz_instance_shape_bincode(void* inst, uint8_t* out, size_t cap);
  * 4..10 = 16/32/128/256/512/768/1500). Size, then fill. */
 size_t spz_zlib_level6(const uint8_t* data, size_t n, int old_header, uint8_t* out, size_t cap);
 size_t spz_zlib_probes(const uint8_t* data, size_t n, unsigned probes, int old_header, uint8_t* out, size_t cap);
+/* The deflater's match search as one independent item per input position, and the parser over its tables (deflate.cc; the device runs the
+ * same search: spartan_hip.h, sp_deflate_*). A table entry is dist | len << 16. spz_deflate_matches_host fills A and B (n entries each) and,
+ * when L is not NULL, the hash-chain links L (n entries) on the calling thread: the CPU yardstick of the device search.
+ * spz_zlib_from_matches runs tdefl's parser, block decisions and Huffman coding over such tables (L == NULL: the links are computed for
+ * the lookups neither table answers) and returns spz_zlib_probes' bytes. Size, then fill; stats (may be NULL) = lookups, and how many of
+ * them neither table answered. */
+void spz_deflate_matches_host(const uint8_t* data, size_t n, unsigned probes, uint16_t* L, uint32_t* A, uint32_t* B);
+size_t spz_zlib_from_matches(const uint8_t* data, size_t n, const uint16_t* L, const uint32_t* A, const uint32_t* B, unsigned probes,
+                             int old_header, uint8_t* out, size_t cap, uint64_t stats[2]);
+/* The whole device-assisted deflate of n bytes of host memory, as the digest runs it over bincode(shape): match search on the context's
+ * device in segments of the option digest.segment, parser and coding on the calling thread behind it. Size, then fill (each call
+ * compresses); 0 with spz_last_error() on failure. stats (may be NULL; 12 doubles): lookups, lookups neither table answered, segments, device
+ * milliseconds of links / search A / search B / downloads, host milliseconds of parse and coding / waiting for the device / building the
+ * stream / in total, and 1.0 when the device path ran. */
+size_t spz_zlib_device(void* ctx, const uint8_t* data, size_t n, unsigned probes, int old_header, uint8_t* out, size_t cap, double stats[12]);
+/* bincode(R1CSShape) with the matrices' part serialised on the device (sp_sparse_bincode): spz_instance_shape_bincode's bytes. Size, then
+ * fill; 0 with spz_last_error() on failure. */
+size_t spz_instance_shape_bincode_device(void* inst, uint8_t* out, size_t cap);
+/* the figures of the instance's last digest computation, laid out as the stats of spz_zlib_device (the host path sets the total only) */
+void spz_instance_digest_stats(void* inst, double stats[12]);
 /* Fiat-Shamir pieces. spz_keccak_run_variant: one permutation by the named form; 1 = ran, 0 = this CPU or build does not have it. */
 int spz_keccak_run_variant(const char* name, uint64_t state[25]);
 void spz_shake256(const uint8_t* in, size_t n, uint8_t* out, size_t outlen);

@@ -20,11 +20,16 @@
 // line-by-line Rust port of tdefl) equals miniz; scripts/compare_with_libspartan.sh prints both digests. The header bytes are the one
 // documented variable: miniz >= 2.2 and miniz_oxide >= 0.4 derive FLEVEL from the probe count (level 6: 0x78 0x9C), older ones write
 // 0x78 0x01 (the `old_header` argument — an explicit API parameter, spz_instance_set_digest_header, never an environment switch).
+// Below the sequential deflater (the oracle of everything that follows, left as it was): the match search restated as one independent item
+// per input position (find_pure, deflate_matches_host — what csrc/deflate_match.hip runs on the device) and the same parser fed from match
+// tables instead of a dictionary (MatchParser, zlib_from_matches), which digest.cc runs behind the device search.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <memory>
 #include <vector>
+
+#include "libspartan.hpp"  // MatchParser and the declarations of what this file defines
 
 namespace spz {
 namespace {
@@ -52,6 +57,9 @@ struct Tdefl {
   uint32_t adler = 1;
   bool old_header = false;
   unsigned probes = 128;  // tdefl flags & 0xFFF: s_tdefl_num_probes[level] = {0, 1, 6, 32, 16, 32, 128, 256, 512, 768, 1500}; 128 = level 6
+  // the table-driven parser (MatchParser below) keeps no dictionary: the bytes of a stored block then come from the input itself
+  const uint8_t* stored_src = nullptr;
+  size_t stored_pos = 0;  // lz_dict_pos without the 32-bit wrap: where the current block began in stored_src
 
   void put(unsigned b, unsigned l) {
     bitbuf |= (uint64_t)b << bits_in;
@@ -266,7 +274,7 @@ struct Tdefl {
       if (bits_in) put(0, 8 - bits_in);
       put(total_lz_bytes & 0xFFFF, 16);
       put((total_lz_bytes ^ 0xFFFF) & 0xFFFF, 16);
-      for (unsigned i = 0; i < total_lz_bytes; ++i) put(dict[(lz_dict_pos + i) & DMASK], 8);
+      for (unsigned i = 0; i < total_lz_bytes; ++i) put(stored_src ? stored_src[stored_pos + i] : dict[(lz_dict_pos + i) & DMASK], 8);
     }
     if (finish) {
       if (bits_in) put(0, 8 - bits_in);
@@ -278,6 +286,7 @@ struct Tdefl {
     toks.clear();
     code_bytes = 1; flags_left = 8;
     lz_dict_pos += total_lz_bytes;
+    stored_pos += total_lz_bytes;
     total_lz_bytes = 0;
     block_index++;
   }
@@ -373,7 +382,187 @@ struct Tdefl {
     flush_block(true);
   }
 };
+// ---- the match search restated as one independent item per input position (what deflate_match.hip runs on the device)
+// find_match above reads three things that depend on how far the parser has come: the ring `dict`, the ring `next`, and dict_size. With
+// the whole input D[0, n) in hand all three are functions of the position p alone:
+//   lookahead   la = min(258, n - p);  dict_size = min(p, 32768 - la)
+//   dict        dict[(q & 32767) + k] is D[q + k] for every q the search can reach (q >= p - dict_size: q + 32768 has not arrived yet)
+//   next        the slot of such a q still holds q's own link L[q] = low 16 bits of the greatest q' < q with the same 3-byte hash (0: none).
+//               The look-back is unbounded: a head written more than 65535 positions ago aliases, and tdefl follows the alias.
+// So find(p, init) below is find_match with those substitutions and nothing else changed: probe budget, three-hop inner loop, c0/c1
+// filter, the dist == 0 break and the early return at the longest match are literally the code above.
+inline void probe_budget(unsigned probes, unsigned mp[2]) {
+  mp[0] = 1 + ((probes & 0xFFF) + 2) / 3;
+  mp[1] = 1 + (((probes & 0xFFF) >> 2) + 2) / 3;
+}
+inline uint32_t pack_match(unsigned dist, unsigned len) { return dist | (len << 16); }
+uint32_t find_pure(const uint8_t* D, size_t n, const uint16_t* Lbase, size_t Lfirst, size_t p, unsigned init, const unsigned mp[2]) {
+  // Lbase[q - Lfirst] = L[q]; the caller keeps [p - 32768, p] addressable
+  const unsigned la = (unsigned)std::min<size_t>(MAXM, n - p), max_dist = (unsigned)std::min<size_t>(p, DICT - la);
+  unsigned dist = 0, best = 0, match_len = init, probe_len;
+  if (la <= match_len) return pack_match(0, init);
+  unsigned probes_left = mp[match_len >= 32];
+  const uint8_t* s = D + p;
+  uint8_t c0 = s[match_len], c1 = s[match_len - 1];
+  size_t cand = p;
+  for (;;) {
+    for (;;) {
+      if (--probes_left == 0) return pack_match(best, match_len);
+      bool hit = false;
+      for (int k = 0; k < 3 && !hit; k++) {
+        const unsigned nx = Lbase[cand - Lfirst];
+        if (!nx || (dist = (uint16_t)((unsigned)p - nx)) > max_dist) return pack_match(best, match_len);
+        cand = p - dist;
+        if (D[cand + match_len] == c0 && D[cand + match_len - 1] == c1) hit = true;
+      }
+      if (hit) break;
+    }
+    if (!dist) break;
+    const uint8_t* q = D + cand;
+    for (probe_len = 0; probe_len < la; probe_len++) if (s[probe_len] != q[probe_len]) break;
+    if (probe_len > match_len) {
+      best = dist;
+      if ((match_len = probe_len) == la) break;
+      c0 = s[match_len]; c1 = s[match_len - 1];
+    }
+  }
+  return pack_match(best, match_len);
+}
+// does the match A[p - 1] = a come out of the parser's filter as a HELD match (then the parser asks at p with init = its length: table B)
+inline bool held_after_filter(uint32_t a, size_t pos_of_a) {
+  const unsigned dist = a & 0xFFFF, len = a >> 16;
+  if (!dist) return false;
+  if ((len == MINM && dist >= 8u * 1024u) || (unsigned)(pos_of_a & DMASK) == dist) return false;
+  return len < 128;
+}
 }  // namespace
+
+void deflate_links_host(const uint8_t* D, size_t n, uint16_t* L) {
+  std::vector<uint16_t> head(HSIZE, 0);
+  for (size_t p = 0; p < n; p++) {
+    if (p + 2 >= n) { L[p] = 0; continue; }
+    const unsigned h = ((D[p] << (HSHIFT * 2)) ^ (D[p + 1] << HSHIFT) ^ D[p + 2]) & (HSIZE - 1);
+    L[p] = head[h];
+    head[h] = (uint16_t)p;
+  }
+}
+void deflate_matches_host(const uint8_t* D, size_t n, unsigned probes, const uint16_t* L, uint32_t* A, uint32_t* B) {
+  std::vector<uint16_t> own;
+  if (!L) { own.resize(n ? n : 1); deflate_links_host(D, n, own.data()); L = own.data(); }
+  unsigned mp[2];
+  probe_budget(probes, mp);
+  for (size_t p = 0; p < n; p++) A[p] = find_pure(D, n, L, 0, p, MINM - 1, mp);
+  for (size_t p = 0; p < n; p++) B[p] = p && held_after_filter(A[p - 1], p - 1) ? find_pure(D, n, L, 0, p, A[p - 1] >> 16, mp) : 0;
+}
+
+// Tdefl::run with the matches read from the tables: the same parser, block decisions, Huffman coding and bit output (the Tdefl members
+// above, untouched), no dictionary and no hash chains. Fed segment by segment, so that it can run behind the device search.
+struct MatchParser::Impl {
+  Tdefl d;
+  size_t n = 0, p = 0;                // input length, next position to parse
+  uint32_t s1 = 1, s2 = 0;            // Adler-32 so far
+  size_t adler_pos = 0;
+  uint32_t prevA = 0;                 // A[first - 1] of the segment being parsed
+  std::vector<uint16_t> ltail;        // L[ltail_first, ltail_first + ltail.size()): the last <= 32768 links of the segments already parsed
+  size_t ltail_first = 0;
+  std::vector<uint16_t> lwin;         // a fallback's view of the links: ltail followed by the current segment's (built on the first fallback of a segment)
+  unsigned mp[2];
+};
+MatchParser::MatchParser(size_t n, unsigned probes, bool old_header) : m(new Impl()) {
+  Tdefl& d = m->d;
+  memset(d.count, 0, sizeof d.count); memset(d.codes, 0, sizeof d.codes); memset(d.sizes, 0, sizeof d.sizes);
+  d.old_header = old_header;
+  d.probes = probes & 0xFFF;
+  probe_budget(d.probes, m->mp);
+  d.max_probes[0] = m->mp[0]; d.max_probes[1] = m->mp[1];
+  m->n = n;
+}
+MatchParser::~MatchParser() { delete m; }
+void MatchParser::parse(const uint8_t* D, size_t first, size_t count, const uint16_t* L, const uint32_t* A, const uint32_t* B) {
+  Impl& s = *m;
+  Tdefl& d = s.d;
+  const size_t n = s.n, end = first + count;
+  d.stored_src = D;
+  for (; s.adler_pos < end;) {  // Adler-32 of the input as it arrives
+    const size_t blk = std::min<size_t>(5552, end - s.adler_pos);
+    for (size_t k = 0; k < blk; k++) { s.s1 += D[s.adler_pos + k]; s.s2 += s.s1; }
+    s.s1 %= 65521; s.s2 %= 65521; s.adler_pos += blk;
+  }
+  bool lwin_built = false;
+  while (s.p < end) {
+    const size_t p = s.p;
+    d.lookahead_pos = (unsigned)p;
+    d.lookahead_size = (unsigned)std::min<size_t>(MAXM, n - p);
+    d.dict_size = std::min(DICT - d.lookahead_size, d.dict_size);
+    unsigned len_to_move = 1, cur_match_dist, cur_match_len;
+    const unsigned init = d.saved_match_len ? d.saved_match_len : (MINM - 1), cur_pos = (unsigned)(p & DMASK);
+    const uint32_t aprev = p > first ? A[p - 1 - first] : s.prevA;
+    uint32_t got;
+    lookups++;
+    if (init == MINM - 1) got = A[p - first];
+    else if (p && held_after_filter(aprev, p - 1) && (aprev >> 16) == init) got = B[p - first];
+    else {  // a lazy chain of three or more whose held length is not A[p - 1]'s: searched here
+      fallbacks++;
+      if (!lwin_built) {
+        s.lwin.assign(s.ltail.begin(), s.ltail.end());
+        s.lwin.insert(s.lwin.end(), L, L + count);
+        lwin_built = true;
+      }
+      got = find_pure(D, n, s.lwin.data(), s.ltail_first, p, init, s.mp);
+    }
+    cur_match_dist = got & 0xFFFF; cur_match_len = got >> 16;
+    if ((cur_match_len == MINM && cur_match_dist >= 8u * 1024u) || cur_pos == cur_match_dist) cur_match_dist = cur_match_len = 0;
+    if (d.saved_match_len) {
+      if (cur_match_len > d.saved_match_len) {
+        d.record_literal((uint8_t)d.saved_lit);
+        if (cur_match_len >= 128) { d.record_match(cur_match_len, cur_match_dist); d.saved_match_len = 0; len_to_move = cur_match_len; }
+        else { d.saved_lit = D[p]; d.saved_match_dist = cur_match_dist; d.saved_match_len = cur_match_len; }
+      } else {
+        d.record_match(d.saved_match_len, d.saved_match_dist);
+        len_to_move = d.saved_match_len - 1;
+        d.saved_match_len = 0;
+      }
+    } else if (!cur_match_dist) {
+      d.record_literal(D[p]);
+    } else if (cur_match_len >= 128) {
+      d.record_match(cur_match_len, cur_match_dist);
+      len_to_move = cur_match_len;
+    } else {
+      d.saved_lit = D[p]; d.saved_match_dist = cur_match_dist; d.saved_match_len = cur_match_len;
+    }
+    s.p += len_to_move;
+    d.lookahead_pos += len_to_move;
+    d.lookahead_size -= len_to_move;
+    d.dict_size = std::min(d.dict_size + len_to_move, DICT);
+    if (d.code_bytes > LZBUF - 8 || (d.total_lz_bytes > 31 * 1024 && ((d.code_bytes * 115) >> 7) >= d.total_lz_bytes)) d.flush_block(false);
+  }
+  // what the next segment needs of this one: its last table entry and the last 32768 links
+  if (count) {
+    s.prevA = A[count - 1];
+    if (count >= DICT) {
+      s.ltail.assign(L + count - DICT, L + count);
+    } else {
+      s.ltail.insert(s.ltail.end(), L, L + count);
+      if (s.ltail.size() > DICT) s.ltail.erase(s.ltail.begin(), s.ltail.end() - DICT);
+    }
+    s.ltail_first = end - s.ltail.size();
+  }
+}
+std::vector<uint8_t> MatchParser::finish() {
+  m->d.adler = (m->s2 << 16) | m->s1;
+  m->d.flush_block(true);
+  return std::move(m->d.out);
+}
+std::vector<uint8_t> zlib_from_matches(const uint8_t* D, size_t n, const uint16_t* L, const uint32_t* A, const uint32_t* B, unsigned probes, bool old_header,
+                                       uint64_t* lookups, uint64_t* fallbacks) {
+  std::vector<uint16_t> own;
+  if (!L) { own.resize(n ? n : 1); deflate_links_host(D, n, own.data()); L = own.data(); }
+  MatchParser mp(n, probes, old_header);
+  mp.parse(D, 0, n, L, A, B);
+  if (lookups) *lookups = mp.lookups;
+  if (fallbacks) *fallbacks = mp.fallbacks;
+  return mp.finish();
+}
 
 std::vector<uint8_t> zlib_miniz_probes(const uint8_t* data, size_t n, unsigned probes, bool old_header) {
   std::unique_ptr<Tdefl> d(new Tdefl());

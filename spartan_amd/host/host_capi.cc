@@ -274,7 +274,9 @@ int spz_instance_set_digest_header(void* inst, int old_header) {
   g_err = "set_digest_header after the digest was first used";
   return -1;
 }
-size_t spz_instance_digest(void* inst, uint8_t* out, size_t cap) { return bytes_out(((Instance*)inst)->compute_digest(), out, cap); }
+size_t spz_instance_digest(void* inst, uint8_t* out, size_t cap) {
+  return guard((size_t)0, [&] { return bytes_out(((Instance*)inst)->compute_digest(), out, cap); });  // a device failure: 0 and spz_last_error()
+}
 size_t spz_instance_shape_bincode(void* inst, uint8_t* out, size_t cap) { return bytes_out(((Instance*)inst)->shape_bincode(), out, cap); }
 int spz_instance_is_sat(void* inst, void* assignment, const uint64_t* vars, size_t nvars, const uint64_t* inputs, size_t ninputs, uint64_t report[2],
                         uint64_t* rows_out, size_t rows_cap) {
@@ -492,6 +494,38 @@ size_t spz_zlib_level6(const uint8_t* data, size_t n, int old_header, uint8_t* o
 size_t spz_zlib_probes(const uint8_t* data, size_t n, unsigned probes, int old_header, uint8_t* out, size_t cap) {
   return bytes_out(zlib_miniz_probes(data, n, probes, old_header != 0), out, cap);
 }
+void spz_deflate_matches_host(const uint8_t* data, size_t n, unsigned probes, uint16_t* L, uint32_t* A, uint32_t* B) {
+  if (L) deflate_links_host(data, n, L);
+  deflate_matches_host(data, n, probes, L, A, B);
+}
+size_t spz_zlib_from_matches(const uint8_t* data, size_t n, const uint16_t* L, const uint32_t* A, const uint32_t* B, unsigned probes, int old_header,
+                             uint8_t* out, size_t cap, uint64_t stats[2]) {
+  uint64_t lookups = 0, fallbacks = 0;
+  const std::vector<uint8_t> z = zlib_from_matches(data, n, L, A, B, probes, old_header != 0, &lookups, &fallbacks);
+  if (stats) { stats[0] = lookups; stats[1] = fallbacks; }
+  return bytes_out(z, out, cap);
+}
+namespace {
+void stats_out(const DeflateStats& s, double* o) {
+  if (!o) return;
+  const double v[12] = {s.lookups, s.fallbacks, s.segments, s.ms_links, s.ms_search_a, s.ms_search_b, s.ms_download, s.ms_parse, s.ms_wait, s.ms_stream,
+                        s.ms_total, s.device};
+  memcpy(o, v, sizeof v);
+}
+}  // namespace
+size_t spz_zlib_device(void* ctx, const uint8_t* data, size_t n, unsigned probes, int old_header, uint8_t* out, size_t cap, double stats[12]) {
+  return guard((size_t)0, [&] {
+    if (!ctx || (n && !data) || probes == 0 || probes > 0xFFF) throw bad_arguments("spz_zlib_device");
+    DeflateStats s;
+    const std::vector<uint8_t> z = zlib_device(((Ctx*)ctx)->h, data, nullptr, n, probes, old_header != 0, &s);
+    stats_out(s, stats);
+    return bytes_out(z, out, cap);
+  });
+}
+size_t spz_instance_shape_bincode_device(void* inst, uint8_t* out, size_t cap) {
+  return guard((size_t)0, [&] { return bytes_out(((Instance*)inst)->shape_bincode_device(), out, cap); });
+}
+void spz_instance_digest_stats(void* inst, double stats[12]) { stats_out(((Instance*)inst)->digest_stats, stats); }
 const char* spz_keccak_variant() { return keccak_f1600_variant(); }
 int spz_keccak_run_variant(const char* name, uint64_t state[25]) { return keccak_f1600_run_variant(name, state); }
 void spz_shake256(const uint8_t* in, size_t n, uint8_t* out, size_t outlen) { Shake256 s; s.absorb(in, n); s.squeeze(out, outlen); }

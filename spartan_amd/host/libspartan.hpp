@@ -176,6 +176,14 @@ struct SNARKGens {  // src/lib.rs:276-309
   void index(const GensLayout& l);  // the MultiCommitGens views into the two streams
 };
 
+// Figures of one device-assisted deflate (digest.cc), as spz_zlib_device and spz_instance_digest_stats report them
+struct DeflateStats {
+  double lookups = 0, fallbacks = 0, segments = 0;
+  double ms_links = 0, ms_search_a = 0, ms_search_b = 0, ms_download = 0;  // device time, from events on the search's stream
+  double ms_parse = 0, ms_wait = 0, ms_stream = 0, ms_total = 0;            // host wall time: parse + coding, waiting for the device, building the stream
+  double device = 0;                                                        // 1: the device-assisted path ran
+};
+
 // ---- instance ----
 struct SparseEntry { uint64_t row, col; Fq val; };
 struct VarsAssignment;
@@ -192,14 +200,20 @@ struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the m
   // R1CSShapeDigest bytes: zlib(level 6)(bincode(shape)) (r1cs.rs:154-158), absorbed by NIZK::prove (lib.rs:514). Computed on first
   // use by compute_digest() (deflate.cc: a restatement of miniz's level-6 tdefl, what flate2's rust_backend runs — byte-identical to the
   // real C miniz 3.0.2 on the test corpus); a caller that holds the bytes of a real libspartan Instance may set them instead
-  // (set_digest). The computation is guarded: concurrent NIZK::prove calls over one Instance compute it once; a caller that wants the
-  // deflate of a large shape (~6 s at 2^20) out of its first prove calls compute_digest() right after construction, as the reference's
-  // Instance::new does (lib.rs:228).
+  // (set_digest). With the option digest.device = 1 (the default) the stream is serialised and the deflater's match search runs on the
+  // device, and only its parser and Huffman coding run here (digest.cc; the same bytes). The computation is guarded: concurrent
+  // NIZK::prove calls over one Instance compute it once; a caller that wants the deflate of a large shape (4.5 s at 2^20 with 9.4 M
+  // entries, 19.9 s on the host alone: profiles/instance_digest.txt) out of its first prove calls compute_digest() right after
+  // construction, as the reference's Instance::new does (lib.rs:228).
   mutable std::vector<uint8_t> digest;
   bool digest_old_header = false;  // zlib header 0x78 0x01 (miniz < 2.2, miniz_oxide 0.3) instead of 0x78 0x9C; set before the first compute_digest()
   mutable std::mutex digest_mu;
   std::vector<uint8_t> shape_bincode() const;  // bincode(R1CSShape): r1cs.rs:18-26, sparse_mlpoly.rs:19-38
   std::vector<uint8_t> compute_digest() const;
+  // option digest.device = 1 (digest.cc): the stream serialised and its matches searched on the device, parsed and coded here; the same bytes
+  std::vector<uint8_t> compute_digest_device() const;
+  std::vector<uint8_t> shape_bincode_device() const;  // test hook: bincode(shape) as sp_sparse_bincode writes it
+  mutable DeflateStats digest_stats;                  // figures of the last computation (device == 0: the host path; only ms_total is set)
   bool set_digest_header(bool old_header);
   void set_digest(const uint8_t* d, size_t n);
   // Instance::new (lib.rs:121-228): padding of num_cons / num_vars and the column shift are applied here.
@@ -291,6 +305,36 @@ Fq seed_scalar(const char* domain, uint64_t seed);
 std::vector<uint8_t> zlib_level6_miniz(const uint8_t* data, size_t n, bool old_header = false);
 // the same compressor at another probe count (tdefl flags & 0xFFF: 16/32/128/256/512/768/1500 = miniz levels 4..10); tests pin each against miniz
 std::vector<uint8_t> zlib_miniz_probes(const uint8_t* data, size_t n, unsigned probes, bool old_header = false);
+// The match search of that compressor as one independent item per input position (deflate.cc; on the device: csrc/deflate_match.hip).
+// A table entry is dist | len << 16, (0, init) when nothing was found:
+//   L[p]  low 16 bits of the greatest q < p whose 3-byte hash equals p's, 0 if none (p + 2 < n; 0 elsewhere)
+//   A[p]  the search at p that starts from nothing (init = 2)
+//   B[p]  the search at p that has to beat A[p - 1], where A[p - 1] leaves the parser's filter as a held match; 0 elsewhere
+// deflate_matches_host is the CPU yardstick and the fallback; L == nullptr: computed inside.
+void deflate_links_host(const uint8_t* data, size_t n, uint16_t* L);
+void deflate_matches_host(const uint8_t* data, size_t n, unsigned probes, const uint16_t* L, uint32_t* A, uint32_t* B);
+// tdefl's parser, block decisions, Huffman coding and bit output (all sequential, all on the host) over such tables, segment by segment:
+// parse(D, first, count, L, A, B) takes the tables of positions [first, first + count) — segments in order, without gaps — and needs
+// D[0, min(n, first + count + 258)) readable. A lookup that neither table answers (a lazy chain of three or more matches whose held
+// length is not A[p - 1]'s) is searched on the spot and counted in `fallbacks`.
+struct MatchParser {
+  MatchParser(size_t n, unsigned probes, bool old_header);
+  ~MatchParser();
+  MatchParser(const MatchParser&) = delete;
+  void parse(const uint8_t* D, size_t first, size_t count, const uint16_t* L, const uint32_t* A, const uint32_t* B);
+  std::vector<uint8_t> finish();  // the zlib stream; the parser is spent
+  uint64_t lookups = 0, fallbacks = 0;
+ private:
+  struct Impl;
+  Impl* m;
+};
+// one call over whole tables: equals zlib_miniz_probes(data, n, probes, old_header) byte for byte
+std::vector<uint8_t> zlib_from_matches(const uint8_t* data, size_t n, const uint16_t* L, const uint32_t* A, const uint32_t* B, unsigned probes,
+                                       bool old_header, uint64_t* lookups = nullptr, uint64_t* fallbacks = nullptr);
+// zlib stream of n bytes at `data` (host memory) or `dev_data` (memory of the context's device), the matches searched on the device
+std::vector<uint8_t> zlib_device(sp_ctx* c, const uint8_t* data, const uint8_t* dev_data, size_t n, unsigned probes, bool old_header, DeflateStats* st);
+// per-entry-point wall time of the option host.callstats (prover.cc), for driver files that cannot use its macro
+void callstats_add(const char* entry, double seconds);
 
 // ---- proof structs: field order == bincode order (same as the reference's serde derives) ----
 struct PolyCommitment { std::vector<CP> C; };                                   // dense_mlpoly.rs:38-41

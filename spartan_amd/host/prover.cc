@@ -36,6 +36,12 @@ struct CallStats {
   }
 };
 static CallStats g_calls;
+void callstats_add(const char* entry, double seconds) {
+  if (!g_calls.on) return;
+  auto& e = g_calls.m[entry];
+  e.t += seconds;
+  e.n++;
+}
 #ifdef SPZ_HOSTPROF
 // diagnostic build only: host-exclusive time per driver function = wall - device-API time - nested spans
 static double g_api_t = 0;
@@ -351,8 +357,15 @@ std::vector<uint8_t> Instance::compute_digest() const {  // by value, copied und
       fprintf(stderr, "spartan_host: R1CSShapeDigest computed by the in-tree deflater (deflate.cc: byte-identical to miniz 3.0.2 level 6 on the test corpus; "
                       "equality with miniz_oxide is the port's claim) — pass the digest of a libspartan Instance with set_digest to bypass it\n");
     });
-    std::vector<uint8_t> sb = shape_bincode();
-    digest = zlib_level6_miniz(sb.data(), sb.size(), digest_old_header);
+    if (ctx_opt(c, "digest.device") != 0) {
+      digest = compute_digest_device();  // digest.cc: stream and match search on the device, parse and coding here
+    } else {
+      const double t0 = now_s();
+      std::vector<uint8_t> sb = shape_bincode();
+      digest = zlib_level6_miniz(sb.data(), sb.size(), digest_old_header);
+      digest_stats = DeflateStats();
+      digest_stats.ms_total = (now_s() - t0) * 1e3;
+    }
   }
   return digest;
 }

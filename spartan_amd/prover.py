@@ -58,6 +58,10 @@ SIGNATURES = {
     "spz_snark_reserialize": (_ll, [vp, sz] + _BYTES), "spz_nizk_parse_probe": (_ll, [vp, sz] + _BYTES),
     "spz_commitment_reserialize": (_ll, [vp, sz] + _BYTES), "spz_instance_shape_bincode": (sz, [vp] + _BYTES),
     "spz_zlib_level6": (sz, [vp, sz, _i] + _BYTES), "spz_zlib_probes": (sz, [vp, sz, ctypes.c_uint, _i] + _BYTES),
+    "spz_deflate_matches_host": (None, [vp, sz, ctypes.c_uint, vp, vp, vp]),
+    "spz_zlib_from_matches": (sz, [vp, sz, vp, vp, vp, ctypes.c_uint, _i] + _BYTES + [vp]),
+    "spz_zlib_device": (sz, [vp, vp, sz, ctypes.c_uint, _i] + _BYTES + [vp]),
+    "spz_instance_shape_bincode_device": (sz, [vp] + _BYTES), "spz_instance_digest_stats": (None, [vp, vp]),
     "spz_keccak_run_variant": (_i, [_s, vp]), "spz_shake256": (None, [vp, sz, vp, sz]),
     "spz_merlin_script": (sz, _SCRIPT), "spz_merlin_state": (None, _SCRIPT), "spz_merlin_challenge_from_state": (None, [vp, _s, vp, sz]),
     "spz_tape_draws": (None, [vp, _s, sz, vp]), "spz_seed_scalar": (None, [_s, _u64, vp]),
@@ -217,7 +221,23 @@ class Instance:
 
     def digest(self):
         """R1CSShapeDigest (src/r1cs.rs:154-158): the bytes set with set_digest, else computed by the host library (zlib level 6 of bincode(shape))"""
-        return _fill(H.spz_instance_digest, self.h)
+        d = _fill(H.spz_instance_digest, self.h)
+        if not d:   # a zlib stream is never empty: the computation failed
+            raise SpartanHipError(_failed("Instance::digest"))
+        return d
+
+    def digest_stats(self):
+        """figures of the last digest computation (see zlib_device); the host path (option digest.device = 0) fills ms_total only"""
+        st = (ctypes.c_double * 12)()
+        H.spz_instance_digest_stats(self.h, st)
+        return dict(zip(DEFLATE_STATS, st))
+
+    def shape_bincode_device(self):
+        """test hook: bincode(R1CSShape) with the matrices serialised on the device (sp_sparse_bincode)"""
+        b = _fill(H.spz_instance_shape_bincode_device, self.h)
+        if not b:
+            raise SpartanHipError(_failed("Instance::shape_bincode_device"))
+        return b
 
     def set_digest_header(self, old_header):
         """zlib header variant of the computed digest: False = 0x78 0x9C (miniz >= 2.2, miniz_oxide >= 0.4), True = 0x78 0x01"""
@@ -342,6 +362,24 @@ def rccl_unique_id():
 def keccak_variant():
     """which form of Keccak-f[1600] the host driver picked for this CPU (keccak.cc): plain | bmi2 | avx512"""
     return H.spz_keccak_variant().decode()
+
+
+DEFLATE_STATS = ("lookups", "fallbacks", "segments", "ms_links", "ms_search_a", "ms_search_b", "ms_download", "ms_parse", "ms_wait", "ms_stream",
+                 "ms_total", "device")
+
+
+def zlib_device(ctx, data, probes=128, old_header=False):
+    """(zlib stream of `data` as miniz writes it at this tdefl probe count, stats): the device-assisted deflate the instance digest runs over
+    bincode(shape) — match search on the GPU in segments of the option digest.segment, parser and Huffman coding on the calling thread.
+    stats: lookups and those neither match table answered, segments, device ms of links / search A / search B / downloads, host ms of parse /
+    wait / stream / total."""
+    data = bytes(data)
+    cap = 2 * len(data) + 1024
+    out = (ctypes.c_uint8 * cap)(); st = (ctypes.c_double * 12)()
+    n = H.spz_zlib_device(ctx.h, data, sz(len(data)), ctypes.c_uint(probes), 1 if old_header else 0, out, sz(cap), st)
+    if n == 0:
+        raise SpartanHipError(_failed("zlib_device"))
+    return bytes(out[:n]), dict(zip(DEFLATE_STATS, st))
 
 
 def seed_scalar(domain, seed):
