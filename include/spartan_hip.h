@@ -439,6 +439,29 @@ int32_t sp_deflate_segment_wait(sp_deflate* d, size_t s, size_t* first, size_t* 
 void sp_deflate_close(sp_deflate* d);
 /* All segments in one call: L, A, B (host arrays of n elements; any may be NULL) filled for the whole input. */
 int32_t sp_deflate_matches(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, uint16_t* L, uint32_t* A, uint32_t* B);
+/* tdefl's lazy PARSE over those tables, on the device too: the host then receives TOKENS and downloads neither L, A nor B. A token is one
+ * 32-bit word per literal or match, in stream order: bit 31 set; bit 30 = tdefl's block check runs after it; bit 29 = a match is held when
+ * that check runs; a literal has its byte in bits 0..7 and bits 15..23 zero, a match its length in bits 15..23 and dist - 1 in bits 0..14
+ * (spartan_amd/host/deflate.cc: walk, TokenCoder). The parser's state is FREE when it holds no match; from a free state at p the next one,
+ * F(p) <= p + 383, depends on the tables alone, so the parse is the set of positions reachable from the segment's entry under F — found
+ * through exits of tiles of `tile` positions and of groups of `group` tiles — and one short walk per reachable position. Device scratch
+ * grows by about 8 bytes a position of one segment (2 of jumps, 4 of token words, 1536 / tile of exits: about 38 in all); the pinned slots
+ * shrink from 11 to 5 bytes a position.
+ *   sp_deflate_open_parse           sp_deflate_open for this form; tile 512..4096 (0: 1024), group 2..4096 (0: 64), else SP_EINVAL.
+ *                                   sp_deflate_segment_start queues the parse behind the searches; sp_deflate_segment_wait is SP_EINVAL.
+ *   sp_deflate_segment_wait_tokens  wait for segment s: first, count, bytes as sp_deflate_segment_wait gives them; tokens / ntok: the tokens
+ *                                   of the parser's steps at positions of this segment (a step in a held state emits at the position before
+ *                                   it, so the first may start at first - 1), valid until segment s + 2 is started; carry (may be NULL; 4):
+ *                                   the state the next segment is entered with — position of its first step, length and distance of the
+ *                                   match held there (0, 0: none) — and the look-ups searched on the spot so far; ms (may be NULL; 6): device
+ *                                   milliseconds of links, search A, search B, reachability, token kernel + compaction, copies.
+ *   sp_deflate_tokens               all segments in one call: tokens (host array of n words, may be NULL) and their number; info (may be
+ *                                   NULL; 2) = segments entered with a held match, look-ups searched on the spot. */
+int32_t sp_deflate_open_parse(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, sp_deflate** out);
+int32_t sp_deflate_segment_wait_tokens(sp_deflate* d, size_t s, size_t* first, size_t* count, const uint8_t** bytes, const uint32_t** tokens,
+                                       size_t* ntok, uint64_t* carry /*4*/, double* ms /*6*/);
+int32_t sp_deflate_tokens(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, uint32_t* tokens /*n*/,
+                          size_t* ntok, uint64_t* info /*2*/);
 /* multiply_vec (sparse_mlpoly.rs:454-464): out[row] = sum val * z[col]; out has num_rows elements. */
 int32_t sp_sparse_mulvec(sp_ctx* ctx, const sp_sparse* m, const sp_table* z, sp_table** out);
 /* compute_eval_table_sparse (sparse_mlpoly.rs:466-481) for nm matrices, combined as r1csproof.rs:275-283 does:

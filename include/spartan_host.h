@@ -69,7 +69,8 @@ void* spz_instance_synthetic(void* ctx, size_t num_cons, size_t num_vars, size_t
                              uint64_t* inputs_out);
 void spz_instance_free(void* inst);
 /* R1CSShape::get_digest (r1cs.rs:154-158): the zlib stream the proofs absorb, computed on first use (option digest.device: 1 = stream and match
- * search on the device, parser and coding on the calling thread; 0 = all of it on the host; the same bytes). Size, then fill; 0 with
+ * search on the device, parser and coding on the calling thread; 2 = the lazy parse on the device too, the calling thread codes its tokens;
+ * 0 = all of it on the host; the same bytes). Size, then fill; 0 with
  * spz_last_error() when the computation failed (a zlib stream is never empty). */
 size_t spz_instance_digest(void* inst, uint8_t* out, size_t cap);
 /* A caller that already holds the digest of a real libspartan Instance sets it instead. */
@@ -243,6 +244,27 @@ size_t spz_zlib_device(void* ctx, const uint8_t* data, size_t n, unsigned probes
 size_t spz_instance_shape_bincode_device(void* inst, uint8_t* out, size_t cap);
 /* the figures of the instance's last digest computation, laid out as the stats of spz_zlib_device (the host path sets the total only) */
 void spz_instance_digest_stats(void* inst, double stats[12]);
+/* The parse restated as walks between the parser's free states, and the coder over its tokens (deflate.cc; the device runs the same parse:
+ * spartan_hip.h, sp_deflate_tokens). A token is one 32-bit word per literal or match, in stream order: bit 31 set; bit 30 = tdefl's block
+ * check runs after it; bit 29 = a match is held when that check runs; a literal has its byte in bits 0..7 and bits 15..23 zero, a match has
+ * its length in bits 15..23 and dist - 1 in bits 0..14. spz_deflate_tokens_host writes up to n tokens and returns their number; geom (may be
+ * NULL; 3) = tile, tiles a group and segment length of the device parse it models, which change no token, only the counters; counters (may be
+ * NULL; 10) = walks, look-ups, look-ups neither match table answered, matches of >= 128 taken from a free state, a literal and a match of
+ * >= 128 from one step, matches spanning a tile / a group boundary within a segment, segments entered with a held match, tokens, the longest
+ * jump between two free states. spz_zlib_from_tokens codes such a list, `piece` tokens at a time (0: all at once), and returns
+ * spz_zlib_probes' bytes. Size, then fill; blocks (may be NULL; 4) = blocks ended by the code-buffer rule, by the 115/128 rule, stored
+ * blocks, static blocks. */
+size_t spz_deflate_tokens_host(const uint8_t* data, size_t n, unsigned probes, const size_t* geom, uint32_t* tokens, uint64_t* counters);
+size_t spz_zlib_from_tokens(const uint8_t* data, size_t n, const uint32_t* tokens, size_t ntok, unsigned probes, int old_header, size_t piece,
+                            uint8_t* out, size_t cap, uint64_t* blocks);
+/* spz_zlib_device with the form named: parse = 0 the parser on the host over downloaded match tables, 1 the parse on the device and the
+ * token coder on the host, -1 what the option digest.device says (2 = the device parse); tile, group = positions a tile and tiles a group
+ * of the device parse (0: 1024 and 64). stats (may be NULL) receives up to stats_cap of 17 doubles: the 12 of spz_zlib_device, then 1.0 when
+ * the device parsed, tokens, look-ups the device searched on the spot, device milliseconds of the reachability kernels and of the token
+ * kernel with its compaction. spz_instance_digest_stats_all: the same 17 of the instance's last digest computation. */
+size_t spz_zlib_device_parse(void* ctx, const uint8_t* data, size_t n, unsigned probes, int old_header, int parse, size_t tile, size_t group,
+                             uint8_t* out, size_t cap, double* stats, size_t stats_cap);
+void spz_instance_digest_stats_all(void* inst, double* stats, size_t stats_cap);
 /* Fiat-Shamir pieces. spz_keccak_run_variant: one permutation by the named form; 1 = ran, 0 = this CPU or build does not have it. */
 int spz_keccak_run_variant(const char* name, uint64_t state[25]);
 void spz_shake256(const uint8_t* in, size_t n, uint8_t* out, size_t outlen);

@@ -1,8 +1,9 @@
 // spartan_amd: the device's share of R1CSShape::get_digest (src/r1cs.rs:154-158). The digest is the zlib stream of bincode(shape) as miniz's
 // tdefl writes it at level 6 (spartan_amd/host/deflate.cc restates tdefl). Two things run here:
 //   sp_sparse_bincode    the matrices' part of bincode(R1CSShape), serialised from the resident entries into a device byte buffer
-//   sp_deflate_*         tdefl's hash-chain match search, one input position per lane
-// The parser that consumes the matches, the block decisions and the Huffman coding are sequential and stay on the host.
+//   sp_deflate_*         tdefl's hash-chain match search, one input position per lane; and, for a handle opened by sp_deflate_open_parse,
+//                        tdefl's lazy PARSE over the tables it fills, so that the host receives tokens instead of tables
+// The block decisions and the Huffman coding are sequential and stay on the host (deflate.cc: MatchParser over tables, TokenCoder over tokens).
 //
 // The search, per position p of the input D[0, n) (names as in deflate.cc, find_match):
 //   links   h(p) = ((D[p] << 10) ^ (D[p+1] << 5) ^ D[p+2]) & 32767;  L[p] = low 16 bits of the greatest q < p with h(q) == h(p), else 0.
@@ -14,7 +15,32 @@
 //   A[p] = find(p, 2);  B[p] = find(p, len(A[p-1])) where A[p-1] leaves the parser's filter as a held match.
 // A segment needs of its predecessors: head[32768], the last 32768 links, A[first - 1]. Every index below is bounded by construction:
 //   D[p + k], k < lookahead <= n - p;  D[cand + k], cand < p;  L window index cand - first + 32768 with cand >= p - 32768 + lookahead >= first - 32768.
+//
+// The parse (names as in deflate.cc, `walk`): the parser's state is FREE when it holds no match. From a free state at p everything up to
+// the next free state F(p) is a function of D, A, B and, for the rare look-up neither table answers, dm_find; 1 <= F(p) - p <= 383 (a walk
+// holds at most 125 times, each longer than the last and below 128, then takes at most 258). The tokens are those of the walks from the
+// positions REACHABLE from the segment's entry under F. Per segment of `count` positions, tiles of T and groups of G tiles (DP_HEAD = 384 <=
+// T, so a jump never skips a tile and enters one within its first 384 positions):
+//   k_dp_jump     one lane a position: delta[i] = F(i) - i by the walk itself, nothing written but the 16-bit delta (a walk stops at the
+//                 segment's end as the parser's loop does: delta then reaches exactly `count`, with a match still held)
+//   k_dp_exit     one workgroup a tile: pointer doubling in LDS, log2(T) + 1 rounds, gives every position of the tile its exit, the first
+//                 position at or past the tile's end; kept for the tile's first 384 positions: X0
+//   k_dp_compose  one lane for each of a group's first 384 positions: G dependent steps through X0 give the group's exit: X1
+//   k_dp_top      one lane: the segment's prologue (an entry that holds a match is resolved from the carried state, its tokens written),
+//                 then the walk over the groups through X1, leaving each group's entry
+//   k_dp_down     one lane a group: G steps through X0 leave each tile's entry
+//   k_dp_mark     one lane a tile: the walk over delta[] from the tile's entry sets bit 15 of every reachable position's delta
+//   k_dp_tokens   one lane a position: a marked one redoes its walk and writes its tokens, one word per position (0: no token starts
+//                 here; slot 0 stands for position first - 1, where the prologue's token starts); the walk that reaches the segment's end
+//                 writes the state the next segment enters with
+//   rocPRIM select  the nonzero words, in order, into the pinned slot, with their number
+// Scratch per position of one segment: about 30 bytes of the search, plus 2 of jumps, 4 of token words and 1536 / T of exits: about 38; the
+// pinned slots hold 5 bytes a position (token words and the bytes) instead of 11.
+// The longest dependent chain is log2(T) + 3 G + count / (T G) + T steps instead of `count`. Every index is bounded: a walk looks up only
+// q < count; delta, tok (count + 1 words) and the marks are indexed by positions < count; X0 / X1 by (tile or group, offset < 384) with
+// offset = position - start of the tile or group it lies in, which a jump of at most 383 from before that start keeps below 384.
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
 
 #include "internal.hpp"
 
@@ -125,6 +151,132 @@ __global__ void __launch_bounds__(DM_BLOCK) k_dm_search_b(const uint8_t* __restr
   Bb[i] = (p && dm_held(a, p - 1)) ? dm_find(D, n, Lw, first, p, a >> 16, mp0, mp1) : 0u;
 }
 
+// ---- the parse: walks between free states
+constexpr uint32_t DP_HEAD = 384;                    // 1 + the longest jump: the positions of a tile a walk from before it can enter at
+constexpr uint32_t DP_NONE = 0xFFFFFFFFu;
+constexpr uint32_t TOK_VALID = 1u << 31, TOK_CHECK = 1u << 30, TOK_HELD = 1u << 29;   // as in host/libspartan.hpp
+constexpr uint32_t DP_MARK = 0x8000u;
+struct DpCarry { uint32_t entry, sl, sd, fallbacks; };  // a segment's entry: position relative to its first, the held match (sl == 0: free)
+__device__ __forceinline__ uint32_t dp_lit(unsigned c, uint32_t bits) { return TOK_VALID | bits | c; }
+__device__ __forceinline__ uint32_t dp_match(unsigned len, unsigned dist, uint32_t bits) { return TOK_VALID | bits | (len << 15) | (dist - 1); }
+// deflate.cc, walk(): steps from (q, sl, sd) until the state is free again or q reaches count. Positions are relative to `first`; tok[1 + q]
+// is position q's word. Returns the next step's position (> count when a match crosses the segment's end); sl, sd: the match then held.
+template <bool EMIT>
+__device__ uint32_t dp_walk(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, const uint32_t* __restrict__ Ab,
+                            const uint32_t* __restrict__ Bb, size_t first, uint32_t count, uint32_t q, unsigned& sl, unsigned& sd, unsigned mp0,
+                            unsigned mp1, uint32_t* __restrict__ tok, unsigned& fallbacks) {
+  do {
+    const size_t p = first + q;
+    uint32_t got;
+    if (!sl) {
+      got = Ab[1 + q];
+    } else {
+      const uint32_t a = Ab[q];  // A[p - 1]
+      if (dm_held(a, p - 1) && (a >> 16) == sl) got = Bb[q];
+      else { got = dm_find(D, n, Lw, first, p, sl, mp0, mp1); fallbacks++; }
+    }
+    unsigned cd = got & 0xFFFFu, cl = got >> 16;
+    if ((cl == DM_MINM && cd >= 8192u) || (unsigned)(p & (DM_DICT - 1)) == cd) cd = cl = 0;
+    if (sl) {
+      if (cl > sl) {
+        if (cl >= 128) {
+          if (EMIT) { tok[q] = dp_lit(D[p - 1], 0); tok[1 + q] = dp_match(cl, cd, TOK_CHECK); }
+          sl = 0; q += cl;
+        } else {
+          if (EMIT) tok[q] = dp_lit(D[p - 1], TOK_CHECK | TOK_HELD);
+          sl = cl; sd = cd; q += 1;
+        }
+      } else {
+        if (EMIT) tok[q] = dp_match(sl, sd, TOK_CHECK);
+        q += sl - 1; sl = 0;
+      }
+    } else if (!cd) {
+      if (EMIT) tok[1 + q] = dp_lit(D[p], TOK_CHECK);
+      q += 1;
+    } else if (cl >= 128) {
+      if (EMIT) tok[1 + q] = dp_match(cl, cd, TOK_CHECK);
+      q += cl;
+    } else {
+      sl = cl; sd = cd; q += 1;
+    }
+  } while (sl && q < count);
+  return q;
+}
+__global__ void __launch_bounds__(DM_BLOCK) k_dp_jump(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, const uint32_t* __restrict__ Ab,
+                                                      const uint32_t* __restrict__ Bb, size_t first, uint32_t count, unsigned mp0, unsigned mp1,
+                                                      uint16_t* __restrict__ delta) {
+  const uint32_t i = blockIdx.x * DM_BLOCK + threadIdx.x;
+  if (i >= count) return;
+  unsigned sl = 0, sd = 0, fb = 0;
+  const uint32_t next = dp_walk<false>(D, n, Lw, Ab, Bb, first, count, i, sl, sd, mp0, mp1, nullptr, fb);
+  delta[i] = (uint16_t)(next - i);  // 1 .. 383
+}
+// dynamic LDS: two arrays of T 16-bit tile-relative targets (< T + 384)
+__global__ void __launch_bounds__(DM_BLOCK) k_dp_exit(const uint16_t* __restrict__ delta, uint32_t count, uint32_t T, uint32_t* __restrict__ X0) {
+  extern __shared__ uint16_t dp_lds[];
+  uint16_t *a = dp_lds, *b = dp_lds + T;
+  const uint32_t t = blockIdx.x, start = t * T, Tt = count - start < T ? count - start : T;  // start < count by the grid
+  for (uint32_t j = threadIdx.x; j < Tt; j += DM_BLOCK) a[j] = (uint16_t)(j + delta[start + j]);
+  __syncthreads();
+  for (uint32_t span = 1; span < Tt; span <<= 1) {  // after r rounds a[j] is 2^r jumps from j, or the exit
+    for (uint32_t j = threadIdx.x; j < Tt; j += DM_BLOCK) { const uint32_t x = a[j]; b[j] = x < Tt ? a[x] : (uint16_t)x; }
+    __syncthreads();
+    uint16_t* s = a; a = b; b = s;
+  }
+  const uint32_t heads = Tt < DP_HEAD ? Tt : DP_HEAD;
+  for (uint32_t j = threadIdx.x; j < heads; j += DM_BLOCK) X0[(size_t)t * DP_HEAD + j] = start + a[j];
+}
+// blockDim = DP_HEAD: lane h follows the group's position h out of the group
+__global__ void __launch_bounds__(DP_HEAD) k_dp_compose(const uint32_t* __restrict__ X0, uint32_t count, uint32_t T, uint32_t G, uint32_t* __restrict__ X1) {
+  const uint32_t g = blockIdx.x, h = threadIdx.x;
+  const uint32_t gstart = g * G * T, gend_tile = (g + 1) * G;
+  uint32_t pos = gstart + h;
+  if (pos >= count) return;
+  while (pos < count && pos / T < gend_tile) { const uint32_t t = pos / T; pos = X0[(size_t)t * DP_HEAD + (pos - t * T)]; }
+  X1[(size_t)g * DP_HEAD + h] = pos;
+}
+// one lane: carry[0] the entry of this segment, carry[1] that of the next (written here only when the prologue already reaches the end)
+__global__ void k_dp_top(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, const uint32_t* __restrict__ Ab,
+                         const uint32_t* __restrict__ Bb, size_t first, uint32_t count, unsigned mp0, unsigned mp1, uint32_t* __restrict__ tok,
+                         const uint32_t* __restrict__ X1, uint32_t T, uint32_t G, uint32_t* __restrict__ Eg, DpCarry* __restrict__ carry) {
+  if (blockIdx.x || threadIdx.x) return;
+  uint32_t pos = carry[0].entry;
+  unsigned sl = carry[0].sl, sd = carry[0].sd, fb = 0;
+  if (sl && pos < count) pos = dp_walk<true>(D, n, Lw, Ab, Bb, first, count, pos, sl, sd, mp0, mp1, tok, fb);
+  if (pos >= count) { carry[1].entry = pos - count; carry[1].sl = sl; carry[1].sd = sd; carry[1].fallbacks = carry[0].fallbacks + fb; return; }
+  carry[1].fallbacks = carry[0].fallbacks + fb;  // the token kernel adds its own
+  const uint32_t GT = G * T;
+  while (pos < count) { const uint32_t g = pos / GT; Eg[g] = pos; pos = X1[(size_t)g * DP_HEAD + (pos - g * GT)]; }
+}
+__global__ void __launch_bounds__(64) k_dp_down(const uint32_t* __restrict__ X0, uint32_t count, uint32_t T, uint32_t G, uint32_t ngroups,
+                                                const uint32_t* __restrict__ Eg, uint32_t* __restrict__ Et) {
+  const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+  if (g >= ngroups) return;
+  uint32_t pos = Eg[g];
+  const uint32_t gend_tile = (g + 1) * G;
+  while (pos < count && pos / T < gend_tile) { const uint32_t t = pos / T; Et[t] = pos; pos = X0[(size_t)t * DP_HEAD + (pos - t * T)]; }
+}
+__global__ void __launch_bounds__(64) k_dp_mark(uint16_t* __restrict__ delta, uint32_t count, uint32_t T, uint32_t ntiles, const uint32_t* __restrict__ Et) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= ntiles) return;
+  uint32_t pos = Et[t];
+  const uint32_t end = (t + 1) * T < count ? (t + 1) * T : count;
+  while (pos < end) { const uint32_t d = delta[pos]; delta[pos] = (uint16_t)(d | DP_MARK); pos += d; }
+}
+__global__ void __launch_bounds__(DM_BLOCK) k_dp_tokens(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, const uint32_t* __restrict__ Ab,
+                                                        const uint32_t* __restrict__ Bb, size_t first, uint32_t count, unsigned mp0, unsigned mp1,
+                                                        const uint16_t* __restrict__ delta, uint32_t* __restrict__ tok, DpCarry* __restrict__ carry) {
+  const uint32_t i = blockIdx.x * DM_BLOCK + threadIdx.x;
+  if (i >= count || !(delta[i] & DP_MARK)) return;
+  unsigned sl = 0, sd = 0, fb = 0;
+  const uint32_t next = dp_walk<true>(D, n, Lw, Ab, Bb, first, count, i, sl, sd, mp0, mp1, tok, fb);
+  if (fb) atomicAdd(&carry[1].fallbacks, fb);
+  if (next >= count) { carry[1].entry = next - count; carry[1].sl = sl; carry[1].sd = sd; }  // the one reachable walk that ends the segment
+}
+struct DpNonZero {
+  __device__ bool operator()(const uint32_t& t) const { return t != 0; }
+};
+
 // one 8-byte word per lane: words 0..2 the matrix's header, then six words an entry
 __global__ void __launch_bounds__(DM_BLOCK) k_sparse_bincode(const uint32_t* __restrict__ ent_row, const uint32_t* __restrict__ ent_col,
                                                              const uint64_t* __restrict__ ent_val, size_t nnz, uint64_t nvx, uint64_t nvy,
@@ -155,7 +307,22 @@ struct sp_deflate {
   void* tmp = nullptr;
   size_t tmp_bytes = 0;
   uint8_t* pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2][5] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+  hipEvent_t ev[2][7] = {{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};
+  // the parse (sp_deflate_open_parse): per position of one segment 2 bytes of jumps, 4 of token words, 1536 / T of exits; the host gets tokens
+  bool parse = false;
+  uint32_t T = 0, G = 0;
+  uint16_t* delta = nullptr;
+  uint32_t *tok = nullptr, *X0 = nullptr, *X1 = nullptr, *Eg = nullptr, *Et = nullptr;
+  DpCarry* carry = nullptr;  // [nseg + 1]: carry[s] is segment s's entry
+  void* sel_tmp = nullptr;
+  size_t sel_bytes = 0;
+  size_t ntiles_of(size_t count) const { return (count + T - 1) / T; }
+  size_t ngroups_of(size_t count) const { return (count + (size_t)T * G - 1) / ((size_t)T * G); }
+  // pinned slot of the parse: [tokens: 4 (seg + 1)][their number: 8][the next segment's entry: 16][bytes: seg + DM_AHEAD]
+  uint32_t* pT(int k) const { return (uint32_t*)pin[k]; }
+  size_t* pN(int k) const { return (size_t*)(pin[k] + 4 * (seg + 1) + (4 * (seg + 1)) % 8); }
+  DpCarry* pC(int k) const { return (DpCarry*)((uint8_t*)pN(k) + 8); }
+  uint8_t* pDt(int k) const { return (uint8_t*)pN(k) + 24; }
   size_t first_of(size_t s) const { return s * seg; }
   size_t count_of(size_t s) const { return n - s * seg < seg ? n - s * seg : seg; }
   // pinned slot: [A: 4 seg][B: 4 seg][L: 2 seg][bytes: seg + DM_AHEAD]
@@ -176,7 +343,8 @@ void sp_deflate_close(sp_deflate* d) {
   for (uint8_t* p : d->pin)
     if (p) (void)hipHostFree(p);
   for (void* p : {(void*)d->dD_own, (void*)d->head, (void*)d->Lw, (void*)d->keys_in, (void*)d->keys_out, (void*)d->Ab, (void*)d->Bb, (void*)d->vals_in,
-                  (void*)d->vals_out, d->tmp})
+                  (void*)d->vals_out, d->tmp, (void*)d->delta, (void*)d->tok, (void*)d->X0, (void*)d->X1, (void*)d->Eg, (void*)d->Et, (void*)d->carry,
+                  d->sel_tmp})
     if (p) (void)hipFree(p);
   if (d->st) (void)hipStreamDestroy(d->st);
   delete d;
@@ -214,18 +382,39 @@ static int32_t deflate_open(sp_deflate* d, const uint8_t* data, int on_device) {
   HIPCHK(hipMalloc((void**)&d->vals_out, 4 * seg));
   HIPCHK(hipMalloc((void**)&d->Ab, 4 * (seg + 1)));
   HIPCHK(hipMalloc((void**)&d->Bb, 4 * seg));
-  for (uint8_t*& p : d->pin) HIPCHK(hipHostMalloc((void**)&p, 11 * seg + DM_AHEAD, hipHostMallocDefault));
+  if (d->parse) {
+    const size_t tiles = d->ntiles_of(seg), groups = d->ngroups_of(seg);
+    HIPCHK(rocprim::select(nullptr, d->sel_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t*)nullptr, seg + 1, DpNonZero(), d->st));
+    HIPCHK(hipMalloc(&d->sel_tmp, d->sel_bytes ? d->sel_bytes : 256));
+    HIPCHK(hipMalloc((void**)&d->delta, 2 * seg));
+    HIPCHK(hipMalloc((void**)&d->tok, 4 * (seg + 1)));
+    HIPCHK(hipMalloc((void**)&d->X0, 4 * (size_t)DP_HEAD * tiles));
+    HIPCHK(hipMalloc((void**)&d->X1, 4 * (size_t)DP_HEAD * groups));
+    HIPCHK(hipMalloc((void**)&d->Eg, 4 * groups));
+    HIPCHK(hipMalloc((void**)&d->Et, 4 * tiles));
+    HIPCHK(hipMalloc((void**)&d->carry, sizeof(DpCarry) * (d->nseg + 1)));
+    HIPCHK(hipMemsetAsync(d->carry, 0, sizeof(DpCarry) * (d->nseg + 1), d->st));
+    for (uint8_t*& p : d->pin) HIPCHK(hipHostMalloc((void**)&p, 4 * (seg + 1) + 8 + 24 + seg + DM_AHEAD, hipHostMallocDefault));
+  } else {
+    for (uint8_t*& p : d->pin) HIPCHK(hipHostMalloc((void**)&p, 11 * seg + DM_AHEAD, hipHostMallocDefault));
+  }
   HIPCHK(hipMemsetAsync(d->head, 0, 2 * DM_DICT, d->st));
   HIPCHK(hipMemsetAsync(d->Lw, 0, 2 * DM_DICT, d->st));
   HIPCHK(hipMemsetAsync(d->Ab, 0, 4, d->st));
   return SP_OK;
 }
-int32_t sp_deflate_open(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, sp_deflate** out) {
+static int32_t deflate_open_form(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, bool parse, size_t tile, size_t group,
+                                 sp_deflate** out) {
   if (!c || !out || (n && !data) || probes == 0 || probes > 0xFFF) return SP_EINVAL;
+  if (!tile) tile = 1024;
+  if (!group) group = 64;
+  if (parse && (tile < 512 || tile > 4096 || group < 2 || group > 4096)) return SP_EINVAL;  // a tile holds a jump (384) and fits the exits' LDS
   sp_deflate* d = new (std::nothrow) sp_deflate();
   if (!d) return SP_ENOMEM;
   d->ctx = c;
   d->n = n;
+  d->parse = parse;
+  d->T = (uint32_t)tile; d->G = (uint32_t)group;
   const size_t opt = (size_t)c->opt.v[OPT_DIGEST_SEGMENT];
   d->seg = n < opt ? (n < DM_DICT ? DM_DICT : n) : opt;  // a short input is one segment of its own length (never below the window)
   d->nseg = (n + d->seg - 1) / d->seg;
@@ -235,6 +424,12 @@ int32_t sp_deflate_open(sp_ctx* c, const uint8_t* data, size_t n, int on_device,
   if (rc != SP_OK) { sp_deflate_close(d); d = nullptr; }
   *out = d;
   return rc;
+}
+int32_t sp_deflate_open(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, sp_deflate** out) {
+  return deflate_open_form(c, data, n, on_device, probes, false, 0, 0, out);
+}
+int32_t sp_deflate_open_parse(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, sp_deflate** out) {
+  return deflate_open_form(c, data, n, on_device, probes, true, tile, group, out);
 }
 size_t sp_deflate_segments(const sp_deflate* d) { return d ? d->nseg : 0; }
 
@@ -266,10 +461,35 @@ int32_t sp_deflate_segment_start(sp_deflate* d, size_t s) {
   HIPCHK(hipEventRecord(d->ev[k][3], st));
   if (hipGetLastError() != hipSuccess) return SP_EHIP;
   const size_t nbytes = (n - first < count + DM_AHEAD ? n - first : count + DM_AHEAD);
-  HIPCHK(hipMemcpyAsync(d->pA(k), d->Ab + 1, 4 * count, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(d->pB(k), d->Bb, 4 * count, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(d->pL(k), Lseg, 2 * count, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(d->pD(k), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
+  if (d->parse) {
+    const uint32_t cnt = (uint32_t)count, T = d->T, G = d->G, tiles = (uint32_t)d->ntiles_of(count), groups = (uint32_t)d->ngroups_of(count);
+    const uint16_t* Lw = d->Lw;
+    const uint32_t *Ab = d->Ab, *Bb = d->Bb;
+    DpCarry* carry = d->carry + s;
+    HIPCHK(hipMemsetAsync(d->tok, 0, 4 * (count + 1), st));
+    HIPCHK(hipMemsetAsync(d->Eg, 0xFF, 4 * (size_t)groups, st));
+    HIPCHK(hipMemsetAsync(d->Et, 0xFF, 4 * (size_t)tiles, st));
+    hipLaunchKernelGGL(k_dp_jump, dm_grid(count), dim3(DM_BLOCK), 0, st, d->dD, n, Lw, Ab, Bb, first, cnt, d->mp[0], d->mp[1], d->delta);
+    hipLaunchKernelGGL(k_dp_exit, dim3(tiles), dim3(DM_BLOCK), 4 * (size_t)T, st, (const uint16_t*)d->delta, cnt, T, d->X0);
+    hipLaunchKernelGGL(k_dp_compose, dim3(groups), dim3(DP_HEAD), 0, st, (const uint32_t*)d->X0, cnt, T, G, d->X1);
+    hipLaunchKernelGGL(k_dp_top, dim3(1), dim3(64), 0, st, d->dD, n, Lw, Ab, Bb, first, cnt, d->mp[0], d->mp[1], d->tok, (const uint32_t*)d->X1, T, G, d->Eg, carry);
+    hipLaunchKernelGGL(k_dp_down, dim3((groups + 63) / 64), dim3(64), 0, st, (const uint32_t*)d->X0, cnt, T, G, groups, (const uint32_t*)d->Eg, d->Et);
+    hipLaunchKernelGGL(k_dp_mark, dim3((tiles + 63) / 64), dim3(64), 0, st, d->delta, cnt, T, tiles, (const uint32_t*)d->Et);
+    HIPCHK(hipEventRecord(d->ev[k][5], st));
+    hipLaunchKernelGGL(k_dp_tokens, dm_grid(count), dim3(DM_BLOCK), 0, st, d->dD, n, Lw, Ab, Bb, first, cnt, d->mp[0], d->mp[1], (const uint16_t*)d->delta, d->tok,
+                       carry);
+    if (hipGetLastError() != hipSuccess) return SP_EHIP;
+    // the compaction writes the dense list and its length straight into the pinned slot
+    HIPCHK(rocprim::select(d->sel_tmp, d->sel_bytes, (const uint32_t*)d->tok, d->pT(k), d->pN(k), count + 1, DpNonZero(), st));
+    HIPCHK(hipEventRecord(d->ev[k][6], st));
+    HIPCHK(hipMemcpyAsync(d->pC(k), carry + 1, sizeof(DpCarry), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->pDt(k), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
+  } else {
+    HIPCHK(hipMemcpyAsync(d->pA(k), d->Ab + 1, 4 * count, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->pB(k), d->Bb, 4 * count, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->pL(k), Lseg, 2 * count, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->pD(k), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
+  }
   if (s + 1 < d->nseg) {  // count == seg >= 32768 here: what the next segment needs of this one
     HIPCHK(hipMemcpyAsync(d->Ab, d->Ab + count, 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(d->Lw, d->Lw + count, 2 * DM_DICT, hipMemcpyDeviceToDevice, st));
@@ -281,7 +501,7 @@ int32_t sp_deflate_segment_start(sp_deflate* d, size_t s) {
 
 int32_t sp_deflate_segment_wait(sp_deflate* d, size_t s, size_t* first, size_t* count, const uint8_t** bytes, const uint16_t** L, const uint32_t** A,
                                 const uint32_t** B, double* ms) {
-  if (!d || s >= d->started || s + 2 < d->started) return SP_EINVAL;
+  if (!d || d->parse || s >= d->started || s + 2 < d->started) return SP_EINVAL;
   const int k = (int)(s & 1);
   HIPCHK(hipSetDevice(d->ctx->dev));
   HIPCHK(hipEventSynchronize(d->ev[k][4]));
@@ -298,6 +518,59 @@ int32_t sp_deflate_segment_wait(sp_deflate* d, size_t s, size_t* first, size_t* 
       ms[i] = t;
     }
   return SP_OK;
+}
+
+int32_t sp_deflate_segment_wait_tokens(sp_deflate* d, size_t s, size_t* first, size_t* count, const uint8_t** bytes, const uint32_t** tokens, size_t* ntok,
+                                       uint64_t* carry, double* ms) {
+  if (!d || !d->parse || s >= d->started || s + 2 < d->started) return SP_EINVAL;
+  const int k = (int)(s & 1);
+  HIPCHK(hipSetDevice(d->ctx->dev));
+  HIPCHK(hipEventSynchronize(d->ev[k][4]));
+  if (first) *first = d->first_of(s);
+  if (count) *count = d->count_of(s);
+  if (bytes) *bytes = d->pDt(k);
+  if (tokens) *tokens = d->pT(k);
+  if (ntok) *ntok = *d->pN(k);
+  if (carry) {
+    const DpCarry* c = d->pC(k);
+    carry[0] = d->first_of(s) + d->count_of(s) + c->entry; carry[1] = c->sl; carry[2] = c->sd; carry[3] = c->fallbacks;
+  }
+  if (ms) {
+    static const int order[7] = {0, 1, 2, 3, 5, 6, 4};  // links, search A, search B, reachability, tokens + compaction, copies
+    for (int i = 0; i < 6; i++) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, d->ev[k][order[i]], d->ev[k][order[i + 1]]));
+      ms[i] = t;
+    }
+  }
+  return SP_OK;
+}
+
+int32_t sp_deflate_tokens(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, uint32_t* tokens,
+                          size_t* ntok, uint64_t* info) {
+  if (!ntok) return SP_EINVAL;
+  sp_deflate* d = nullptr;
+  SPCHK(sp_deflate_open_parse(c, data, n, on_device, probes, tile, group, &d));
+  int32_t rc = SP_OK;
+  size_t total = 0;
+  uint64_t held = 0, fallbacks = 0;
+  for (size_t s = 0; s < d->nseg && rc == SP_OK; s++) {
+    const uint32_t* t;
+    size_t cnt = 0;
+    uint64_t carry[4];
+    rc = sp_deflate_segment_start(d, s);
+    if (rc == SP_OK) rc = sp_deflate_segment_wait_tokens(d, s, nullptr, nullptr, nullptr, &t, &cnt, carry, nullptr);
+    if (rc != SP_OK) break;
+    if (total + cnt > n) { rc = SP_EINVAL; break; }  // more tokens than positions: never, and never written past the caller's array
+    if (tokens) memcpy(tokens + total, t, 4 * cnt);
+    total += cnt;
+    if (carry[1] && s + 1 < d->nseg) held++;
+    fallbacks = carry[3];
+  }
+  *ntok = total;
+  if (info) { info[0] = held; info[1] = fallbacks; }
+  sp_deflate_close(d);
+  return rc;
 }
 
 int32_t sp_deflate_matches(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, uint16_t* L, uint32_t* A, uint32_t* B) {

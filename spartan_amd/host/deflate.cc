@@ -22,7 +22,9 @@
 // 0x78 0x01 (the `old_header` argument — an explicit API parameter, spz_instance_set_digest_header, never an environment switch).
 // Below the sequential deflater (the oracle of everything that follows, left as it was): the match search restated as one independent item
 // per input position (find_pure, deflate_matches_host — what csrc/deflate_match.hip runs on the device) and the same parser fed from match
-// tables instead of a dictionary (MatchParser, zlib_from_matches), which digest.cc runs behind the device search.
+// tables instead of a dictionary (MatchParser, zlib_from_matches), which digest.cc runs behind the device search. Last, the parse restated
+// as walks between FREE states (deflate_tokens_host — what the device parse of deflate_match.hip runs) and the coder fed from its tokens
+// (TokenCoder, zlib_from_tokens): record_literal, record_match, the block check and flush_block with no tables and no search.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -60,6 +62,7 @@ struct Tdefl {
   // the table-driven parser (MatchParser below) keeps no dictionary: the bytes of a stored block then come from the input itself
   const uint8_t* stored_src = nullptr;
   size_t stored_pos = 0;  // lz_dict_pos without the 32-bit wrap: where the current block began in stored_src
+  unsigned static_blocks = 0, stored_blocks = 0;  // counted for the token coder's tests; nothing reads them here
 
   void put(unsigned b, unsigned l) {
     bitbuf |= (uint64_t)b << bits_in;
@@ -265,11 +268,12 @@ struct Tdefl {
     const size_t saved_out = out.size();
     const uint64_t saved_buf = bitbuf;
     const unsigned saved_bits = bits_in;
-    if (total_lz_bytes < 48) start_static_block(); else start_dynamic_block();
+    if (total_lz_bytes < 48) { static_blocks++; start_static_block(); } else start_dynamic_block();
     compress_lz_codes();
     // if the block got expanded, forget it and send a stored block instead (the data is still in the dictionary)
     if (total_lz_bytes && (out.size() - saved_out + 1u) >= total_lz_bytes && (lookahead_pos - lz_dict_pos) <= dict_size) {
       out.resize(saved_out); bitbuf = saved_buf; bits_in = saved_bits;
+      stored_blocks++;
       put(0, 2);
       if (bits_in) put(0, 8 - bits_in);
       put(total_lz_bytes & 0xFFFF, 16);
@@ -562,6 +566,165 @@ std::vector<uint8_t> zlib_from_matches(const uint8_t* D, size_t n, const uint16_
   if (lookups) *lookups = mp.lookups;
   if (fallbacks) *fallbacks = mp.fallbacks;
   return mp.finish();
+}
+
+// ---- the parse restated as walks between free states (what the device parse of deflate_match.hip runs), and the coder over its tokens
+// The parser's state before a step is (p, saved_len, saved_dist); call it FREE when saved_len == 0. From a free state at p, read off
+// MatchParser::parse above: A[p] filtered is nothing (a literal at p, free at p + 1), a match of >= 128 (taken at once, free at p + len), or
+// a match that is HELD. A held match at q - 1 meets the look-up at q with init = its length: a longer one makes D[q - 1] a literal and is
+// itself taken (>= 128) or held in turn; otherwise the held match is emitted at q - 1 and the state is free at q - 1 + len. Held lengths
+// strictly grow from >= 3 and stay below 128, so a walk holds at most 125 times (positions p .. p + 124), its last step is at q <= p + 125
+// and the next free state F(p) is at most q + 258: 1 <= F(p) - p <= 383. Every token of a walk starts at a position of its own (a literal at
+// each chain position that lost, the match at the last), so the parse is one word per input position: tokens of the positions reachable
+// from the entry state under F. Nothing in a walk reads the coder's state; the coder needs of a token only what the block check after the
+// parser's STEP reads (lookahead_pos, dict_size), which two bits carry: TOK_CHECK (a check follows this token: a step that only holds emits
+// nothing and its check sees the numbers of the check before it, which did not fire or reset them) and TOK_HELD (a match is held when that
+// check runs: lookahead_pos is then one past the emitted bytes).
+namespace {
+inline uint32_t tok_lit(uint8_t c, uint32_t bits) { return TOK_VALID | bits | c; }
+inline uint32_t tok_match(unsigned len, unsigned dist, uint32_t bits) { return TOK_VALID | bits | (len << 15) | (dist - 1); }
+struct WalkState { size_t q; unsigned sl, sd; };  // next step at q; held match (sl, sd) found at q - 1, sl == 0: free
+// steps from `w` until the state is free again (after at least one step) or q reaches `end`, where the parser's segment loop stops too.
+// emit(position, token); lookup(q, init) -> dist | len << 16
+template <typename Lookup, typename Emit>
+inline void walk(const uint8_t* D, WalkState& w, size_t end, Lookup lookup, Emit emit) {
+  do {
+    const size_t q = w.q;
+    const uint32_t got = lookup(q, w.sl ? w.sl : MINM - 1);
+    unsigned cd = got & 0xFFFF, cl = got >> 16;
+    if ((cl == MINM && cd >= 8u * 1024u) || (unsigned)(q & DMASK) == cd) cd = cl = 0;
+    if (w.sl) {
+      if (cl > w.sl) {
+        if (cl >= 128) { emit(q - 1, tok_lit(D[q - 1], 0)); emit(q, tok_match(cl, cd, TOK_CHECK)); w.sl = 0; w.q = q + cl; }
+        else { emit(q - 1, tok_lit(D[q - 1], TOK_CHECK | TOK_HELD)); w.sl = cl; w.sd = cd; w.q = q + 1; }
+      } else {
+        emit(q - 1, tok_match(w.sl, w.sd, TOK_CHECK));
+        w.q = q - 1 + w.sl; w.sl = 0;
+      }
+    } else if (!cd) {
+      emit(q, tok_lit(D[q], TOK_CHECK)); w.q = q + 1;
+    } else if (cl >= 128) {
+      emit(q, tok_match(cl, cd, TOK_CHECK)); w.q = q + cl;
+    } else {
+      w.sl = cl; w.sd = cd; w.q = q + 1;
+    }
+  } while (w.sl && w.q < end);
+}
+}  // namespace
+
+size_t deflate_tokens_host(const uint8_t* D, size_t n, unsigned probes, const size_t geom[3], uint32_t* tokens, uint64_t counters[TOKC_COUNT]) {
+  std::vector<uint16_t> L(n ? n : 1);
+  std::vector<uint32_t> A(n ? n : 1), B(n ? n : 1);
+  deflate_links_host(D, n, L.data());
+  deflate_matches_host(D, n, probes, L.data(), A.data(), B.data());
+  unsigned mp[2];
+  probe_budget(probes, mp);
+  uint64_t own[TOKC_COUNT];
+  uint64_t* C = counters ? counters : own;
+  memset(C, 0, sizeof own);
+  const size_t tile = geom && geom[0] ? geom[0] : 1024, group = tile * (geom && geom[1] ? geom[1] : 64), seg = geom && geom[2] ? geom[2] : (n ? n : 1);
+  size_t ntok = 0, first = 0;
+  unsigned chain = 0;  // holds of the walk under way
+  auto lookup = [&](size_t q, unsigned init) -> uint32_t {
+    C[TOKC_LOOKUPS]++;
+    if (init == MINM - 1) { chain = 0; return A[q]; }
+    chain++;
+    if (held_after_filter(A[q - 1], q - 1) && (A[q - 1] >> 16) == init) return B[q];
+    C[TOKC_FALLBACKS]++;  // a lazy chain of three or more whose held length is not A[q - 1]'s: neither table answers
+    return find_pure(D, n, L.data(), 0, q, init, mp);
+  };
+  auto emit = [&](size_t pos, uint32_t t) {
+    tokens[ntok++] = t;
+    const unsigned len = (t >> 15) & 0x1FF;
+    if (len) {
+      const size_t a = pos - first, b = a + len - 1;  // a match starts in the segment under way (or one position before it: the prologue's)
+      if (pos >= first && b < seg && first + b < n) {
+        if (a / tile != b / tile) C[TOKC_SPAN_TILE]++;
+        if (a / group != b / group) C[TOKC_SPAN_GROUP]++;
+      }
+    }
+  };
+  WalkState w{0, 0, 0};
+  for (; first < n; first += seg) {
+    const size_t end = std::min(n, first + seg);
+    if (w.sl) C[TOKC_SEAM_HELD]++;  // the segment's entry is a held match: its first walk is resolved from the carried state
+    while (w.q < end) {
+      const size_t p = w.q, before = ntok;
+      const bool was_free = w.sl == 0;
+      walk(D, w, end, lookup, emit);
+      C[TOKC_WALKS]++;
+      if (was_free && !w.sl) C[TOKC_MAX_JUMP] = std::max<uint64_t>(C[TOKC_MAX_JUMP], w.q - p);
+      if (ntok - before == 1 && was_free && ((tokens[before] >> 15) & 0x1FF) >= 128) C[TOKC_FREE_LONG]++;
+      if (ntok - before >= 2 && !(tokens[ntok - 2] & TOK_CHECK)) C[TOKC_LIT_AND_LONG]++;
+    }
+  }
+  C[TOKC_TOKENS] = ntok;
+  return ntok;
+}
+
+// record_literal, record_match, the block check and flush_block of Tdefl over a token list: no tables, no dictionary, no search. The two
+// numbers flush_block's stored-block test reads are those of the parser's step the token closes (MatchParser::parse): the step at p with
+// lookahead la = min(258, n - p) starts from dict_size = min(p, 32768 - la) and moves m positions.
+struct TokenCoder::Impl {
+  Tdefl d;
+  size_t n = 0, pos = 0;    // input length, position of the next token
+  uint32_t s1 = 1, s2 = 0;  // Adler-32 so far
+  size_t adler_pos = 0;
+};
+TokenCoder::TokenCoder(size_t n, unsigned probes, bool old_header) : m(new Impl()) {
+  Tdefl& d = m->d;
+  memset(d.count, 0, sizeof d.count); memset(d.codes, 0, sizeof d.codes); memset(d.sizes, 0, sizeof d.sizes);
+  d.old_header = old_header;
+  d.probes = probes & 0xFFF;
+  m->n = n;
+}
+TokenCoder::~TokenCoder() { delete m; }
+void TokenCoder::code(const uint8_t* D, size_t bytes_end, const uint32_t* tokens, size_t ntok) {
+  Impl& s = *m;
+  Tdefl& d = s.d;
+  d.stored_src = D;
+  for (; s.adler_pos < bytes_end;) {  // Adler-32 of the input as it arrives
+    const size_t blk = std::min<size_t>(5552, bytes_end - s.adler_pos);
+    for (size_t k = 0; k < blk; k++) { s.s1 += D[s.adler_pos + k]; s.s2 += s.s1; }
+    s.s1 %= 65521; s.s2 %= 65521; s.adler_pos += blk;
+  }
+  for (size_t i = 0; i < ntok; i++) {
+    const uint32_t t = tokens[i];
+    const unsigned len = (t >> 15) & 0x1FF;
+    size_t step, move;  // the parser's step this token closes: where it looked, how far it moved
+    if (!len) {
+      d.record_literal((uint8_t)t);
+      step = s.pos + ((t & TOK_HELD) ? 1 : 0); move = 1;
+      s.pos += 1;
+    } else {
+      d.record_match(len, (t & 0x7FFF) + 1);
+      if (len >= 128) { step = s.pos; move = len; } else { step = s.pos + 1; move = len - 1; }  // taken at once | the held match of step - 1
+      s.pos += len;
+    }
+    if (!(t & TOK_CHECK)) continue;
+    const unsigned la = (unsigned)std::min<size_t>(MAXM, s.n - step);
+    d.lookahead_pos = (unsigned)(step + move);
+    d.dict_size = (unsigned)std::min<size_t>(std::min<size_t>(step, DICT - la) + move, DICT);
+    if (d.code_bytes > LZBUF - 8) { full_blocks++; d.flush_block(false); }
+    else if (d.total_lz_bytes > 31 * 1024 && ((d.code_bytes * 115) >> 7) >= d.total_lz_bytes) { ratio_blocks++; d.flush_block(false); }
+  }
+  tokens_coded += ntok;
+}
+std::vector<uint8_t> TokenCoder::finish() {
+  m->d.adler = (m->s2 << 16) | m->s1;
+  m->d.flush_block(true);
+  static_blocks = m->d.static_blocks; stored_blocks = m->d.stored_blocks;
+  return std::move(m->d.out);
+}
+std::vector<uint8_t> zlib_from_tokens(const uint8_t* D, size_t n, const uint32_t* tokens, size_t ntok, unsigned probes, bool old_header, size_t piece,
+                                      uint64_t blocks[4]) {
+  TokenCoder tc(n, probes, old_header);
+  if (!piece) piece = ntok ? ntok : 1;
+  for (size_t i = 0; i < ntok; i += piece) tc.code(D, n, tokens + i, std::min(piece, ntok - i));
+  if (!ntok) tc.code(D, n, tokens, 0);
+  std::vector<uint8_t> z = tc.finish();
+  if (blocks) { blocks[0] = tc.full_blocks; blocks[1] = tc.ratio_blocks; blocks[2] = tc.stored_blocks; blocks[3] = tc.static_blocks; }
+  return z;
 }
 
 std::vector<uint8_t> zlib_miniz_probes(const uint8_t* data, size_t n, unsigned probes, bool old_header) {

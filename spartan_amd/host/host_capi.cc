@@ -517,7 +517,7 @@ size_t spz_zlib_device(void* ctx, const uint8_t* data, size_t n, unsigned probes
   return guard((size_t)0, [&] {
     if (!ctx || (n && !data) || probes == 0 || probes > 0xFFF) throw bad_arguments("spz_zlib_device");
     DeflateStats s;
-    const std::vector<uint8_t> z = zlib_device(((Ctx*)ctx)->h, data, nullptr, n, probes, old_header != 0, &s);
+    const std::vector<uint8_t> z = zlib_device(((Ctx*)ctx)->h, data, nullptr, n, probes, old_header != 0, &s, 0);  // this entry is the host parser's
     stats_out(s, stats);
     return bytes_out(z, out, cap);
   });
@@ -526,6 +526,33 @@ size_t spz_instance_shape_bincode_device(void* inst, uint8_t* out, size_t cap) {
   return guard((size_t)0, [&] { return bytes_out(((Instance*)inst)->shape_bincode_device(), out, cap); });
 }
 void spz_instance_digest_stats(void* inst, double stats[12]) { stats_out(((Instance*)inst)->digest_stats, stats); }
+namespace {
+void stats_out_all(const DeflateStats& s, double* o, size_t cap) {
+  if (!o) return;
+  double v[17];
+  stats_out(s, v);
+  v[12] = s.parse; v[13] = s.tokens; v[14] = s.device_fallbacks; v[15] = s.ms_reach; v[16] = s.ms_emit;
+  memcpy(o, v, sizeof(double) * std::min<size_t>(cap, 17));
+}
+}  // namespace
+size_t spz_deflate_tokens_host(const uint8_t* data, size_t n, unsigned probes, const size_t* geom, uint32_t* tokens, uint64_t* counters) {
+  return deflate_tokens_host(data, n, probes, geom, tokens, counters);
+}
+size_t spz_zlib_from_tokens(const uint8_t* data, size_t n, const uint32_t* tokens, size_t ntok, unsigned probes, int old_header, size_t piece,
+                            uint8_t* out, size_t cap, uint64_t* blocks) {
+  return bytes_out(zlib_from_tokens(data, n, tokens, ntok, probes, old_header != 0, piece, blocks), out, cap);
+}
+size_t spz_zlib_device_parse(void* ctx, const uint8_t* data, size_t n, unsigned probes, int old_header, int parse, size_t tile, size_t group,
+                             uint8_t* out, size_t cap, double* stats, size_t stats_cap) {
+  return guard((size_t)0, [&] {
+    if (!ctx || (n && !data) || probes == 0 || probes > 0xFFF || parse < -1 || parse > 1) throw bad_arguments("spz_zlib_device_parse");
+    DeflateStats s;
+    const std::vector<uint8_t> z = zlib_device(((Ctx*)ctx)->h, data, nullptr, n, probes, old_header != 0, &s, parse, tile, group);
+    stats_out_all(s, stats, stats_cap);
+    return bytes_out(z, out, cap);
+  });
+}
+void spz_instance_digest_stats_all(void* inst, double* stats, size_t stats_cap) { stats_out_all(((Instance*)inst)->digest_stats, stats, stats_cap); }
 const char* spz_keccak_variant() { return keccak_f1600_variant(); }
 int spz_keccak_run_variant(const char* name, uint64_t state[25]) { return keccak_f1600_run_variant(name, state); }
 void spz_shake256(const uint8_t* in, size_t n, uint8_t* out, size_t outlen) { Shake256 s; s.absorb(in, n); s.squeeze(out, outlen); }

@@ -182,6 +182,10 @@ struct DeflateStats {
   double ms_links = 0, ms_search_a = 0, ms_search_b = 0, ms_download = 0;  // device time, from events on the search's stream
   double ms_parse = 0, ms_wait = 0, ms_stream = 0, ms_total = 0;            // host wall time: parse + coding, waiting for the device, building the stream
   double device = 0;                                                        // 1: the device-assisted path ran
+  // the device parse (digest.device = 2): 1 when it ran, tokens it handed over, look-ups it searched on the spot (those neither table answers),
+  // device time of the reachability kernels (jumps, exits, composition, entries, marks) and of the token kernel with its compaction.
+  // ms_parse is then the token coder alone, ms_download the copies of tokens and bytes, lookups / fallbacks stay 0 (nothing is looked up here)
+  double parse = 0, tokens = 0, device_fallbacks = 0, ms_reach = 0, ms_emit = 0;
 };
 
 // ---- instance ----
@@ -201,7 +205,8 @@ struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the m
   // use by compute_digest() (deflate.cc: a restatement of miniz's level-6 tdefl, what flate2's rust_backend runs — byte-identical to the
   // real C miniz 3.0.2 on the test corpus); a caller that holds the bytes of a real libspartan Instance may set them instead
   // (set_digest). With the option digest.device = 1 (the default) the stream is serialised and the deflater's match search runs on the
-  // device, and only its parser and Huffman coding run here (digest.cc; the same bytes). The computation is guarded: concurrent
+  // device, and only its parser and Huffman coding run here (digest.cc; the same bytes; digest.device = 2: the lazy parse on the device
+  // too, only the token coder here — 13 % faster at 2^20, not at 2^16: profiles/instance_digest_parse.txt). The computation is guarded: concurrent
   // NIZK::prove calls over one Instance compute it once; a caller that wants the deflate of a large shape (4.5 s at 2^20 with 9.4 M
   // entries, 19.9 s on the host alone: profiles/instance_digest.txt) out of its first prove calls compute_digest() right after
   // construction, as the reference's Instance::new does (lib.rs:228).
@@ -331,8 +336,43 @@ struct MatchParser {
 // one call over whole tables: equals zlib_miniz_probes(data, n, probes, old_header) byte for byte
 std::vector<uint8_t> zlib_from_matches(const uint8_t* data, size_t n, const uint16_t* L, const uint32_t* A, const uint32_t* B, unsigned probes,
                                        bool old_header, uint64_t* lookups = nullptr, uint64_t* fallbacks = nullptr);
-// zlib stream of n bytes at `data` (host memory) or `dev_data` (memory of the context's device), the matches searched on the device
-std::vector<uint8_t> zlib_device(sp_ctx* c, const uint8_t* data, const uint8_t* dev_data, size_t n, unsigned probes, bool old_header, DeflateStats* st);
+// The parse of that compressor restated as walks between free states (deflate.cc; on the device: the parse kernels of csrc/deflate_match.hip):
+// one 32-bit token per literal or match, in stream order. A literal carries its byte in bits 0..7 and length 0; a match (len, dist) carries
+// dist - 1 in bits 0..14 and len in bits 15..23. TOK_CHECK: tdefl's block check runs after this token (a literal emitted together with a match
+// of >= 128 has none); TOK_HELD: a match is held when that check runs (lookahead_pos is one past the emitted bytes). TOK_VALID is always
+// set, so that 0 is "no token starts here" in the device's one-word-per-position form.
+constexpr uint32_t TOK_VALID = 1u << 31, TOK_CHECK = 1u << 30, TOK_HELD = 1u << 29;
+// what deflate_tokens_host counts: conditions on an input that the tests ask for, not measurements
+enum TokCounter { TOKC_WALKS, TOKC_LOOKUPS, TOKC_FALLBACKS, TOKC_FREE_LONG, TOKC_LIT_AND_LONG, TOKC_SPAN_TILE, TOKC_SPAN_GROUP, TOKC_SEAM_HELD,
+                  TOKC_TOKENS, TOKC_MAX_JUMP, TOKC_COUNT };
+// The token list of D[0, n) over the host tables of deflate_matches_host; tokens holds up to n entries; returns their number. geom (may be
+// nullptr) = tile, tiles a group, segment length of the device parse this models: they change no token, only what the counters report —
+// walks, look-ups, look-ups neither table answered, matches of >= 128 taken from a free state, a literal and a match of >= 128 from one
+// step, matches spanning a tile / a group boundary inside a segment, segments entered with a held match, tokens, the longest jump F(p) - p.
+size_t deflate_tokens_host(const uint8_t* data, size_t n, unsigned probes, const size_t geom[3], uint32_t* tokens, uint64_t counters[TOKC_COUNT]);
+// tdefl's record_literal / record_match, block decisions, Huffman coding and bit output over such a token list, piece by piece (so that it
+// runs behind the device parse): code(D, bytes_end, tokens, ntok) takes the next ntok tokens; D[0, bytes_end) has arrived (Adler-32, stored
+// blocks) and covers every byte the tokens so far stand for.
+struct TokenCoder {
+  TokenCoder(size_t n, unsigned probes, bool old_header);
+  ~TokenCoder();
+  TokenCoder(const TokenCoder&) = delete;
+  void code(const uint8_t* D, size_t bytes_end, const uint32_t* tokens, size_t ntok);
+  std::vector<uint8_t> finish();  // the zlib stream; the coder is spent
+  uint64_t tokens_coded = 0, full_blocks = 0, ratio_blocks = 0, stored_blocks = 0, static_blocks = 0;  // blocks ended by the code-buffer rule / the 115/128 rule
+ private:
+  struct Impl;
+  Impl* m;
+};
+// one call over a whole list, fed `piece` tokens at a time (0: all at once): equals zlib_miniz_probes(data, n, probes, old_header) byte for byte.
+// blocks (may be nullptr) = blocks ended by the code-buffer rule, by the 115/128 rule, stored blocks, static blocks
+std::vector<uint8_t> zlib_from_tokens(const uint8_t* data, size_t n, const uint32_t* tokens, size_t ntok, unsigned probes, bool old_header,
+                                      size_t piece = 0, uint64_t blocks[4] = nullptr);
+// zlib stream of n bytes at `data` (host memory) or `dev_data` (memory of the context's device), the matches searched on the device.
+// parse: 0 = MatchParser over the downloaded tables, 1 = the parse on the device too and TokenCoder behind it, -1 = as digest.device says
+// (2: the device parse); tile, group: positions a tile and tiles a group of the device parse (0: the library's defaults)
+std::vector<uint8_t> zlib_device(sp_ctx* c, const uint8_t* data, const uint8_t* dev_data, size_t n, unsigned probes, bool old_header, DeflateStats* st,
+                                 int parse = -1, size_t tile = 0, size_t group = 0);
 // per-entry-point wall time of the option host.callstats (prover.cc), for driver files that cannot use its macro
 void callstats_add(const char* entry, double seconds);
 

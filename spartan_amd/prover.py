@@ -62,6 +62,10 @@ SIGNATURES = {
     "spz_zlib_from_matches": (sz, [vp, sz, vp, vp, vp, ctypes.c_uint, _i] + _BYTES + [vp]),
     "spz_zlib_device": (sz, [vp, vp, sz, ctypes.c_uint, _i] + _BYTES + [vp]),
     "spz_instance_shape_bincode_device": (sz, [vp] + _BYTES), "spz_instance_digest_stats": (None, [vp, vp]),
+    "spz_deflate_tokens_host": (sz, [vp, sz, ctypes.c_uint, vp, vp, vp]),
+    "spz_zlib_from_tokens": (sz, [vp, sz, vp, sz, ctypes.c_uint, _i, sz] + _BYTES + [vp]),
+    "spz_zlib_device_parse": (sz, [vp, vp, sz, ctypes.c_uint, _i, _i, sz, sz] + _BYTES + [vp, sz]),
+    "spz_instance_digest_stats_all": (None, [vp, vp, sz]),
     "spz_keccak_run_variant": (_i, [_s, vp]), "spz_shake256": (None, [vp, sz, vp, sz]),
     "spz_merlin_script": (sz, _SCRIPT), "spz_merlin_state": (None, _SCRIPT), "spz_merlin_challenge_from_state": (None, [vp, _s, vp, sz]),
     "spz_tape_draws": (None, [vp, _s, sz, vp]), "spz_seed_scalar": (None, [_s, _u64, vp]),
@@ -228,8 +232,8 @@ class Instance:
 
     def digest_stats(self):
         """figures of the last digest computation (see zlib_device); the host path (option digest.device = 0) fills ms_total only"""
-        st = (ctypes.c_double * 12)()
-        H.spz_instance_digest_stats(self.h, st)
+        st = (ctypes.c_double * len(DEFLATE_STATS))()
+        H.spz_instance_digest_stats_all(self.h, st, sz(len(DEFLATE_STATS)))
         return dict(zip(DEFLATE_STATS, st))
 
     def shape_bincode_device(self):
@@ -365,21 +369,39 @@ def keccak_variant():
 
 
 DEFLATE_STATS = ("lookups", "fallbacks", "segments", "ms_links", "ms_search_a", "ms_search_b", "ms_download", "ms_parse", "ms_wait", "ms_stream",
-                 "ms_total", "device")
+                 "ms_total", "device", "parse", "tokens", "device_fallbacks", "ms_reach", "ms_emit")
 
 
-def zlib_device(ctx, data, probes=128, old_header=False):
+def zlib_device(ctx, data, probes=128, old_header=False, parse=0, tile=0, group=0):
     """(zlib stream of `data` as miniz writes it at this tdefl probe count, stats): the device-assisted deflate the instance digest runs over
-    bincode(shape) — match search on the GPU in segments of the option digest.segment, parser and Huffman coding on the calling thread.
+    bincode(shape) — match search on the GPU in segments of the option digest.segment, parser and Huffman coding on the calling thread; with
+    parse = 1 the lazy parse on the GPU too (tiles of `tile` positions, groups of `group` tiles; 0: the defaults) and only the token coder on
+    the calling thread; parse = None: as the option digest.device says (2 = the device parse), which is what Instance.digest() follows.
     stats: lookups and those neither match table answered, segments, device ms of links / search A / search B / downloads, host ms of parse /
-    wait / stream / total."""
+    wait / stream / total; parse = 1.0 when the device parsed, its tokens, the look-ups it searched on the spot, device ms of the reachability
+    kernels and of the token kernel with its compaction (ms_parse is then the token coder alone)."""
     data = bytes(data)
     cap = 2 * len(data) + 1024
-    out = (ctypes.c_uint8 * cap)(); st = (ctypes.c_double * 12)()
-    n = H.spz_zlib_device(ctx.h, data, sz(len(data)), ctypes.c_uint(probes), 1 if old_header else 0, out, sz(cap), st)
+    out = (ctypes.c_uint8 * cap)(); st = (ctypes.c_double * len(DEFLATE_STATS))()
+    n = H.spz_zlib_device_parse(ctx.h, data, sz(len(data)), ctypes.c_uint(probes), 1 if old_header else 0, -1 if parse is None else int(parse),
+                                sz(tile), sz(group), out, sz(cap), st, sz(len(DEFLATE_STATS)))
     if n == 0:
         raise SpartanHipError(_failed("zlib_device"))
     return bytes(out[:n]), dict(zip(DEFLATE_STATS, st))
+
+
+def deflate_tokens(ctx, data, probes=128, tile=0, group=0):
+    """test hook: (tokens of tdefl's lazy parse of `data` as the device produces them (sp_deflate_tokens), segments entered with a held match,
+    look-ups the device searched on the spot). A token is one 32-bit word, see include/spartan_hip.h."""
+    from .capi import lib
+    data = bytes(data)
+    n = len(data)
+    tok = (ctypes.c_uint32 * max(1, n))(); ntok = ctypes.c_size_t(0); info = (ctypes.c_uint64 * 2)()
+    buf = (ctypes.c_uint8 * max(1, n)).from_buffer_copy(data) if n else (ctypes.c_uint8 * 1)()
+    rc = lib.sp_deflate_tokens(ctx.raw(), buf, sz(n), ctypes.c_int(0), ctypes.c_uint32(probes), sz(tile), sz(group), tok, ctypes.byref(ntok), info)
+    if rc != 0:
+        raise SpartanHipError("sp_deflate_tokens failed: %d" % rc)
+    return tok, ntok.value, info[0], info[1]
 
 
 def seed_scalar(domain, seed):
