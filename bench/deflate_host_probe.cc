@@ -1,6 +1,7 @@
 // Stand-alone host program over spartan_amd/host/deflate.cc (no device, no Python): two uses.
-//   check   the token model and the token coder against the sequential deflater on a few inputs; built with sanitizers this is the
-//           host-code sanitizer run of the deflate restatements:
+//   check   the token model, the token coder and the parser over match tables (whole, and fed in segments of 32 768 and 49 999 positions as
+//           it is behind the device search) against the sequential deflater on a few inputs; built with sanitizers this is the host-code
+//           sanitizer run of the deflate restatements:
 //             clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
 //                 bench/deflate_host_probe.cc spartan_amd/host/deflate.cc -o deflate_host_probe_san && ./deflate_host_probe_san check
 //   time K  where the host's time goes on bincode(shape) of a 2^K instance (three entries a row and matrix, random scalars: the bytes of
@@ -67,6 +68,20 @@ int check() {
       const std::vector<uint8_t> want = zlib_miniz_probes(x.data(), x.size(), probes);
       const bool ok = zlib_from_tokens(x.data(), x.size(), tok.data(), k, probes, false, 0, blocks) == want &&
                       zlib_from_tokens(x.data(), x.size(), tok.data(), k, probes, false, 777) == want;
+      // the parser over host tables, fed as digest.cc feeds it behind the device search: segment by segment
+      const size_t n = x.size();
+      std::vector<uint16_t> L(n ? n : 1);
+      std::vector<uint32_t> A(n ? n : 1), B(n ? n : 1);
+      deflate_links_host(x.data(), n, L.data());
+      deflate_matches_host(x.data(), n, probes, L.data(), A.data(), B.data());
+      for (size_t seg : {(size_t)32768, (size_t)49999}) {
+        MatchParser mp(n, probes, false);
+        for (size_t first = 0; first < n; first += seg) mp.parse(x.data(), first, std::min(seg, n - first), L.data() + first, A.data() + first, B.data() + first);
+        const bool same = mp.finish() == want;
+        printf("%-16s %4u probes: MatchParser in segments of %5zu: %8llu look-ups, %6llu searched on the spot: %s\n", in.first.c_str(), probes, seg,
+               (unsigned long long)mp.lookups, (unsigned long long)mp.fallbacks, same ? "equal" : "DIFFERS");
+        bad += !same;
+      }
       printf("%-16s %4u probes: %8zu tokens, %6llu look-ups searched on the spot, longest jump %3llu, blocks full/ratio/stored/static %llu/%llu/%llu/%llu: %s\n",
              in.first.c_str(), probes, k, (unsigned long long)cnt[TOKC_FALLBACKS], (unsigned long long)cnt[TOKC_MAX_JUMP], (unsigned long long)blocks[0],
              (unsigned long long)blocks[1], (unsigned long long)blocks[2], (unsigned long long)blocks[3], ok ? "equal" : "DIFFERS");

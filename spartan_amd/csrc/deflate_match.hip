@@ -4,23 +4,22 @@
 //   sp_deflate_*         tdefl's hash-chain match search, one input position per lane; and, for a handle opened by sp_deflate_open_parse,
 //                        tdefl's lazy PARSE over the tables it fills, so that the host receives tokens instead of tables
 // The block decisions and the Huffman coding are sequential and stay on the host (deflate.cc: MatchParser over tables, TokenCoder over tokens).
+// tdefl's rules themselves — hash, probe budget, find, the candidate filter, walk, the token word — are tdefl_rules.hpp, which the host runs
+// too; this file holds the kernels that apply them a position per lane, and the segment pipeline around them.
 //
-// The search, per position p of the input D[0, n) (names as in deflate.cc, find_match):
-//   links   h(p) = ((D[p] << 10) ^ (D[p+1] << 5) ^ D[p+2]) & 32767;  L[p] = low 16 bits of the greatest q < p with h(q) == h(p), else 0.
-//           Within a segment: a stable radix sort of the positions by h (rocPRIM); an element takes the position before it in its group,
-//           the first of a group takes the head carried from the segments before; the last of a group becomes the new head.
-//   find    find_match with lookahead min(258, n - p), dict_size min(p, 32768 - lookahead), dict[q + k] = D[q + k] and next[q] = L[q]:
-//           within dict_size the ring slots tdefl reads still hold exactly these. Probe budget, three-hop inner loop, c0/c1 filter, the
-//           dist == 0 break and the early return at the longest match are as in the host code.
+// The search, per position p of the input D[0, n):
+//   links   L[p] = low 16 bits of the greatest q < p with hash3(q) == hash3(p), else 0. Within a segment: a stable radix sort of the
+//           positions by hash (rocPRIM); an element takes the position before it in its group, the first of a group takes the head carried
+//           from the segments before; the last of a group becomes the new head.
 //   A[p] = find(p, 2);  B[p] = find(p, len(A[p-1])) where A[p-1] leaves the parser's filter as a held match.
-// A segment needs of its predecessors: head[32768], the last 32768 links, A[first - 1]. Every index below is bounded by construction:
-//   D[p + k], k < lookahead <= n - p;  D[cand + k], cand < p;  L window index cand - first + 32768 with cand >= p - 32768 + lookahead >= first - 32768.
+// A segment needs of its predecessors: head[32768], the last 32768 links, A[first - 1]. The link window Lw holds L[first - 32768, first +
+// count), so find's Lfirst is first - 32768 (modulo 2^64 in segment 0, whose first 32768 slots no search reaches): window index
+// cand - first + 32768 with cand >= p - 32768 + lookahead >= first - 32768.
 //
-// The parse (names as in deflate.cc, `walk`): the parser's state is FREE when it holds no match. From a free state at p everything up to
-// the next free state F(p) is a function of D, A, B and, for the rare look-up neither table answers, dm_find; 1 <= F(p) - p <= 383 (a walk
-// holds at most 125 times, each longer than the last and below 128, then takes at most 258). The tokens are those of the walks from the
-// positions REACHABLE from the segment's entry under F. Per segment of `count` positions, tiles of T and groups of G tiles (DP_HEAD = 384 <=
-// T, so a jump never skips a tile and enters one within its first 384 positions):
+// The parse: from a free state at p everything up to the next free state F(p) is a function of D, A, B and, for the rare look-up neither
+// table answers, find; 1 <= F(p) - p <= 383 (tdefl_rules.hpp, walk). The tokens are those of the walks from the positions REACHABLE from
+// the segment's entry under F. Per segment of `count` positions, tiles of T and groups of G tiles (DP_HEAD = 384 <= T, so a jump never
+// skips a tile and enters one within its first 384 positions):
 //   k_dp_jump     one lane a position: delta[i] = F(i) - i by the walk itself, nothing written but the 16-bit delta (a walk stops at the
 //                 segment's end as the parser's loop does: delta then reaches exactly `count`, with a match still held)
 //   k_dp_exit     one workgroup a tile: pointer doubling in LDS, log2(T) + 1 rounds, gives every position of the tile its exit, the first
@@ -37,27 +36,26 @@
 // Scratch per position of one segment: about 30 bytes of the search, plus 2 of jumps, 4 of token words and 1536 / T of exits: about 38; the
 // pinned slots hold 5 bytes a position (token words and the bytes) instead of 11.
 // The longest dependent chain is log2(T) + 3 G + count / (T G) + T steps instead of `count`. Every index is bounded: a walk looks up only
-// q < count; delta, tok (count + 1 words) and the marks are indexed by positions < count; X0 / X1 by (tile or group, offset < 384) with
-// offset = position - start of the tile or group it lies in, which a jump of at most 383 from before that start keeps below 384.
+// positions below first + count; delta, tok (count + 1 words) and the marks are indexed by positions < count; X0 / X1 by (tile or group,
+// offset < 384) with offset = position - start of the tile or group it lies in, which a jump of at most 383 from before that start keeps
+// below 384.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 
 #include "internal.hpp"
+#include "tdefl_rules.hpp"
 
 namespace {
 constexpr unsigned DM_BLOCK = 256;       // one position per lane, four wavefronts a workgroup
-constexpr unsigned DM_DICT = 32768, DM_MAXM = 258, DM_MINM = 3, DM_HBITS = 15;
-constexpr size_t DM_AHEAD = DM_MAXM;     // bytes past a segment's end its parser reads (the lookahead of its last position)
+constexpr unsigned DM_DICT = tdefl::DICT;
+constexpr size_t DM_AHEAD = tdefl::MAXM;  // bytes past a segment's end its parser reads (the lookahead of its last position)
 
-__device__ __forceinline__ unsigned dm_hash(const uint8_t* __restrict__ D, size_t p) {
-  return (((unsigned)D[p] << 10) ^ ((unsigned)D[p + 1] << 5) ^ (unsigned)D[p + 2]) & (DM_DICT - 1);
-}
-// keys[i] = h(first + i), vals[i] = i for the m positions of the segment that have three bytes
+// keys[i] = hash3(first + i), vals[i] = i for the m positions of the segment that have three bytes
 __global__ void __launch_bounds__(DM_BLOCK) k_dm_hash(const uint8_t* __restrict__ D, size_t first, uint32_t m, uint16_t* __restrict__ keys,
                                                       uint32_t* __restrict__ vals) {
   const uint32_t i = blockIdx.x * DM_BLOCK + threadIdx.x;
   if (i >= m) return;
-  keys[i] = (uint16_t)dm_hash(D, first + i);
+  keys[i] = (uint16_t)tdefl::hash3(D + first + i);
   vals[i] = i;
 }
 // sorted (stable) by hash: within a group the positions ascend
@@ -78,69 +76,13 @@ __global__ void __launch_bounds__(DM_BLOCK) k_dm_heads(const uint16_t* __restric
   if (i == m - 1 || keys[i + 1] != k) head[k] = (uint16_t)(first_lo + vals[i]);
 }
 
-__device__ __forceinline__ uint32_t dm_pack(unsigned dist, unsigned len) { return dist | (len << 16); }
-__device__ __forceinline__ uint32_t dm_ld32(const uint8_t* p) {  // any alignment
-  uint32_t x;
-  __builtin_memcpy(&x, p, 4);
-  return x;
-}
-// Lw[q - first + 32768] = L[q]
-__device__ uint32_t dm_find(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, size_t first, size_t p, unsigned init, unsigned mp0,
-                            unsigned mp1) {
-  const size_t left = n - p;
-  const unsigned la = left < DM_MAXM ? (unsigned)left : DM_MAXM;
-  const unsigned max_dist = p < (size_t)(DM_DICT - la) ? (unsigned)p : DM_DICT - la;
-  unsigned dist = 0, best = 0, match_len = init;
-  if (la <= match_len) return dm_pack(0, init);
-  unsigned probes_left = match_len >= 32 ? mp1 : mp0;
-  const uint8_t* s = D + p;
-  uint8_t c0 = s[match_len], c1 = s[match_len - 1];
-  size_t cand = p;
-  for (;;) {
-    for (;;) {
-      if (--probes_left == 0) return dm_pack(best, match_len);
-      bool hit = false;
-#pragma unroll 1
-      for (int k = 0; k < 3 && !hit; k++) {
-        const unsigned nx = Lw[(cand + DM_DICT) - first];
-        if (!nx || (dist = (((unsigned)p - nx) & 0xFFFFu)) > max_dist) return dm_pack(best, match_len);
-        cand = p - dist;
-        if (D[cand + match_len] == c0 && D[cand + match_len - 1] == c1) hit = true;
-      }
-      if (hit) break;
-    }
-    if (!dist) break;
-    const uint8_t* q = D + cand;
-    unsigned probe_len = 0;
-    bool differ = false;
-    while (probe_len + 4 <= la) {
-      const uint32_t x = dm_ld32(s + probe_len) ^ dm_ld32(q + probe_len);
-      if (x) { probe_len += (unsigned)(__ffs((int)x) - 1) >> 3; differ = true; break; }
-      probe_len += 4;
-    }
-    if (!differ)
-      while (probe_len < la && s[probe_len] == q[probe_len]) probe_len++;
-    if (probe_len > match_len) {
-      best = dist;
-      if ((match_len = probe_len) == la) break;
-      c0 = s[match_len]; c1 = s[match_len - 1];
-    }
-  }
-  return dm_pack(best, match_len);
-}
-// does A[pos] = a leave the parser's filter as a held match (deflate.cc, held_after_filter)
-__device__ __forceinline__ bool dm_held(uint32_t a, size_t pos) {
-  const unsigned dist = a & 0xFFFFu, len = a >> 16;
-  if (!dist) return false;
-  if ((len == DM_MINM && dist >= 8192u) || (unsigned)(pos & (DM_DICT - 1)) == dist) return false;
-  return len < 128;
-}
-// Ab[0] = A[first - 1] (0 before the first position), Ab[1 + i] = A[first + i]
+// Lw[q - first + 32768] = L[q];  Ab[0] = A[first - 1] (0 before the first position), Ab[1 + i] = A[first + i];  Bb[i] = B[first + i]
 __global__ void __launch_bounds__(DM_BLOCK) k_dm_search_a(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, size_t first, uint32_t count,
                                                           unsigned mp0, unsigned mp1, uint32_t* __restrict__ Ab) {
   const uint32_t i = blockIdx.x * DM_BLOCK + threadIdx.x;
   if (i >= count) return;
-  Ab[1 + i] = dm_find(D, n, Lw, first, first + i, DM_MINM - 1, mp0, mp1);
+  const unsigned mp[2] = {mp0, mp1};
+  Ab[1 + i] = tdefl::find(D, n, Lw, first - DM_DICT, first + i, tdefl::MINM - 1, mp);
 }
 __global__ void __launch_bounds__(DM_BLOCK) k_dm_search_b(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, size_t first, uint32_t count,
                                                           unsigned mp0, unsigned mp1, const uint32_t* __restrict__ Ab, uint32_t* __restrict__ Bb) {
@@ -148,59 +90,38 @@ __global__ void __launch_bounds__(DM_BLOCK) k_dm_search_b(const uint8_t* __restr
   if (i >= count) return;
   const size_t p = first + i;
   const uint32_t a = Ab[i];
-  Bb[i] = (p && dm_held(a, p - 1)) ? dm_find(D, n, Lw, first, p, a >> 16, mp0, mp1) : 0u;
+  const unsigned mp[2] = {mp0, mp1};
+  Bb[i] = (p && tdefl::held(a, p - 1)) ? tdefl::find(D, n, Lw, first - DM_DICT, p, a >> 16, mp) : 0u;
 }
 
 // ---- the parse: walks between free states
 constexpr uint32_t DP_HEAD = 384;                    // 1 + the longest jump: the positions of a tile a walk from before it can enter at
-constexpr uint32_t DP_NONE = 0xFFFFFFFFu;
-constexpr uint32_t TOK_VALID = 1u << 31, TOK_CHECK = 1u << 30, TOK_HELD = 1u << 29;   // as in host/libspartan.hpp
 constexpr uint32_t DP_MARK = 0x8000u;
 struct DpCarry { uint32_t entry, sl, sd, fallbacks; };  // a segment's entry: position relative to its first, the held match (sl == 0: free)
-__device__ __forceinline__ uint32_t dp_lit(unsigned c, uint32_t bits) { return TOK_VALID | bits | c; }
-__device__ __forceinline__ uint32_t dp_match(unsigned len, unsigned dist, uint32_t bits) { return TOK_VALID | bits | (len << 15) | (dist - 1); }
-// deflate.cc, walk(): steps from (q, sl, sd) until the state is free again or q reaches count. Positions are relative to `first`; tok[1 + q]
-// is position q's word. Returns the next step's position (> count when a match crosses the segment's end); sl, sd: the match then held.
+// tdefl::walk from the state (first + q, sl, sd) over the segment's tables: the look-up is A when free, B when A[p - 1] is held at exactly
+// this length, else searched on the spot; tok[1 + i] is position first + i's word. Returns the next step's position relative to `first`
+// (> count when a match crosses the segment's end); sl, sd: the match then held.
 template <bool EMIT>
-__device__ uint32_t dp_walk(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, const uint32_t* __restrict__ Ab,
-                            const uint32_t* __restrict__ Bb, size_t first, uint32_t count, uint32_t q, unsigned& sl, unsigned& sd, unsigned mp0,
-                            unsigned mp1, uint32_t* __restrict__ tok, unsigned& fallbacks) {
-  do {
-    const size_t p = first + q;
-    uint32_t got;
-    if (!sl) {
-      got = Ab[1 + q];
-    } else {
-      const uint32_t a = Ab[q];  // A[p - 1]
-      if (dm_held(a, p - 1) && (a >> 16) == sl) got = Bb[q];
-      else { got = dm_find(D, n, Lw, first, p, sl, mp0, mp1); fallbacks++; }
-    }
-    unsigned cd = got & 0xFFFFu, cl = got >> 16;
-    if ((cl == DM_MINM && cd >= 8192u) || (unsigned)(p & (DM_DICT - 1)) == cd) cd = cl = 0;
-    if (sl) {
-      if (cl > sl) {
-        if (cl >= 128) {
-          if (EMIT) { tok[q] = dp_lit(D[p - 1], 0); tok[1 + q] = dp_match(cl, cd, TOK_CHECK); }
-          sl = 0; q += cl;
-        } else {
-          if (EMIT) tok[q] = dp_lit(D[p - 1], TOK_CHECK | TOK_HELD);
-          sl = cl; sd = cd; q += 1;
-        }
-      } else {
-        if (EMIT) tok[q] = dp_match(sl, sd, TOK_CHECK);
-        q += sl - 1; sl = 0;
-      }
-    } else if (!cd) {
-      if (EMIT) tok[1 + q] = dp_lit(D[p], TOK_CHECK);
-      q += 1;
-    } else if (cl >= 128) {
-      if (EMIT) tok[1 + q] = dp_match(cl, cd, TOK_CHECK);
-      q += cl;
-    } else {
-      sl = cl; sd = cd; q += 1;
-    }
-  } while (sl && q < count);
-  return q;
+__device__ __forceinline__ uint32_t dp_segment_walk(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, const uint32_t* __restrict__ Ab,
+                                                    const uint32_t* __restrict__ Bb, size_t first, uint32_t count, uint32_t q, unsigned& sl, unsigned& sd,
+                                                    unsigned mp0, unsigned mp1, uint32_t* __restrict__ tok, unsigned& fallbacks) {
+  const unsigned mp[2] = {mp0, mp1};
+  tdefl::WalkState w{first + q, sl, sd};
+  tdefl::walk(
+      D, w, first + count,
+      [&](size_t p, unsigned init) -> uint32_t {
+        const size_t i = p - first;
+        if (init == tdefl::MINM - 1) return Ab[1 + i];
+        const uint32_t a = Ab[i];  // A[p - 1]
+        if (tdefl::held(a, p - 1) && (a >> 16) == init) return Bb[i];
+        fallbacks++;
+        return tdefl::find(D, n, Lw, first - DM_DICT, p, init, mp);
+      },
+      [&](size_t pos, uint32_t t) {
+        if (EMIT) tok[1 + pos - first] = t;
+      });
+  sl = w.sl; sd = w.sd;
+  return (uint32_t)(w.q - first);
 }
 __global__ void __launch_bounds__(DM_BLOCK) k_dp_jump(const uint8_t* __restrict__ D, size_t n, const uint16_t* __restrict__ Lw, const uint32_t* __restrict__ Ab,
                                                       const uint32_t* __restrict__ Bb, size_t first, uint32_t count, unsigned mp0, unsigned mp1,
@@ -208,7 +129,7 @@ __global__ void __launch_bounds__(DM_BLOCK) k_dp_jump(const uint8_t* __restrict_
   const uint32_t i = blockIdx.x * DM_BLOCK + threadIdx.x;
   if (i >= count) return;
   unsigned sl = 0, sd = 0, fb = 0;
-  const uint32_t next = dp_walk<false>(D, n, Lw, Ab, Bb, first, count, i, sl, sd, mp0, mp1, nullptr, fb);
+  const uint32_t next = dp_segment_walk<false>(D, n, Lw, Ab, Bb, first, count, i, sl, sd, mp0, mp1, nullptr, fb);
   delta[i] = (uint16_t)(next - i);  // 1 .. 383
 }
 // dynamic LDS: two arrays of T 16-bit tile-relative targets (< T + 384)
@@ -242,7 +163,7 @@ __global__ void k_dp_top(const uint8_t* __restrict__ D, size_t n, const uint16_t
   if (blockIdx.x || threadIdx.x) return;
   uint32_t pos = carry[0].entry;
   unsigned sl = carry[0].sl, sd = carry[0].sd, fb = 0;
-  if (sl && pos < count) pos = dp_walk<true>(D, n, Lw, Ab, Bb, first, count, pos, sl, sd, mp0, mp1, tok, fb);
+  if (sl && pos < count) pos = dp_segment_walk<true>(D, n, Lw, Ab, Bb, first, count, pos, sl, sd, mp0, mp1, tok, fb);
   if (pos >= count) { carry[1].entry = pos - count; carry[1].sl = sl; carry[1].sd = sd; carry[1].fallbacks = carry[0].fallbacks + fb; return; }
   carry[1].fallbacks = carry[0].fallbacks + fb;  // the token kernel adds its own
   const uint32_t GT = G * T;
@@ -269,7 +190,7 @@ __global__ void __launch_bounds__(DM_BLOCK) k_dp_tokens(const uint8_t* __restric
   const uint32_t i = blockIdx.x * DM_BLOCK + threadIdx.x;
   if (i >= count || !(delta[i] & DP_MARK)) return;
   unsigned sl = 0, sd = 0, fb = 0;
-  const uint32_t next = dp_walk<true>(D, n, Lw, Ab, Bb, first, count, i, sl, sd, mp0, mp1, tok, fb);
+  const uint32_t next = dp_segment_walk<true>(D, n, Lw, Ab, Bb, first, count, i, sl, sd, mp0, mp1, tok, fb);
   if (fb) atomicAdd(&carry[1].fallbacks, fb);
   if (next >= count) { carry[1].entry = next - count; carry[1].sl = sl; carry[1].sd = sd; }  // the one reachable walk that ends the segment
 }
@@ -318,18 +239,18 @@ struct sp_deflate {
   size_t sel_bytes = 0;
   size_t ntiles_of(size_t count) const { return (count + T - 1) / T; }
   size_t ngroups_of(size_t count) const { return (count + (size_t)T * G - 1) / ((size_t)T * G); }
-  // pinned slot of the parse: [tokens: 4 (seg + 1)][their number: 8][the next segment's entry: 16][bytes: seg + DM_AHEAD]
-  uint32_t* pT(int k) const { return (uint32_t*)pin[k]; }
-  size_t* pN(int k) const { return (size_t*)(pin[k] + 4 * (seg + 1) + (4 * (seg + 1)) % 8); }
-  DpCarry* pC(int k) const { return (DpCarry*)((uint8_t*)pN(k) + 8); }
-  uint8_t* pDt(int k) const { return (uint8_t*)pN(k) + 24; }
   size_t first_of(size_t s) const { return s * seg; }
   size_t count_of(size_t s) const { return n - s * seg < seg ? n - s * seg : seg; }
-  // pinned slot: [A: 4 seg][B: 4 seg][L: 2 seg][bytes: seg + DM_AHEAD]
-  uint32_t* pA(int k) const { return (uint32_t*)pin[k]; }
-  uint32_t* pB(int k) const { return (uint32_t*)(pin[k] + 4 * seg); }
-  uint16_t* pL(int k) const { return (uint16_t*)(pin[k] + 8 * seg); }
-  uint8_t* pD(int k) const { return pin[k] + 10 * seg; }
+  // byte offsets into a pinned slot, set once at open. A and the tokens stand at 0.
+  //   tables  [A: 4 seg][B: 4 seg][L: 2 seg][bytes: seg + DM_AHEAD]
+  //   parse   [tokens: 4 (seg + 1), padded to 8][their number: 8][the next segment's entry: 16][bytes: seg + DM_AHEAD]
+  struct Slot { size_t B = 0, L = 0, N = 0, C = 0, D = 0, bytes = 0; } slot;
+  void lay_out_slot() {
+    if (parse) { slot.N = (4 * (seg + 1) + 7) / 8 * 8; slot.C = slot.N + 8; slot.D = slot.C + sizeof(DpCarry); }
+    else { slot.B = 4 * seg; slot.L = 8 * seg; slot.D = 10 * seg; }
+    slot.bytes = slot.D + seg + DM_AHEAD;
+  }
+  template <typename T_> T_* at(int k, size_t off) const { return (T_*)(pin[k] + off); }
 };
 
 extern "C" {
@@ -369,9 +290,9 @@ static int32_t deflate_open(sp_deflate* d, const uint8_t* data, int on_device) {
   const size_t last = d->n - (d->nseg - 1) * seg, last_m = last > 2 ? last - 2 : 1;
   size_t tmp_last = 0;
   HIPCHK(rocprim::radix_sort_pairs(nullptr, d->tmp_bytes, (const uint16_t*)nullptr, (uint16_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, seg, 0u,
-                                   DM_HBITS, d->st));
+                                   tdefl::HBITS, d->st));
   HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_last, (const uint16_t*)nullptr, (uint16_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, last_m, 0u,
-                                   DM_HBITS, d->st));
+                                   tdefl::HBITS, d->st));
   if (tmp_last > d->tmp_bytes) d->tmp_bytes = tmp_last;
   HIPCHK(hipMalloc(&d->tmp, d->tmp_bytes ? d->tmp_bytes : 256));
   HIPCHK(hipMalloc((void**)&d->head, 2 * DM_DICT));
@@ -394,10 +315,8 @@ static int32_t deflate_open(sp_deflate* d, const uint8_t* data, int on_device) {
     HIPCHK(hipMalloc((void**)&d->Et, 4 * tiles));
     HIPCHK(hipMalloc((void**)&d->carry, sizeof(DpCarry) * (d->nseg + 1)));
     HIPCHK(hipMemsetAsync(d->carry, 0, sizeof(DpCarry) * (d->nseg + 1), d->st));
-    for (uint8_t*& p : d->pin) HIPCHK(hipHostMalloc((void**)&p, 4 * (seg + 1) + 8 + 24 + seg + DM_AHEAD, hipHostMallocDefault));
-  } else {
-    for (uint8_t*& p : d->pin) HIPCHK(hipHostMalloc((void**)&p, 11 * seg + DM_AHEAD, hipHostMallocDefault));
   }
+  for (uint8_t*& p : d->pin) HIPCHK(hipHostMalloc((void**)&p, d->slot.bytes, hipHostMallocDefault));
   HIPCHK(hipMemsetAsync(d->head, 0, 2 * DM_DICT, d->st));
   HIPCHK(hipMemsetAsync(d->Lw, 0, 2 * DM_DICT, d->st));
   HIPCHK(hipMemsetAsync(d->Ab, 0, 4, d->st));
@@ -418,8 +337,8 @@ static int32_t deflate_open_form(sp_ctx* c, const uint8_t* data, size_t n, int o
   const size_t opt = (size_t)c->opt.v[OPT_DIGEST_SEGMENT];
   d->seg = n < opt ? (n < DM_DICT ? DM_DICT : n) : opt;  // a short input is one segment of its own length (never below the window)
   d->nseg = (n + d->seg - 1) / d->seg;
-  d->mp[0] = 1 + (probes + 2) / 3;
-  d->mp[1] = 1 + ((probes >> 2) + 2) / 3;
+  d->lay_out_slot();
+  tdefl::probe_budget(probes, d->mp);
   const int32_t rc = deflate_open(d, data, on_device);
   if (rc != SP_OK) { sp_deflate_close(d); d = nullptr; }
   *out = d;
@@ -447,7 +366,7 @@ int32_t sp_deflate_segment_start(sp_deflate* d, size_t s) {
   if (m < count) HIPCHK(hipMemsetAsync(Lseg + m, 0, 2 * (count - m), st));
   if (m) {
     hipLaunchKernelGGL(k_dm_hash, dm_grid(m), dim3(DM_BLOCK), 0, st, d->dD, first, (uint32_t)m, d->keys_in, d->vals_in);
-    HIPCHK(rocprim::radix_sort_pairs(d->tmp, d->tmp_bytes, (const uint16_t*)d->keys_in, d->keys_out, (const uint32_t*)d->vals_in, d->vals_out, m, 0u, DM_HBITS, st));
+    HIPCHK(rocprim::radix_sort_pairs(d->tmp, d->tmp_bytes, (const uint16_t*)d->keys_in, d->keys_out, (const uint32_t*)d->vals_in, d->vals_out, m, 0u, tdefl::HBITS, st));
     hipLaunchKernelGGL(k_dm_links, dm_grid(m), dim3(DM_BLOCK), 0, st, (const uint16_t*)d->keys_out, (const uint32_t*)d->vals_out, (uint32_t)m,
                        (unsigned)(first & 0xFFFFu), (const uint16_t*)d->head, Lseg);
     hipLaunchKernelGGL(k_dm_heads, dm_grid(m), dim3(DM_BLOCK), 0, st, (const uint16_t*)d->keys_out, (const uint32_t*)d->vals_out, (uint32_t)m,
@@ -480,16 +399,15 @@ int32_t sp_deflate_segment_start(sp_deflate* d, size_t s) {
                        carry);
     if (hipGetLastError() != hipSuccess) return SP_EHIP;
     // the compaction writes the dense list and its length straight into the pinned slot
-    HIPCHK(rocprim::select(d->sel_tmp, d->sel_bytes, (const uint32_t*)d->tok, d->pT(k), d->pN(k), count + 1, DpNonZero(), st));
+    HIPCHK(rocprim::select(d->sel_tmp, d->sel_bytes, (const uint32_t*)d->tok, d->at<uint32_t>(k, 0), d->at<size_t>(k, d->slot.N), count + 1, DpNonZero(), st));
     HIPCHK(hipEventRecord(d->ev[k][6], st));
-    HIPCHK(hipMemcpyAsync(d->pC(k), carry + 1, sizeof(DpCarry), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(d->pDt(k), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->at<DpCarry>(k, d->slot.C), carry + 1, sizeof(DpCarry), hipMemcpyDeviceToHost, st));
   } else {
-    HIPCHK(hipMemcpyAsync(d->pA(k), d->Ab + 1, 4 * count, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(d->pB(k), d->Bb, 4 * count, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(d->pL(k), Lseg, 2 * count, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(d->pD(k), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->at<uint32_t>(k, 0), d->Ab + 1, 4 * count, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->at<uint32_t>(k, d->slot.B), d->Bb, 4 * count, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->at<uint16_t>(k, d->slot.L), Lseg, 2 * count, hipMemcpyDeviceToHost, st));
   }
+  HIPCHK(hipMemcpyAsync(d->at<uint8_t>(k, d->slot.D), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
   if (s + 1 < d->nseg) {  // count == seg >= 32768 here: what the next segment needs of this one
     HIPCHK(hipMemcpyAsync(d->Ab, d->Ab + count, 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(d->Lw, d->Lw + count, 2 * DM_DICT, hipMemcpyDeviceToDevice, st));
@@ -499,96 +417,103 @@ int32_t sp_deflate_segment_start(sp_deflate* d, size_t s) {
   return SP_OK;
 }
 
+// segment s of a handle of the given form is ready in its pinned slot
+static int32_t deflate_segment_ready(sp_deflate* d, bool parse, size_t s, size_t* first, size_t* count) {
+  if (!d || d->parse != parse || s >= d->started || s + 2 < d->started) return SP_EINVAL;
+  HIPCHK(hipSetDevice(d->ctx->dev));
+  HIPCHK(hipEventSynchronize(d->ev[s & 1][4]));
+  if (first) *first = d->first_of(s);
+  if (count) *count = d->count_of(s);
+  return SP_OK;
+}
+// device time of the segment's stages, between the events in the order the form recorded them (event 4 is the last of both)
+//   tables  links, search A, search B, copies
+//   parse   links, search A, search B, reachability, tokens + compaction, copies
+static int32_t deflate_stage_ms(const sp_deflate* d, int k, double* ms) {
+  static const int order[2][7] = {{0, 1, 2, 3, 4, -1, -1}, {0, 1, 2, 3, 5, 6, 4}};
+  const int* o = order[d->parse];
+  for (int i = 0; ms && o[i] != 4; i++) {
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, d->ev[k][o[i]], d->ev[k][o[i + 1]]));
+    ms[i] = t;
+  }
+  return SP_OK;
+}
 int32_t sp_deflate_segment_wait(sp_deflate* d, size_t s, size_t* first, size_t* count, const uint8_t** bytes, const uint16_t** L, const uint32_t** A,
                                 const uint32_t** B, double* ms) {
-  if (!d || d->parse || s >= d->started || s + 2 < d->started) return SP_EINVAL;
+  SPCHK(deflate_segment_ready(d, false, s, first, count));
   const int k = (int)(s & 1);
-  HIPCHK(hipSetDevice(d->ctx->dev));
-  HIPCHK(hipEventSynchronize(d->ev[k][4]));
-  if (first) *first = d->first_of(s);
-  if (count) *count = d->count_of(s);
-  if (bytes) *bytes = d->pD(k);
-  if (L) *L = d->pL(k);
-  if (A) *A = d->pA(k);
-  if (B) *B = d->pB(k);
-  if (ms)
-    for (int i = 0; i < 4; i++) {
-      float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, d->ev[k][i], d->ev[k][i + 1]));
-      ms[i] = t;
-    }
-  return SP_OK;
+  if (bytes) *bytes = d->at<uint8_t>(k, d->slot.D);
+  if (L) *L = d->at<uint16_t>(k, d->slot.L);
+  if (A) *A = d->at<uint32_t>(k, 0);
+  if (B) *B = d->at<uint32_t>(k, d->slot.B);
+  return deflate_stage_ms(d, k, ms);
 }
-
 int32_t sp_deflate_segment_wait_tokens(sp_deflate* d, size_t s, size_t* first, size_t* count, const uint8_t** bytes, const uint32_t** tokens, size_t* ntok,
                                        uint64_t* carry, double* ms) {
-  if (!d || !d->parse || s >= d->started || s + 2 < d->started) return SP_EINVAL;
+  SPCHK(deflate_segment_ready(d, true, s, first, count));
   const int k = (int)(s & 1);
-  HIPCHK(hipSetDevice(d->ctx->dev));
-  HIPCHK(hipEventSynchronize(d->ev[k][4]));
-  if (first) *first = d->first_of(s);
-  if (count) *count = d->count_of(s);
-  if (bytes) *bytes = d->pDt(k);
-  if (tokens) *tokens = d->pT(k);
-  if (ntok) *ntok = *d->pN(k);
+  if (bytes) *bytes = d->at<uint8_t>(k, d->slot.D);
+  if (tokens) *tokens = d->at<uint32_t>(k, 0);
+  if (ntok) *ntok = *d->at<size_t>(k, d->slot.N);
   if (carry) {
-    const DpCarry* c = d->pC(k);
+    const DpCarry* c = d->at<DpCarry>(k, d->slot.C);
     carry[0] = d->first_of(s) + d->count_of(s) + c->entry; carry[1] = c->sl; carry[2] = c->sd; carry[3] = c->fallbacks;
   }
-  if (ms) {
-    static const int order[7] = {0, 1, 2, 3, 5, 6, 4};  // links, search A, search B, reachability, tokens + compaction, copies
-    for (int i = 0; i < 6; i++) {
-      float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, d->ev[k][order[i]], d->ev[k][order[i + 1]]));
-      ms[i] = t;
-    }
-  }
-  return SP_OK;
+  return deflate_stage_ms(d, k, ms);
 }
 
+}  // extern "C"
+
+// the whole input through an opened handle, one segment after the other: each(s) waits for segment s and takes what it wants; closes the handle
+template <typename Each>
+static int32_t deflate_whole(sp_deflate* d, Each each) {
+  int32_t rc = SP_OK;
+  for (size_t s = 0; s < d->nseg && rc == SP_OK; s++) {
+    rc = sp_deflate_segment_start(d, s);
+    if (rc == SP_OK) rc = each(s);
+  }
+  sp_deflate_close(d);
+  return rc;
+}
+
+extern "C" {
 int32_t sp_deflate_tokens(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, uint32_t* tokens,
                           size_t* ntok, uint64_t* info) {
   if (!ntok) return SP_EINVAL;
   sp_deflate* d = nullptr;
   SPCHK(sp_deflate_open_parse(c, data, n, on_device, probes, tile, group, &d));
-  int32_t rc = SP_OK;
+  const size_t nseg = d->nseg;
   size_t total = 0;
   uint64_t held = 0, fallbacks = 0;
-  for (size_t s = 0; s < d->nseg && rc == SP_OK; s++) {
+  const int32_t rc = deflate_whole(d, [&](size_t s) -> int32_t {
     const uint32_t* t;
     size_t cnt = 0;
     uint64_t carry[4];
-    rc = sp_deflate_segment_start(d, s);
-    if (rc == SP_OK) rc = sp_deflate_segment_wait_tokens(d, s, nullptr, nullptr, nullptr, &t, &cnt, carry, nullptr);
-    if (rc != SP_OK) break;
-    if (total + cnt > n) { rc = SP_EINVAL; break; }  // more tokens than positions: never, and never written past the caller's array
+    SPCHK(sp_deflate_segment_wait_tokens(d, s, nullptr, nullptr, nullptr, &t, &cnt, carry, nullptr));
+    if (total + cnt > n) return SP_EINVAL;  // more tokens than positions: never, and never written past the caller's array
     if (tokens) memcpy(tokens + total, t, 4 * cnt);
     total += cnt;
-    if (carry[1] && s + 1 < d->nseg) held++;
+    if (carry[1] && s + 1 < nseg) held++;
     fallbacks = carry[3];
-  }
+    return SP_OK;
+  });
   *ntok = total;
   if (info) { info[0] = held; info[1] = fallbacks; }
-  sp_deflate_close(d);
   return rc;
 }
-
 int32_t sp_deflate_matches(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, uint16_t* L, uint32_t* A, uint32_t* B) {
   sp_deflate* d = nullptr;
   SPCHK(sp_deflate_open(c, data, n, on_device, probes, &d));
-  int32_t rc = SP_OK;
-  for (size_t s = 0; s < d->nseg && rc == SP_OK; s++) {
+  return deflate_whole(d, [&](size_t s) -> int32_t {
     size_t first = 0, count = 0;
     const uint16_t* l; const uint32_t *a, *b;
-    rc = sp_deflate_segment_start(d, s);
-    if (rc == SP_OK) rc = sp_deflate_segment_wait(d, s, &first, &count, nullptr, &l, &a, &b, nullptr);
-    if (rc != SP_OK) break;
+    SPCHK(sp_deflate_segment_wait(d, s, &first, &count, nullptr, &l, &a, &b, nullptr));
     if (L) memcpy(L + first, l, 2 * count);
     if (A) memcpy(A + first, a, 4 * count);
     if (B) memcpy(B + first, b, 4 * count);
-  }
-  sp_deflate_close(d);
-  return rc;
+    return SP_OK;
+  });
 }
 
 int32_t sp_sparse_bincode(sp_ctx* c, const sp_sparse* const* ms, size_t count, uint64_t num_vars_x, uint64_t num_vars_y, uint8_t* dev_out, size_t cap) {

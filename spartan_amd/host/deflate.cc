@@ -20,11 +20,17 @@
 // line-by-line Rust port of tdefl) equals miniz; scripts/compare_with_libspartan.sh prints both digests. The header bytes are the one
 // documented variable: miniz >= 2.2 and miniz_oxide >= 0.4 derive FLEVEL from the probe count (level 6: 0x78 0x9C), older ones write
 // 0x78 0x01 (the `old_header` argument — an explicit API parameter, spz_instance_set_digest_header, never an environment switch).
-// Below the sequential deflater (the oracle of everything that follows, left as it was): the match search restated as one independent item
-// per input position (find_pure, deflate_matches_host — what csrc/deflate_match.hip runs on the device) and the same parser fed from match
-// tables instead of a dictionary (MatchParser, zlib_from_matches), which digest.cc runs behind the device search. Last, the parse restated
-// as walks between FREE states (deflate_tokens_host — what the device parse of deflate_match.hip runs) and the coder fed from its tokens
-// (TokenCoder, zlib_from_tokens): record_literal, record_match, the block check and flush_block with no tables and no search.
+// Below the sequential deflater (Tdefl::run and Tdefl::find_match: the oracle of everything that follows, left as it was and sharing
+// nothing with it) stand the restatements that run behind the device. Their rules — the search as one independent item per input position
+// (find), the parser's step as walks between FREE states (walk), the candidate filter, the token word — are csrc/tdefl_rules.hpp, which
+// csrc/deflate_match.hip runs on the device; here they are applied on the host:
+//   deflate_links_host, deflate_matches_host   the tables L, A, B over a whole input
+//   TableLookup                                the parser's look-up answered from such tables: A, or B, or a search on the spot
+//   Coder                                      record_literal, record_match, the block check and flush_block (the Tdefl members, untouched)
+//                                              fed one token at a time, with Adler-32 as the input arrives: no tables, no search
+//   MatchParser, zlib_from_matches             TableLookup -> walk -> Coder, segment by segment: what digest.cc runs behind the device search
+//   deflate_tokens_host                        TableLookup -> walk -> a token list: the host model of the device parse
+//   TokenCoder, zlib_from_tokens               a token list -> Coder: what digest.cc runs behind the device parse
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -386,66 +392,93 @@ struct Tdefl {
     flush_block(true);
   }
 };
-// ---- the match search restated as one independent item per input position (what deflate_match.hip runs on the device)
-// find_match above reads three things that depend on how far the parser has come: the ring `dict`, the ring `next`, and dict_size. With
-// the whole input D[0, n) in hand all three are functions of the position p alone:
-//   lookahead   la = min(258, n - p);  dict_size = min(p, 32768 - la)
-//   dict        dict[(q & 32767) + k] is D[q + k] for every q the search can reach (q >= p - dict_size: q + 32768 has not arrived yet)
-//   next        the slot of such a q still holds q's own link L[q] = low 16 bits of the greatest q' < q with the same 3-byte hash (0: none).
-//               The look-back is unbounded: a head written more than 65535 positions ago aliases, and tdefl follows the alias.
-// So find(p, init) below is find_match with those substitutions and nothing else changed: probe budget, three-hop inner loop, c0/c1
-// filter, the dist == 0 break and the early return at the longest match are literally the code above.
-inline void probe_budget(unsigned probes, unsigned mp[2]) {
-  mp[0] = 1 + ((probes & 0xFFF) + 2) / 3;
-  mp[1] = 1 + (((probes & 0xFFF) >> 2) + 2) / 3;
+
+// ---- the restatements: the rules of csrc/tdefl_rules.hpp applied on the host
+// The parser's look-up at p (init == 2: it holds nothing; else the length it holds) answered from the tables of one segment: A and B are
+// those of positions [first, first + count), prevA is A[first - 1]. A when the parser is free; B when A[p - 1] is held at exactly this
+// length; else — a lazy chain of three or more whose held length is not A[p - 1]'s — searched on the spot over links() = Lbase with
+// Lbase[q - Lfirst] = L[q], asked for on the first such look-up only.
+template <typename Links>
+struct TableLookup {
+  const uint8_t* D;
+  size_t n, first;
+  const uint32_t *A, *B;
+  uint32_t prevA;
+  Links links;
+  size_t Lfirst;
+  const unsigned* mp;
+  uint64_t lookups = 0, fallbacks = 0;
+  uint32_t operator()(size_t p, unsigned init) {
+    lookups++;
+    if (init == tdefl::MINM - 1) return A[p - first];
+    const uint32_t aprev = p > first ? A[p - 1 - first] : prevA;
+    if (p && tdefl::held(aprev, p - 1) && (aprev >> 16) == init) return B[p - first];
+    fallbacks++;
+    return tdefl::find(D, n, links(), Lfirst, p, init, mp);
+  }
+};
+template <typename Links>
+TableLookup<Links> table_lookup(const uint8_t* D, size_t n, size_t first, const uint32_t* A, const uint32_t* B, uint32_t prevA, Links links, size_t Lfirst,
+                                const unsigned* mp) {
+  return TableLookup<Links>{D, n, first, A, B, prevA, links, Lfirst, mp};
 }
-inline uint32_t pack_match(unsigned dist, unsigned len) { return dist | (len << 16); }
-uint32_t find_pure(const uint8_t* D, size_t n, const uint16_t* Lbase, size_t Lfirst, size_t p, unsigned init, const unsigned mp[2]) {
-  // Lbase[q - Lfirst] = L[q]; the caller keeps [p - 32768, p] addressable
-  const unsigned la = (unsigned)std::min<size_t>(MAXM, n - p), max_dist = (unsigned)std::min<size_t>(p, DICT - la);
-  unsigned dist = 0, best = 0, match_len = init, probe_len;
-  if (la <= match_len) return pack_match(0, init);
-  unsigned probes_left = mp[match_len >= 32];
-  const uint8_t* s = D + p;
-  uint8_t c0 = s[match_len], c1 = s[match_len - 1];
-  size_t cand = p;
-  for (;;) {
-    for (;;) {
-      if (--probes_left == 0) return pack_match(best, match_len);
-      bool hit = false;
-      for (int k = 0; k < 3 && !hit; k++) {
-        const unsigned nx = Lbase[cand - Lfirst];
-        if (!nx || (dist = (uint16_t)((unsigned)p - nx)) > max_dist) return pack_match(best, match_len);
-        cand = p - dist;
-        if (D[cand + match_len] == c0 && D[cand + match_len - 1] == c1) hit = true;
-      }
-      if (hit) break;
-    }
-    if (!dist) break;
-    const uint8_t* q = D + cand;
-    for (probe_len = 0; probe_len < la; probe_len++) if (s[probe_len] != q[probe_len]) break;
-    if (probe_len > match_len) {
-      best = dist;
-      if ((match_len = probe_len) == la) break;
-      c0 = s[match_len]; c1 = s[match_len - 1];
+
+// record_literal, record_match, the block check and flush_block of Tdefl, one token at a time: no tables, no dictionary, no search. The
+// two numbers flush_block's stored-block test reads are those of the parser's step the token closes: the step at p with lookahead
+// la = min(258, n - p) starts from dict_size = min(p, 32768 - la) and moves m positions.
+struct Coder {
+  Tdefl d;
+  size_t n, pos = 0;        // input length, position of the next token
+  uint32_t s1 = 1, s2 = 0;  // Adler-32 so far
+  size_t adler_pos = 0;
+  uint64_t full_blocks = 0, ratio_blocks = 0;  // blocks ended by the code-buffer rule / the 115/128 rule
+  Coder(size_t n_, unsigned probes, bool old_header) : n(n_) {
+    memset(d.count, 0, sizeof d.count); memset(d.codes, 0, sizeof d.codes); memset(d.sizes, 0, sizeof d.sizes);
+    d.old_header = old_header;
+    d.probes = probes & 0xFFF;
+  }
+  // D[0, end) has arrived: Adler-32 of the input as it arrives; the bytes of a stored block come from D
+  void arrive(const uint8_t* D, size_t end) {
+    d.stored_src = D;
+    while (adler_pos < end) {
+      const size_t blk = std::min<size_t>(5552, end - adler_pos);
+      for (size_t k = 0; k < blk; k++) { s1 += D[adler_pos + k]; s2 += s1; }
+      s1 %= 65521; s2 %= 65521; adler_pos += blk;
     }
   }
-  return pack_match(best, match_len);
-}
-// does the match A[p - 1] = a come out of the parser's filter as a HELD match (then the parser asks at p with init = its length: table B)
-inline bool held_after_filter(uint32_t a, size_t pos_of_a) {
-  const unsigned dist = a & 0xFFFF, len = a >> 16;
-  if (!dist) return false;
-  if ((len == MINM && dist >= 8u * 1024u) || (unsigned)(pos_of_a & DMASK) == dist) return false;
-  return len < 128;
-}
+  // inlined into its callers' loops by force: left as a call it costs the coder 5-10 % (bench/deflate_host_probe.cc, time 16)
+  __attribute__((always_inline)) void token(uint32_t t) {
+    const unsigned len = tdefl::tok_len(t);
+    size_t step, move;  // the parser's step this token closes: where it looked, how far it moved
+    if (!len) {
+      d.record_literal((uint8_t)t);
+      step = pos + ((t & TOK_HELD) ? 1 : 0); move = 1;
+      pos += 1;
+    } else {
+      d.record_match(len, tdefl::tok_dist(t));
+      if (len >= tdefl::TAKE) { step = pos; move = len; } else { step = pos + 1; move = len - 1; }  // taken at once | the held match of step - 1
+      pos += len;
+    }
+    if (!(t & TOK_CHECK)) return;
+    const unsigned la = (unsigned)std::min<size_t>(tdefl::MAXM, n - step);
+    d.lookahead_pos = (unsigned)(step + move);
+    d.dict_size = (unsigned)std::min<size_t>(std::min<size_t>(step, tdefl::DICT - la) + move, tdefl::DICT);
+    if (d.code_bytes > LZBUF - 8) { full_blocks++; d.flush_block(false); }
+    else if (d.total_lz_bytes > 31 * 1024 && ((d.code_bytes * 115) >> 7) >= d.total_lz_bytes) { ratio_blocks++; d.flush_block(false); }
+  }
+  std::vector<uint8_t> finish() {
+    d.adler = (s2 << 16) | s1;
+    d.flush_block(true);
+    return std::move(d.out);
+  }
+};
 }  // namespace
 
 void deflate_links_host(const uint8_t* D, size_t n, uint16_t* L) {
-  std::vector<uint16_t> head(HSIZE, 0);
+  std::vector<uint16_t> head((size_t)1 << tdefl::HBITS, 0);
   for (size_t p = 0; p < n; p++) {
     if (p + 2 >= n) { L[p] = 0; continue; }
-    const unsigned h = ((D[p] << (HSHIFT * 2)) ^ (D[p + 1] << HSHIFT) ^ D[p + 2]) & (HSIZE - 1);
+    const unsigned h = tdefl::hash3(D + p);
     L[p] = head[h];
     head[h] = (uint16_t)p;
   }
@@ -454,109 +487,48 @@ void deflate_matches_host(const uint8_t* D, size_t n, unsigned probes, const uin
   std::vector<uint16_t> own;
   if (!L) { own.resize(n ? n : 1); deflate_links_host(D, n, own.data()); L = own.data(); }
   unsigned mp[2];
-  probe_budget(probes, mp);
-  for (size_t p = 0; p < n; p++) A[p] = find_pure(D, n, L, 0, p, MINM - 1, mp);
-  for (size_t p = 0; p < n; p++) B[p] = p && held_after_filter(A[p - 1], p - 1) ? find_pure(D, n, L, 0, p, A[p - 1] >> 16, mp) : 0;
+  tdefl::probe_budget(probes, mp);
+  for (size_t p = 0; p < n; p++) A[p] = tdefl::find(D, n, L, 0, p, tdefl::MINM - 1, mp);
+  for (size_t p = 0; p < n; p++) B[p] = p && tdefl::held(A[p - 1], p - 1) ? tdefl::find(D, n, L, 0, p, A[p - 1] >> 16, mp) : 0;
 }
 
-// Tdefl::run with the matches read from the tables: the same parser, block decisions, Huffman coding and bit output (the Tdefl members
-// above, untouched), no dictionary and no hash chains. Fed segment by segment, so that it can run behind the device search.
+// Fed segment by segment, so that it can run behind the device search. What a segment needs of those before it: the walk's state, A's last
+// entry, and for a search on the spot the last 32768 links (zeros before position 0, which no search reaches).
 struct MatchParser::Impl {
-  Tdefl d;
-  size_t n = 0, p = 0;                // input length, next position to parse
-  uint32_t s1 = 1, s2 = 0;            // Adler-32 so far
-  size_t adler_pos = 0;
-  uint32_t prevA = 0;                 // A[first - 1] of the segment being parsed
-  std::vector<uint16_t> ltail;        // L[ltail_first, ltail_first + ltail.size()): the last <= 32768 links of the segments already parsed
-  size_t ltail_first = 0;
-  std::vector<uint16_t> lwin;         // a fallback's view of the links: ltail followed by the current segment's (built on the first fallback of a segment)
+  Coder coder;
+  tdefl::WalkState w{0, 0, 0};
+  uint32_t prevA = 0;                                         // A[first - 1] of the segment being parsed
+  std::vector<uint16_t> ltail = std::vector<uint16_t>(tdefl::DICT);  // L[first - 32768, first)
+  std::vector<uint16_t> lwin;                                 // ltail followed by the segment's links, built on the segment's first fallback
   unsigned mp[2];
+  Impl(size_t n, unsigned probes, bool old_header) : coder(n, probes, old_header) { tdefl::probe_budget(probes, mp); }
 };
-MatchParser::MatchParser(size_t n, unsigned probes, bool old_header) : m(new Impl()) {
-  Tdefl& d = m->d;
-  memset(d.count, 0, sizeof d.count); memset(d.codes, 0, sizeof d.codes); memset(d.sizes, 0, sizeof d.sizes);
-  d.old_header = old_header;
-  d.probes = probes & 0xFFF;
-  probe_budget(d.probes, m->mp);
-  d.max_probes[0] = m->mp[0]; d.max_probes[1] = m->mp[1];
-  m->n = n;
-}
+MatchParser::MatchParser(size_t n, unsigned probes, bool old_header) : m(new Impl(n, probes, old_header)) {}
 MatchParser::~MatchParser() { delete m; }
 void MatchParser::parse(const uint8_t* D, size_t first, size_t count, const uint16_t* L, const uint32_t* A, const uint32_t* B) {
   Impl& s = *m;
-  Tdefl& d = s.d;
-  const size_t n = s.n, end = first + count;
-  d.stored_src = D;
-  for (; s.adler_pos < end;) {  // Adler-32 of the input as it arrives
-    const size_t blk = std::min<size_t>(5552, end - s.adler_pos);
-    for (size_t k = 0; k < blk; k++) { s.s1 += D[s.adler_pos + k]; s.s2 += s.s1; }
-    s.s1 %= 65521; s.s2 %= 65521; s.adler_pos += blk;
-  }
+  const size_t end = first + count;
+  s.coder.arrive(D, end);
   bool lwin_built = false;
-  while (s.p < end) {
-    const size_t p = s.p;
-    d.lookahead_pos = (unsigned)p;
-    d.lookahead_size = (unsigned)std::min<size_t>(MAXM, n - p);
-    d.dict_size = std::min(DICT - d.lookahead_size, d.dict_size);
-    unsigned len_to_move = 1, cur_match_dist, cur_match_len;
-    const unsigned init = d.saved_match_len ? d.saved_match_len : (MINM - 1), cur_pos = (unsigned)(p & DMASK);
-    const uint32_t aprev = p > first ? A[p - 1 - first] : s.prevA;
-    uint32_t got;
-    lookups++;
-    if (init == MINM - 1) got = A[p - first];
-    else if (p && held_after_filter(aprev, p - 1) && (aprev >> 16) == init) got = B[p - first];
-    else {  // a lazy chain of three or more whose held length is not A[p - 1]'s: searched here
-      fallbacks++;
-      if (!lwin_built) {
-        s.lwin.assign(s.ltail.begin(), s.ltail.end());
-        s.lwin.insert(s.lwin.end(), L, L + count);
-        lwin_built = true;
-      }
-      got = find_pure(D, n, s.lwin.data(), s.ltail_first, p, init, s.mp);
+  auto links = [&]() -> const uint16_t* {
+    if (!lwin_built) {
+      s.lwin.assign(s.ltail.begin(), s.ltail.end());
+      s.lwin.insert(s.lwin.end(), L, L + count);
+      lwin_built = true;
     }
-    cur_match_dist = got & 0xFFFF; cur_match_len = got >> 16;
-    if ((cur_match_len == MINM && cur_match_dist >= 8u * 1024u) || cur_pos == cur_match_dist) cur_match_dist = cur_match_len = 0;
-    if (d.saved_match_len) {
-      if (cur_match_len > d.saved_match_len) {
-        d.record_literal((uint8_t)d.saved_lit);
-        if (cur_match_len >= 128) { d.record_match(cur_match_len, cur_match_dist); d.saved_match_len = 0; len_to_move = cur_match_len; }
-        else { d.saved_lit = D[p]; d.saved_match_dist = cur_match_dist; d.saved_match_len = cur_match_len; }
-      } else {
-        d.record_match(d.saved_match_len, d.saved_match_dist);
-        len_to_move = d.saved_match_len - 1;
-        d.saved_match_len = 0;
-      }
-    } else if (!cur_match_dist) {
-      d.record_literal(D[p]);
-    } else if (cur_match_len >= 128) {
-      d.record_match(cur_match_len, cur_match_dist);
-      len_to_move = cur_match_len;
-    } else {
-      d.saved_lit = D[p]; d.saved_match_dist = cur_match_dist; d.saved_match_len = cur_match_len;
-    }
-    s.p += len_to_move;
-    d.lookahead_pos += len_to_move;
-    d.lookahead_size -= len_to_move;
-    d.dict_size = std::min(d.dict_size + len_to_move, DICT);
-    if (d.code_bytes > LZBUF - 8 || (d.total_lz_bytes > 31 * 1024 && ((d.code_bytes * 115) >> 7) >= d.total_lz_bytes)) d.flush_block(false);
-  }
-  // what the next segment needs of this one: its last table entry and the last 32768 links
+    return s.lwin.data();
+  };
+  auto lookup = table_lookup(D, s.coder.n, first, A, B, s.prevA, links, first - tdefl::DICT, s.mp);
+  auto emit = [&](size_t, uint32_t t) { s.coder.token(t); };
+  while (s.w.q < end) tdefl::walk(D, s.w, end, lookup, emit);
+  lookups += lookup.lookups; fallbacks += lookup.fallbacks;
   if (count) {
     s.prevA = A[count - 1];
-    if (count >= DICT) {
-      s.ltail.assign(L + count - DICT, L + count);
-    } else {
-      s.ltail.insert(s.ltail.end(), L, L + count);
-      if (s.ltail.size() > DICT) s.ltail.erase(s.ltail.begin(), s.ltail.end() - DICT);
-    }
-    s.ltail_first = end - s.ltail.size();
+    if (count < tdefl::DICT) s.ltail.erase(s.ltail.begin(), s.ltail.begin() + count); else s.ltail.clear();
+    s.ltail.insert(s.ltail.end(), L + count - std::min<size_t>(count, tdefl::DICT), L + count);
   }
 }
-std::vector<uint8_t> MatchParser::finish() {
-  m->d.adler = (m->s2 << 16) | m->s1;
-  m->d.flush_block(true);
-  return std::move(m->d.out);
-}
+std::vector<uint8_t> MatchParser::finish() { return m->coder.finish(); }
 std::vector<uint8_t> zlib_from_matches(const uint8_t* D, size_t n, const uint16_t* L, const uint32_t* A, const uint32_t* B, unsigned probes, bool old_header,
                                        uint64_t* lookups, uint64_t* fallbacks) {
   std::vector<uint16_t> own;
@@ -568,74 +540,22 @@ std::vector<uint8_t> zlib_from_matches(const uint8_t* D, size_t n, const uint16_
   return mp.finish();
 }
 
-// ---- the parse restated as walks between free states (what the device parse of deflate_match.hip runs), and the coder over its tokens
-// The parser's state before a step is (p, saved_len, saved_dist); call it FREE when saved_len == 0. From a free state at p, read off
-// MatchParser::parse above: A[p] filtered is nothing (a literal at p, free at p + 1), a match of >= 128 (taken at once, free at p + len), or
-// a match that is HELD. A held match at q - 1 meets the look-up at q with init = its length: a longer one makes D[q - 1] a literal and is
-// itself taken (>= 128) or held in turn; otherwise the held match is emitted at q - 1 and the state is free at q - 1 + len. Held lengths
-// strictly grow from >= 3 and stay below 128, so a walk holds at most 125 times (positions p .. p + 124), its last step is at q <= p + 125
-// and the next free state F(p) is at most q + 258: 1 <= F(p) - p <= 383. Every token of a walk starts at a position of its own (a literal at
-// each chain position that lost, the match at the last), so the parse is one word per input position: tokens of the positions reachable
-// from the entry state under F. Nothing in a walk reads the coder's state; the coder needs of a token only what the block check after the
-// parser's STEP reads (lookahead_pos, dict_size), which two bits carry: TOK_CHECK (a check follows this token: a step that only holds emits
-// nothing and its check sees the numbers of the check before it, which did not fire or reset them) and TOK_HELD (a match is held when that
-// check runs: lookahead_pos is then one past the emitted bytes).
-namespace {
-inline uint32_t tok_lit(uint8_t c, uint32_t bits) { return TOK_VALID | bits | c; }
-inline uint32_t tok_match(unsigned len, unsigned dist, uint32_t bits) { return TOK_VALID | bits | (len << 15) | (dist - 1); }
-struct WalkState { size_t q; unsigned sl, sd; };  // next step at q; held match (sl, sd) found at q - 1, sl == 0: free
-// steps from `w` until the state is free again (after at least one step) or q reaches `end`, where the parser's segment loop stops too.
-// emit(position, token); lookup(q, init) -> dist | len << 16
-template <typename Lookup, typename Emit>
-inline void walk(const uint8_t* D, WalkState& w, size_t end, Lookup lookup, Emit emit) {
-  do {
-    const size_t q = w.q;
-    const uint32_t got = lookup(q, w.sl ? w.sl : MINM - 1);
-    unsigned cd = got & 0xFFFF, cl = got >> 16;
-    if ((cl == MINM && cd >= 8u * 1024u) || (unsigned)(q & DMASK) == cd) cd = cl = 0;
-    if (w.sl) {
-      if (cl > w.sl) {
-        if (cl >= 128) { emit(q - 1, tok_lit(D[q - 1], 0)); emit(q, tok_match(cl, cd, TOK_CHECK)); w.sl = 0; w.q = q + cl; }
-        else { emit(q - 1, tok_lit(D[q - 1], TOK_CHECK | TOK_HELD)); w.sl = cl; w.sd = cd; w.q = q + 1; }
-      } else {
-        emit(q - 1, tok_match(w.sl, w.sd, TOK_CHECK));
-        w.q = q - 1 + w.sl; w.sl = 0;
-      }
-    } else if (!cd) {
-      emit(q, tok_lit(D[q], TOK_CHECK)); w.q = q + 1;
-    } else if (cl >= 128) {
-      emit(q, tok_match(cl, cd, TOK_CHECK)); w.q = q + cl;
-    } else {
-      w.sl = cl; w.sd = cd; w.q = q + 1;
-    }
-  } while (w.sl && w.q < end);
-}
-}  // namespace
-
 size_t deflate_tokens_host(const uint8_t* D, size_t n, unsigned probes, const size_t geom[3], uint32_t* tokens, uint64_t counters[TOKC_COUNT]) {
   std::vector<uint16_t> L(n ? n : 1);
   std::vector<uint32_t> A(n ? n : 1), B(n ? n : 1);
   deflate_links_host(D, n, L.data());
   deflate_matches_host(D, n, probes, L.data(), A.data(), B.data());
   unsigned mp[2];
-  probe_budget(probes, mp);
+  tdefl::probe_budget(probes, mp);
   uint64_t own[TOKC_COUNT];
   uint64_t* C = counters ? counters : own;
   memset(C, 0, sizeof own);
   const size_t tile = geom && geom[0] ? geom[0] : 1024, group = tile * (geom && geom[1] ? geom[1] : 64), seg = geom && geom[2] ? geom[2] : (n ? n : 1);
   size_t ntok = 0, first = 0;
-  unsigned chain = 0;  // holds of the walk under way
-  auto lookup = [&](size_t q, unsigned init) -> uint32_t {
-    C[TOKC_LOOKUPS]++;
-    if (init == MINM - 1) { chain = 0; return A[q]; }
-    chain++;
-    if (held_after_filter(A[q - 1], q - 1) && (A[q - 1] >> 16) == init) return B[q];
-    C[TOKC_FALLBACKS]++;  // a lazy chain of three or more whose held length is not A[q - 1]'s: neither table answers
-    return find_pure(D, n, L.data(), 0, q, init, mp);
-  };
+  auto lookup = table_lookup(D, n, 0, A.data(), B.data(), 0, [&] { return L.data(); }, 0, mp);
   auto emit = [&](size_t pos, uint32_t t) {
     tokens[ntok++] = t;
-    const unsigned len = (t >> 15) & 0x1FF;
+    const unsigned len = tdefl::tok_len(t);
     if (len) {
       const size_t a = pos - first, b = a + len - 1;  // a match starts in the segment under way (or one position before it: the prologue's)
       if (pos >= first && b < seg && first + b < n) {
@@ -644,77 +564,40 @@ size_t deflate_tokens_host(const uint8_t* D, size_t n, unsigned probes, const si
       }
     }
   };
-  WalkState w{0, 0, 0};
+  tdefl::WalkState w{0, 0, 0};
   for (; first < n; first += seg) {
     const size_t end = std::min(n, first + seg);
     if (w.sl) C[TOKC_SEAM_HELD]++;  // the segment's entry is a held match: its first walk is resolved from the carried state
     while (w.q < end) {
       const size_t p = w.q, before = ntok;
       const bool was_free = w.sl == 0;
-      walk(D, w, end, lookup, emit);
+      tdefl::walk(D, w, end, lookup, emit);
       C[TOKC_WALKS]++;
       if (was_free && !w.sl) C[TOKC_MAX_JUMP] = std::max<uint64_t>(C[TOKC_MAX_JUMP], w.q - p);
-      if (ntok - before == 1 && was_free && ((tokens[before] >> 15) & 0x1FF) >= 128) C[TOKC_FREE_LONG]++;
+      if (ntok - before == 1 && was_free && tdefl::tok_len(tokens[before]) >= tdefl::TAKE) C[TOKC_FREE_LONG]++;
       if (ntok - before >= 2 && !(tokens[ntok - 2] & TOK_CHECK)) C[TOKC_LIT_AND_LONG]++;
     }
   }
+  C[TOKC_LOOKUPS] = lookup.lookups; C[TOKC_FALLBACKS] = lookup.fallbacks;
   C[TOKC_TOKENS] = ntok;
   return ntok;
 }
 
-// record_literal, record_match, the block check and flush_block of Tdefl over a token list: no tables, no dictionary, no search. The two
-// numbers flush_block's stored-block test reads are those of the parser's step the token closes (MatchParser::parse): the step at p with
-// lookahead la = min(258, n - p) starts from dict_size = min(p, 32768 - la) and moves m positions.
 struct TokenCoder::Impl {
-  Tdefl d;
-  size_t n = 0, pos = 0;    // input length, position of the next token
-  uint32_t s1 = 1, s2 = 0;  // Adler-32 so far
-  size_t adler_pos = 0;
+  Coder coder;
 };
-TokenCoder::TokenCoder(size_t n, unsigned probes, bool old_header) : m(new Impl()) {
-  Tdefl& d = m->d;
-  memset(d.count, 0, sizeof d.count); memset(d.codes, 0, sizeof d.codes); memset(d.sizes, 0, sizeof d.sizes);
-  d.old_header = old_header;
-  d.probes = probes & 0xFFF;
-  m->n = n;
-}
+TokenCoder::TokenCoder(size_t n, unsigned probes, bool old_header) : m(new Impl{Coder(n, probes, old_header)}) {}
 TokenCoder::~TokenCoder() { delete m; }
 void TokenCoder::code(const uint8_t* D, size_t bytes_end, const uint32_t* tokens, size_t ntok) {
-  Impl& s = *m;
-  Tdefl& d = s.d;
-  d.stored_src = D;
-  for (; s.adler_pos < bytes_end;) {  // Adler-32 of the input as it arrives
-    const size_t blk = std::min<size_t>(5552, bytes_end - s.adler_pos);
-    for (size_t k = 0; k < blk; k++) { s.s1 += D[s.adler_pos + k]; s.s2 += s.s1; }
-    s.s1 %= 65521; s.s2 %= 65521; s.adler_pos += blk;
-  }
-  for (size_t i = 0; i < ntok; i++) {
-    const uint32_t t = tokens[i];
-    const unsigned len = (t >> 15) & 0x1FF;
-    size_t step, move;  // the parser's step this token closes: where it looked, how far it moved
-    if (!len) {
-      d.record_literal((uint8_t)t);
-      step = s.pos + ((t & TOK_HELD) ? 1 : 0); move = 1;
-      s.pos += 1;
-    } else {
-      d.record_match(len, (t & 0x7FFF) + 1);
-      if (len >= 128) { step = s.pos; move = len; } else { step = s.pos + 1; move = len - 1; }  // taken at once | the held match of step - 1
-      s.pos += len;
-    }
-    if (!(t & TOK_CHECK)) continue;
-    const unsigned la = (unsigned)std::min<size_t>(MAXM, s.n - step);
-    d.lookahead_pos = (unsigned)(step + move);
-    d.dict_size = (unsigned)std::min<size_t>(std::min<size_t>(step, DICT - la) + move, DICT);
-    if (d.code_bytes > LZBUF - 8) { full_blocks++; d.flush_block(false); }
-    else if (d.total_lz_bytes > 31 * 1024 && ((d.code_bytes * 115) >> 7) >= d.total_lz_bytes) { ratio_blocks++; d.flush_block(false); }
-  }
-  tokens_coded += ntok;
+  Coder& c = m->coder;
+  c.arrive(D, bytes_end);
+  for (size_t i = 0; i < ntok; i++) c.token(tokens[i]);
+  tokens_coded += ntok; full_blocks = c.full_blocks; ratio_blocks = c.ratio_blocks;
 }
 std::vector<uint8_t> TokenCoder::finish() {
-  m->d.adler = (m->s2 << 16) | m->s1;
-  m->d.flush_block(true);
-  static_blocks = m->d.static_blocks; stored_blocks = m->d.stored_blocks;
-  return std::move(m->d.out);
+  std::vector<uint8_t> z = m->coder.finish();
+  static_blocks = m->coder.d.static_blocks; stored_blocks = m->coder.d.stored_blocks;
+  return z;
 }
 std::vector<uint8_t> zlib_from_tokens(const uint8_t* D, size_t n, const uint32_t* tokens, size_t ntok, unsigned probes, bool old_header, size_t piece,
                                       uint64_t blocks[4]) {

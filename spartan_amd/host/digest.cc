@@ -1,14 +1,15 @@
-// spartan_amd host driver: R1CSShape::get_digest (src/r1cs.rs:154-158) with the device's help (option digest.device = 1).
+// spartan_amd host driver: R1CSShape::get_digest (src/r1cs.rs:154-158) with the device's help (option digest.device = 1 or 2).
 //   device   bincode(shape) serialised from the resident entries (sp_sparse_bincode); tdefl's match search, one input position per lane,
-//            segment by segment (sp_deflate_*: csrc/deflate_match.hip)
-//   host     the parser over the match tables, the block decisions, the Huffman coding and the bit output (deflate.cc, MatchParser): all of
-//            it sequential, all of it here. Segment s is parsed while the device searches segment s + 1; tables and bytes arrive through
-//            the search's two pinned slots.
-// With digest.device = 2 the lazy parse runs on the device as well (sp_deflate_open_parse: walks between the parser's free states from the
-// positions reachable from each segment's entry) and the host codes the tokens it hands over (deflate.cc, TokenCoder): record_literal,
-// record_match, the block check and flush_block, no table look-up. L, A and B are then not downloaded.
-// The bytes are those of zlib_level6_miniz by construction (tests/test_deflate_matches.py, tests/test_gpu_deflate_matches.py). The Rust
-// crate computes its digest with flate2 itself and has no use for this file, which is why it stands apart from prover.cc.
+//            segment by segment (sp_deflate_*: csrc/deflate_match.hip); with digest.device = 2 the lazy parse as well (sp_deflate_open_parse:
+//            walks between the parser's free states from the positions reachable from each segment's entry)
+//   host     what is sequential (deflate.cc). digest.device = 1: the parser over the match tables L, A, B with the coder behind it
+//            (MatchParser). digest.device = 2: the coder alone over the tokens the device hands over (TokenCoder: record_literal,
+//            record_match, the block check and flush_block, no table look-up); L, A and B are then not downloaded.
+// Both forms run one pipeline (run_segments): segment s is consumed here while the device works on segment s + 1; what the device made
+// arrives through its two pinned slots. They differ in the wait call and in what consumes the segment.
+// The bytes are those of zlib_level6_miniz by construction (tests/test_deflate_matches.py, tests/test_gpu_deflate_matches.py,
+// tests/test_gpu_deflate_tokens.py). The Rust crate computes its digest with flate2 itself and has no use for this file, which is why it
+// stands apart from prover.cc.
 #include <chrono>
 
 #include <hip/hip_runtime_api.h>
@@ -36,38 +37,50 @@ struct DeviceBytes {
   ~DeviceBytes() { if (p) (void)hipFree(p); }
 };
 size_t log_2(size_t n) { size_t l = 0; while (((size_t)1 << l) < n) l++; return l; }
-// the device parse and the token coder: segment s + 1 is searched and parsed on the device while the tokens of segment s are coded here
-std::vector<uint8_t> zlib_device_tokens(sp_ctx* c, const uint8_t* data, const uint8_t* dev_data, size_t n, unsigned probes, bool old_header, DeflateStats& S,
-                                        size_t tile, size_t group) {
-  DeflateHandle h;
-  DSPX(sp_deflate_open_parse(c, dev_data ? dev_data : data, n, dev_data != nullptr, probes, tile, group, &h.d));
-  const size_t nseg = sp_deflate_segments(h.d);
+
+struct Arrived { size_t first = 0, count = 0; const uint8_t* bytes = nullptr; };  // a segment in its pinned slot: positions, and its bytes + 258
+// The segment pipeline of both forms: segment s + 1 is started on the device before segment s is waited for, so the device works on it
+// while the host consumes segment s. wait(s, a, ms) is the form's sp_deflate_segment_wait*; consume(D, bytes_end, a) hands what it left to the
+// form's parser or coder, D[0, bytes_end) being the input as the host reads it (Adler-32, stored blocks, a fallback search): the caller's
+// bytes, or the device's as they arrive (a match of this segment's tokens ends within 258 of its end); finish() returns the stream.
+// stage[] sums the device's stage times in the form's order.
+template <typename Wait, typename Consume, typename Finish>
+std::vector<uint8_t> run_segments(sp_deflate* d, const uint8_t* data, size_t n, DeflateStats& S, double stage[6], Wait wait, Consume consume, Finish finish) {
+  const size_t nseg = sp_deflate_segments(d);
   S.segments = (double)nseg;
-  S.parse = 1;
-  TokenCoder coder(n, probes, old_header);
-  std::vector<uint8_t> arrived;  // the input as the coder reads it (Adler-32, stored blocks): the caller's bytes, or the device's as they arrive
+  std::vector<uint8_t> arrived;
   if (!data) arrived.resize(n);
-  if (nseg) DSPX(sp_deflate_segment_start(h.d, 0));
+  if (nseg) DSPX(sp_deflate_segment_start(d, 0));
   for (size_t s = 0; s < nseg; s++) {
-    if (s + 1 < nseg) DSPX(sp_deflate_segment_start(h.d, s + 1));
-    size_t first = 0, count = 0, ntok = 0;
-    const uint8_t* bytes; const uint32_t* tokens;
-    uint64_t carry[4];
-    double ms[6];
+    if (s + 1 < nseg) DSPX(sp_deflate_segment_start(d, s + 1));
+    Arrived a;
+    double ms[6] = {0, 0, 0, 0, 0, 0};
     const double t0 = now_ms();
-    DSPX(sp_deflate_segment_wait_tokens(h.d, s, &first, &count, &bytes, &tokens, &ntok, carry, ms));
+    wait(s, a, ms);
     const double t1 = now_ms();
     S.ms_wait += t1 - t0;
-    S.ms_links += ms[0]; S.ms_search_a += ms[1]; S.ms_search_b += ms[2]; S.ms_reach += ms[3]; S.ms_emit += ms[4]; S.ms_download += ms[5];
-    S.tokens += (double)ntok; S.device_fallbacks = (double)carry[3];
-    if (!data) memcpy(arrived.data() + first, bytes, std::min(n - first, count + 258));  // a match of this segment's tokens ends within 258 of its end
-    coder.code(data ? data : arrived.data(), data ? n : std::min(n, first + count + 258), tokens, ntok);
+    for (int i = 0; i < 6; i++) stage[i] += ms[i];
+    const size_t have = std::min(n, a.first + a.count + 258);
+    if (!data) memcpy(arrived.data() + a.first, a.bytes, have - a.first);
+    consume(data ? data : arrived.data(), data ? n : have, a);
     S.ms_parse += now_ms() - t1;
   }
   const double t2 = now_ms();
-  std::vector<uint8_t> z = coder.finish();
+  std::vector<uint8_t> z = finish();
   S.ms_parse += now_ms() - t2;
   return z;
+}
+
+// bincode(R1CSShape) in device memory: the 24-byte header from here, the three matrices serialised where they live. Returns its length.
+size_t shape_bincode_on_device(const Instance& I, DeviceBytes& buf, const std::string& who) {
+  const size_t n = 24 + 3 * 24 + 48 * (I.nnz[0] + I.nnz[1] + I.nnz[2]);
+  if (hipSetDevice(sp_ctx_device(I.c)) != hipSuccess) throw Error(who + ": hipSetDevice failed");
+  if (hipMalloc((void**)&buf.p, n) != hipSuccess) throw Error(who + ": no device memory for bincode(shape)");
+  const uint64_t head[3] = {I.num_cons, I.num_vars, I.num_inputs};
+  if (hipMemcpy(buf.p, head, 24, hipMemcpyHostToDevice) != hipSuccess) throw Error(who + ": copy failed");
+  const sp_sparse* ms[3] = {I.dA, I.dB, I.dC};
+  DSPX(sp_sparse_bincode(I.c, ms, 3, log_2(I.num_cons), log_2(2 * I.num_vars), buf.p + 24, n - 24));
+  return n;
 }
 }  // namespace
 
@@ -79,57 +92,50 @@ std::vector<uint8_t> zlib_device(sp_ctx* c, const uint8_t* data, const uint8_t* 
   S.device = 1;
   if (hipSetDevice(sp_ctx_device(c)) != hipSuccess) throw Error("zlib_device: hipSetDevice failed");
   if (parse < 0) parse = ctx_opt(c, "digest.device") == 2;
-  if (parse) {
-    std::vector<uint8_t> z = zlib_device_tokens(c, data, dev_data, n, probes, old_header, S, tile, group);
-    S.ms_total += now_ms() - t_begin;
-    return z;
-  }
+  const uint8_t* src = dev_data ? dev_data : data;
   DeflateHandle h;
-  DSPX(sp_deflate_open(c, dev_data ? dev_data : data, n, dev_data != nullptr, probes, &h.d));
-  const size_t nseg = sp_deflate_segments(h.d);
-  S.segments = (double)nseg;
-  MatchParser parser(n, probes, old_header);
-  // the input as the parser reads it: the caller's bytes, or the device's as they arrive with each segment
-  std::vector<uint8_t> arrived;
-  if (!data) arrived.resize(n);
-  if (nseg) DSPX(sp_deflate_segment_start(h.d, 0));
-  for (size_t s = 0; s < nseg; s++) {
-    if (s + 1 < nseg) DSPX(sp_deflate_segment_start(h.d, s + 1));  // searched while segment s is parsed
-    size_t first = 0, count = 0;
-    const uint8_t* bytes; const uint16_t* L; const uint32_t *A, *B;
-    double ms[4];
-    const double t0 = now_ms();
-    DSPX(sp_deflate_segment_wait(h.d, s, &first, &count, &bytes, &L, &A, &B, ms));
-    const double t1 = now_ms();
-    S.ms_wait += t1 - t0;
-    S.ms_links += ms[0]; S.ms_search_a += ms[1]; S.ms_search_b += ms[2]; S.ms_download += ms[3];
-    if (!data) {
-      const size_t have = std::min(n - first, count + 258);
-      memcpy(arrived.data() + first, bytes, have);
-    }
-    parser.parse(data ? data : arrived.data(), first, count, L, A, B);
-    S.ms_parse += now_ms() - t1;
+  double stage[6] = {0, 0, 0, 0, 0, 0};
+  std::vector<uint8_t> z;
+  if (parse) {  // the device hands over tokens; the coder behind it
+    DSPX(sp_deflate_open_parse(c, src, n, dev_data != nullptr, probes, tile, group, &h.d));
+    TokenCoder coder(n, probes, old_header);
+    const uint32_t* tokens = nullptr;
+    size_t ntok = 0;
+    uint64_t carry[4] = {0, 0, 0, 0};
+    z = run_segments(
+        h.d, data, n, S, stage,
+        [&](size_t s, Arrived& a, double* ms) { DSPX(sp_deflate_segment_wait_tokens(h.d, s, &a.first, &a.count, &a.bytes, &tokens, &ntok, carry, ms)); },
+        [&](const uint8_t* D, size_t bytes_end, const Arrived&) {
+          S.tokens += (double)ntok; S.device_fallbacks = (double)carry[3];
+          coder.code(D, bytes_end, tokens, ntok);
+        },
+        [&] { return coder.finish(); });
+    S.parse = 1;
+    S.ms_reach += stage[3]; S.ms_emit += stage[4]; S.ms_download += stage[5];
+  } else {  // the device hands over the tables L, A, B; the parser over them, and the coder behind it
+    DSPX(sp_deflate_open(c, src, n, dev_data != nullptr, probes, &h.d));
+    MatchParser parser(n, probes, old_header);
+    const uint16_t* L = nullptr;
+    const uint32_t *A = nullptr, *B = nullptr;
+    z = run_segments(
+        h.d, data, n, S, stage,
+        [&](size_t s, Arrived& a, double* ms) { DSPX(sp_deflate_segment_wait(h.d, s, &a.first, &a.count, &a.bytes, &L, &A, &B, ms)); },
+        [&](const uint8_t* D, size_t, const Arrived& a) { parser.parse(D, a.first, a.count, L, A, B); },
+        [&] { return parser.finish(); });
+    S.lookups = (double)parser.lookups; S.fallbacks = (double)parser.fallbacks;
+    S.ms_download += stage[3];
   }
-  const double t2 = now_ms();
-  std::vector<uint8_t> z = parser.finish();
-  S.ms_parse += now_ms() - t2;
-  S.lookups = (double)parser.lookups; S.fallbacks = (double)parser.fallbacks;
+  S.ms_links += stage[0]; S.ms_search_a += stage[1]; S.ms_search_b += stage[2];
   S.ms_total += now_ms() - t_begin;
   return z;
 }
 
-// bincode(R1CSShape) in device memory, the three matrices serialised where they live; the digest from there
+// the digest from bincode(R1CSShape) in device memory
 std::vector<uint8_t> Instance::compute_digest_device() const {
   DeflateStats S;
   const double t0 = now_ms();
-  const size_t n = 24 + 3 * 24 + 48 * (nnz[0] + nnz[1] + nnz[2]);
   DeviceBytes buf;
-  if (hipSetDevice(sp_ctx_device(c)) != hipSuccess) throw Error("Instance::compute_digest: hipSetDevice failed");
-  if (hipMalloc((void**)&buf.p, n) != hipSuccess) throw Error("Instance::compute_digest: no device memory for bincode(shape)");
-  const uint64_t head[3] = {num_cons, num_vars, num_inputs};
-  if (hipMemcpy(buf.p, head, 24, hipMemcpyHostToDevice) != hipSuccess) throw Error("Instance::compute_digest: copy failed");
-  const sp_sparse* ms[3] = {dA, dB, dC};
-  DSPX(sp_sparse_bincode(c, ms, 3, log_2(num_cons), log_2(2 * num_vars), buf.p + 24, n - 24));
+  const size_t n = shape_bincode_on_device(*this, buf, "Instance::compute_digest");
   S.ms_stream = now_ms() - t0;
   std::vector<uint8_t> z = zlib_device(c, nullptr, buf.p, n, 128, digest_old_header, &S);
   S.ms_total = now_ms() - t0;
@@ -137,16 +143,9 @@ std::vector<uint8_t> Instance::compute_digest_device() const {
   return z;
 }
 std::vector<uint8_t> Instance::shape_bincode_device() const {
-  const size_t n = 24 + 3 * 24 + 48 * (nnz[0] + nnz[1] + nnz[2]);
   DeviceBytes buf;
-  if (hipSetDevice(sp_ctx_device(c)) != hipSuccess) throw Error("Instance::shape_bincode_device: hipSetDevice failed");
-  if (hipMalloc((void**)&buf.p, n) != hipSuccess) throw Error("Instance::shape_bincode_device: no device memory");
-  const sp_sparse* ms[3] = {dA, dB, dC};
-  DSPX(sp_sparse_bincode(c, ms, 3, log_2(num_cons), log_2(2 * num_vars), buf.p + 24, n - 24));
-  std::vector<uint8_t> b(n);
-  const uint64_t head[3] = {num_cons, num_vars, num_inputs};
-  memcpy(b.data(), head, 24);
-  if (hipMemcpy(b.data() + 24, buf.p + 24, n - 24, hipMemcpyDeviceToHost) != hipSuccess) throw Error("Instance::shape_bincode_device: copy failed");
+  std::vector<uint8_t> b(shape_bincode_on_device(*this, buf, "Instance::shape_bincode_device"));
+  if (hipMemcpy(b.data(), buf.p, b.size(), hipMemcpyDeviceToHost) != hipSuccess) throw Error("Instance::shape_bincode_device: copy failed");
   return b;
 }
 }  // namespace spz

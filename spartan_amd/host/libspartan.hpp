@@ -20,6 +20,7 @@
 
 #include "../../include/spartan_host.h"  // the driver's C boundary; brings spartan_hip.h
 #include "transcript.hpp"
+#include "../csrc/tdefl_rules.hpp"  // the token word (TOK_*) and the rules behind the deflate declarations below
 
 namespace spz {
 
@@ -310,8 +311,8 @@ Fq seed_scalar(const char* domain, uint64_t seed);
 std::vector<uint8_t> zlib_level6_miniz(const uint8_t* data, size_t n, bool old_header = false);
 // the same compressor at another probe count (tdefl flags & 0xFFF: 16/32/128/256/512/768/1500 = miniz levels 4..10); tests pin each against miniz
 std::vector<uint8_t> zlib_miniz_probes(const uint8_t* data, size_t n, unsigned probes, bool old_header = false);
-// The match search of that compressor as one independent item per input position (deflate.cc; on the device: csrc/deflate_match.hip).
-// A table entry is dist | len << 16, (0, init) when nothing was found:
+// The match search of that compressor as one independent item per input position (the rule: csrc/tdefl_rules.hpp, find; over whole tables
+// on the host: deflate.cc; on the device: csrc/deflate_match.hip). A table entry is dist | len << 16, (0, init) when nothing was found:
 //   L[p]  low 16 bits of the greatest q < p whose 3-byte hash equals p's, 0 if none (p + 2 < n; 0 elsewhere)
 //   A[p]  the search at p that starts from nothing (init = 2)
 //   B[p]  the search at p that has to beat A[p - 1], where A[p - 1] leaves the parser's filter as a held match; 0 elsewhere
@@ -319,9 +320,10 @@ std::vector<uint8_t> zlib_miniz_probes(const uint8_t* data, size_t n, unsigned p
 void deflate_links_host(const uint8_t* data, size_t n, uint16_t* L);
 void deflate_matches_host(const uint8_t* data, size_t n, unsigned probes, const uint16_t* L, uint32_t* A, uint32_t* B);
 // tdefl's parser, block decisions, Huffman coding and bit output (all sequential, all on the host) over such tables, segment by segment:
-// parse(D, first, count, L, A, B) takes the tables of positions [first, first + count) — segments in order, without gaps — and needs
-// D[0, min(n, first + count + 258)) readable. A lookup that neither table answers (a lazy chain of three or more matches whose held
-// length is not A[p - 1]'s) is searched on the spot and counted in `fallbacks`.
+// a table look-up, the walk of tdefl_rules.hpp and the coder's step for each token it emits. parse(D, first, count, L, A, B) takes the
+// tables of positions [first, first + count) — segments in order, without gaps — and needs D[0, min(n, first + count + 258)) readable. A
+// lookup that neither table answers (a lazy chain of three or more matches whose held length is not A[p - 1]'s) is searched on the spot
+// and counted in `fallbacks`.
 struct MatchParser {
   MatchParser(size_t n, unsigned probes, bool old_header);
   ~MatchParser();
@@ -336,12 +338,12 @@ struct MatchParser {
 // one call over whole tables: equals zlib_miniz_probes(data, n, probes, old_header) byte for byte
 std::vector<uint8_t> zlib_from_matches(const uint8_t* data, size_t n, const uint16_t* L, const uint32_t* A, const uint32_t* B, unsigned probes,
                                        bool old_header, uint64_t* lookups = nullptr, uint64_t* fallbacks = nullptr);
-// The parse of that compressor restated as walks between free states (deflate.cc; on the device: the parse kernels of csrc/deflate_match.hip):
-// one 32-bit token per literal or match, in stream order. A literal carries its byte in bits 0..7 and length 0; a match (len, dist) carries
-// dist - 1 in bits 0..14 and len in bits 15..23. TOK_CHECK: tdefl's block check runs after this token (a literal emitted together with a match
-// of >= 128 has none); TOK_HELD: a match is held when that check runs (lookahead_pos is one past the emitted bytes). TOK_VALID is always
-// set, so that 0 is "no token starts here" in the device's one-word-per-position form.
-constexpr uint32_t TOK_VALID = 1u << 31, TOK_CHECK = 1u << 30, TOK_HELD = 1u << 29;
+// The parse of that compressor restated as walks between free states (the rule: csrc/tdefl_rules.hpp, walk; on the device: the parse
+// kernels of csrc/deflate_match.hip): one 32-bit token per literal or match, in stream order, laid out as tdefl_rules.hpp says (TOK_CHECK:
+// tdefl's block check runs after this token; TOK_HELD: a match is held when it runs; TOK_VALID: always set).
+using tdefl::TOK_VALID;
+using tdefl::TOK_CHECK;
+using tdefl::TOK_HELD;
 // what deflate_tokens_host counts: conditions on an input that the tests ask for, not measurements
 enum TokCounter { TOKC_WALKS, TOKC_LOOKUPS, TOKC_FALLBACKS, TOKC_FREE_LONG, TOKC_LIT_AND_LONG, TOKC_SPAN_TILE, TOKC_SPAN_GROUP, TOKC_SEAM_HELD,
                   TOKC_TOKENS, TOKC_MAX_JUMP, TOKC_COUNT };
