@@ -1,13 +1,15 @@
 // Stand-alone host program over spartan_amd/host/deflate.cc (no device, no Python): two uses.
 //   check   the token model, the token coder and the parser over match tables (whole, and fed in segments of 32 768 and 49 999 positions as
-//           it is behind the device search) against the sequential deflater on a few inputs; built with sanitizers this is the host-code
-//           sanitizer run of the deflate restatements:
+//           it is behind the device search), and the coder split into block records, per-block plans and independent token items (found in
+//           segments of 32 768 and 49 999 positions as the device finds them) against the sequential deflater on a few inputs; built with
+//           sanitizers this is the host-code sanitizer run of the deflate restatements:
 //             clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
 //                 bench/deflate_host_probe.cc spartan_amd/host/deflate.cc -o deflate_host_probe_san && ./deflate_host_probe_san check
 //   time K  where the host's time goes on bincode(shape) of a 2^K instance (three entries a row and matrix, random scalars: the bytes of
 //           bench/digest_probe.py's instance in kind): the sequential deflater, the parser over match tables with its coding
 //           (zlib_from_matches: what runs behind the device search), the token coder alone (zlib_from_tokens: what runs behind the device
-//           parse) and Adler-32 alone. Build with -O2 and without sanitizers.
+//           parse), the block records and the stream from them (what digest.device = 3 leaves the host is BlockPlanner alone, timed by itself)
+//           and Adler-32 alone. Build with -O2 and without sanitizers.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -57,6 +59,9 @@ int check() {
   for (auto& c : r) c = (uint8_t)rnd();
   inputs.push_back({"random 66000", r});
   inputs.push_back({"shape 2^9", shape_like(9)});
+  std::vector<uint8_t> mixed = words(40000, 20);  // a coded block that runs into random bytes, then stored blocks
+  for (int i = 0; i < 130000; i++) mixed.push_back((uint8_t)rnd());
+  inputs.push_back({"words+random", mixed});
   int bad = 0;
   for (const auto& in : inputs) {
     const std::vector<uint8_t>& x = in.second;
@@ -80,6 +85,19 @@ int check() {
         const bool same = mp.finish() == want;
         printf("%-16s %4u probes: MatchParser in segments of %5zu: %8llu look-ups, %6llu searched on the spot: %s\n", in.first.c_str(), probes, seg,
                (unsigned long long)mp.lookups, (unsigned long long)mp.fallbacks, same ? "equal" : "DIFFERS");
+        bad += !same;
+      }
+      for (size_t seg : {(size_t)0, (size_t)32768, (size_t)49999}) {  // the coder split as the device runs it
+        const size_t cap = k / 11306 + 4;
+        std::vector<uint64_t> rec(BLOCK_REC * cap);
+        std::vector<uint16_t> hist(BLOCK_HIST * cap);
+        uint64_t bc[BLKC_COUNT], st3[3];
+        const size_t nb = deflate_blocks_host(tok.data(), k, n, seg, rec.data(), hist.data(), cap, bc);
+        const bool same = zlib_from_blocks(rec.data(), hist.data(), nb, tok.data(), x.data(), n, probes, false, st3) == want;
+        printf("%-16s %4u probes: blocks in segments of %5zu: %3zu (full %llu, ratio %llu, stored %llu, static %llu, stored off a byte %llu), open over %llu seams, "
+               "widest span %llu: %s\n", in.first.c_str(), probes, seg, nb, (unsigned long long)bc[BLKC_FULL], (unsigned long long)bc[BLKC_RATIO],
+               (unsigned long long)st3[0], (unsigned long long)st3[1], (unsigned long long)st3[2], (unsigned long long)bc[BLKC_SEAM_OPEN],
+               (unsigned long long)bc[BLKC_MAX_SPAN], same ? "equal" : "DIFFERS");
         bad += !same;
       }
       printf("%-16s %4u probes: %8zu tokens, %6llu look-ups searched on the spot, longest jump %3llu, blocks full/ratio/stored/static %llu/%llu/%llu/%llu: %s\n",
@@ -114,6 +132,24 @@ int time_phases(size_t log2) {
   const bool ok2 = zlib_from_tokens(x.data(), n, tok.data(), k, 128, false) == want;
   const double t_tokens = now_ms() - t0;
   printf("token coder alone (zlib_from_tokens)                    %10.1f   %s, %zu tokens\n", t_tokens, ok2 ? "equal" : "DIFFERS", k);
+  {
+    const size_t cap = k / 11306 + 4;
+    std::vector<uint64_t> rec(BLOCK_REC * cap);
+    std::vector<uint16_t> hist(BLOCK_HIST * cap);
+    t0 = now_ms();
+    const size_t nb = deflate_blocks_host(tok.data(), k, n, 4194304, rec.data(), hist.data(), cap, nullptr);
+    const double t_rec = now_ms() - t0;
+    t0 = now_ms();
+    const bool ok3 = zlib_from_blocks(rec.data(), hist.data(), nb, tok.data(), x.data(), n, 128, false, nullptr) == want;
+    const double t_blocks = now_ms() - t0;
+    t0 = now_ms();
+    BlockPlanner bp(128, false);
+    BlockPlan p;
+    for (size_t b = 0; b < nb; b++) bp.plan(rec.data() + BLOCK_REC * b, hist.data() + BLOCK_HIST * b, p);
+    printf("block records on the host (the device's share, form 3)  %10.1f   %zu blocks\n", t_rec, nb);
+    printf("stream from the records (zlib_from_blocks)              %10.1f   %s\n", t_blocks, ok3 ? "equal" : "DIFFERS");
+    printf("tables, headers, offsets alone (BlockPlanner: form 3)   %10.1f   %.1f us a block\n", now_ms() - t0, 1e3 * (now_ms() - t0) / (double)nb);
+  }
   t0 = now_ms();
   uint32_t s1 = 1, s2 = 0;
   for (size_t i = 0; i < n;) { const size_t blk = std::min<size_t>(5552, n - i); for (size_t j = 0; j < blk; j++) { s1 += x[i + j]; s2 += s1; } s1 %= 65521; s2 %= 65521; i += blk; }

@@ -462,6 +462,38 @@ int32_t sp_deflate_segment_wait_tokens(sp_deflate* d, size_t s, size_t* first, s
                                        size_t* ntok, uint64_t* carry /*4*/, double* ms /*6*/);
 int32_t sp_deflate_tokens(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, uint32_t* tokens /*n*/,
                           size_t* ntok, uint64_t* info /*2*/);
+/* tdefl's CODER over those tokens on the device as well (deflate_emit.hip): neither the tokens nor the input bytes come down. Per segment the
+ * device finds the block boundaries (prefix sums of the token costs, a chain of first-hit searches of the block check), the blocks'
+ * histograms and the segment's Adler-32 pair; the host receives BLOCK RECORDS, builds each block's Huffman tables, header and bit offset
+ * from its histogram (spartan_amd/host/deflate.cc: BlockPlanner) and hands them back; the device then ORs every token's bits into the
+ * resident output at its offset and copies stored blocks from the input. A record is 6 64-bit words — index of the block's first token in
+ * the whole list, its tokens, its input bytes, the rule that closed it (1 code buffer, 2 ratio, 3 finish), lookahead_pos - lz_dict_pos and
+ * dict_size of tdefl's stored-block test — with 320 16-bit counters beside it (288 literal/length symbols, 32 distance symbols). The tokens
+ * of the block still open at a segment's end (at most 58249) lead the next segment's list on the device. Device scratch grows by about 24
+ * bytes a position of one segment; the compressed bytes stay resident (at most 1.5 n and 512 bytes a block) and come down once.
+ *   sp_deflate_open_emit            sp_deflate_open_parse for this form; chunk = tokens a workgroup of the emission, 256..65536 (0: 4096), else
+ *                                   SP_EINVAL. sp_deflate_segment_start queues the block stage behind the parse; the other wait calls are
+ *                                   SP_EINVAL.
+ *   sp_deflate_segment_wait_blocks  wait for segment s: first, count; nblocks, records, hist: the blocks CLOSED in this segment (the last
+ *                                   segment closes the finish block, which may be empty), valid until segment s + 2 is started; adler (may be
+ *                                   NULL; 2): (sum d, sum (count - i) d) mod 65521 over the segment's bytes d_0 .. d_count-1; carry, ms: as
+ *                                   sp_deflate_segment_wait_tokens gives them, the sixth stage being the block stage with its copy.
+ *   sp_deflate_segment_emit         queue segment s's emission, after its wait and before segment s + 2 is started: per block 6 words of plan
+ *                                   (bit offset of its first bit, header bits, kind 0 dynamic / 1 static / 2 stored, bit offset of its first
+ *                                   token or stored byte, bit offset of its end-of-block symbol, input position of its first byte), 320 words
+ *                                   code | size << 16, and 320 bytes holding the header bits from its first bit on. nblocks as waited for.
+ *   sp_deflate_emit_bytes           wait for every queued emission and copy the first nbytes of the stream down (the two zlib header bytes and
+ *                                   the trailer are the host's); ms (may be NULL; 1): device milliseconds of the emissions.
+ *   sp_deflate_blocks               all segments in one call, without emission: the records and histograms of the whole input (cap blocks at
+ *                                   most, else SP_EINVAL); n == 0 gives the one empty finish block. */
+int32_t sp_deflate_open_emit(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, size_t chunk,
+                             sp_deflate** out);
+int32_t sp_deflate_segment_wait_blocks(sp_deflate* d, size_t s, size_t* first, size_t* count, size_t* nblocks, const uint64_t** records,
+                                       const uint16_t** hist, uint64_t* adler /*2*/, uint64_t* carry /*4*/, double* ms /*6*/);
+int32_t sp_deflate_segment_emit(sp_deflate* d, size_t s, size_t nblocks, const uint64_t* plans, const uint32_t* tables, const uint8_t* headers);
+int32_t sp_deflate_emit_bytes(sp_deflate* d, uint8_t* out, size_t nbytes, double* ms /*1*/);
+int32_t sp_deflate_blocks(sp_ctx* ctx, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, uint64_t* records,
+                          uint16_t* hist, size_t cap, size_t* nblocks);
 /* multiply_vec (sparse_mlpoly.rs:454-464): out[row] = sum val * z[col]; out has num_rows elements. */
 int32_t sp_sparse_mulvec(sp_ctx* ctx, const sp_sparse* m, const sp_table* z, sp_table** out);
 /* compute_eval_table_sparse (sparse_mlpoly.rs:466-481) for nm matrices, combined as r1csproof.rs:275-283 does:

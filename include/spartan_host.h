@@ -70,7 +70,8 @@ void* spz_instance_synthetic(void* ctx, size_t num_cons, size_t num_vars, size_t
 void spz_instance_free(void* inst);
 /* R1CSShape::get_digest (r1cs.rs:154-158): the zlib stream the proofs absorb, computed on first use (option digest.device: 1 = stream and match
  * search on the device, parser and coding on the calling thread; 2 = the lazy parse on the device too, the calling thread codes its tokens;
- * 0 = all of it on the host; the same bytes). Size, then fill; 0 with
+ * 3 = the coder on the device too, the calling thread builds each block's Huffman tables and bit offsets; 0 = all of it on the host; the
+ * same bytes). Size, then fill; 0 with
  * spz_last_error() when the computation failed (a zlib stream is never empty). */
 size_t spz_instance_digest(void* inst, uint8_t* out, size_t cap);
 /* A caller that already holds the digest of a real libspartan Instance sets it instead. */
@@ -265,6 +266,28 @@ size_t spz_zlib_from_tokens(const uint8_t* data, size_t n, const uint32_t* token
 size_t spz_zlib_device_parse(void* ctx, const uint8_t* data, size_t n, unsigned probes, int old_header, int parse, size_t tile, size_t group,
                              uint8_t* out, size_t cap, double* stats, size_t stats_cap);
 void spz_instance_digest_stats_all(void* inst, double* stats, size_t stats_cap);
+/* The coder split as the device runs it with digest.device = 3 (deflate.cc; the device side: spartan_hip.h, sp_deflate_open_emit). A block
+ * record is 6 words: index of the block's first token, its tokens, its input bytes, the rule that closed it (1 code buffer, 2 ratio,
+ * 3 finish), and lookahead_pos - lz_dict_pos and dict_size of tdefl's stored-block test; beside it 320 16-bit counters, 288 of the
+ * literal/length alphabet and 32 of the distances. spz_deflate_blocks_host finds the records of a token list of n input bytes segment by
+ * segment (`segment` input positions; 0: one) as the device does and returns their number, at most cap, -1 with spz_last_error() for a
+ * block of more than 58249 tokens; counters (may be NULL; 7) = blocks closed by the code-buffer rule, by the ratio rule, empty final
+ * blocks, seams an open block was carried over, the most segments one block touched, blocks that end with a segment's last token, the
+ * most tokens of a block. spz_zlib_from_blocks builds tables, headers and bit offsets from the histograms and ORs every token's bits in
+ * at its offset: spz_zlib_probes' bytes. Size, then fill; stats (may be NULL; 3) = stored blocks, static blocks, stored blocks after a
+ * block that ends within a byte. */
+long long spz_deflate_blocks_host(const uint32_t* tokens, size_t ntok, size_t n, size_t segment, uint64_t* records, uint16_t* hist, size_t cap,
+                                  uint64_t* counters);
+size_t spz_zlib_from_blocks(const uint64_t* records, const uint16_t* hist, size_t nblocks, const uint32_t* tokens, const uint8_t* data, size_t n,
+                            unsigned probes, int old_header, uint8_t* out, size_t cap, uint64_t* stats);
+/* spz_zlib_device_parse with the third form: parse = 2 the coder's block boundaries, histograms, bit emission, stored-block copies and
+ * Adler-32 on the device too (the calling thread builds the Huffman tables and bit offsets per block), -1 what digest.device says (3 = this
+ * form); chunk = tokens a workgroup of the emission, 256..65536 (0: 4096). stats receives up to stats_cap of 26 doubles: the 17 of
+ * spz_zlib_device_parse, then 1.0 when the device coded, the tokens it coded, blocks, stored blocks, static blocks, device milliseconds of the
+ * block stage and of the bit emission, host milliseconds of the table building and of the download of the compressed bytes.
+ * spz_instance_digest_stats_all reports the same 26. */
+size_t spz_zlib_device_emit(void* ctx, const uint8_t* data, size_t n, unsigned probes, int old_header, int parse, size_t tile, size_t group, size_t chunk,
+                            uint8_t* out, size_t cap, double* stats, size_t stats_cap);
 /* Fiat-Shamir pieces. spz_keccak_run_variant: one permutation by the named form; 1 = ran, 0 = this CPU or build does not have it. */
 int spz_keccak_run_variant(const char* name, uint64_t state[25]);
 void spz_shake256(const uint8_t* in, size_t n, uint8_t* out, size_t outlen);

@@ -3,7 +3,9 @@
 //   sp_sparse_bincode    the matrices' part of bincode(R1CSShape), serialised from the resident entries into a device byte buffer
 //   sp_deflate_*         tdefl's hash-chain match search, one input position per lane; and, for a handle opened by sp_deflate_open_parse,
 //                        tdefl's lazy PARSE over the tables it fills, so that the host receives tokens instead of tables
-// The block decisions and the Huffman coding are sequential and stay on the host (deflate.cc: MatchParser over tables, TokenCoder over tokens).
+// The block decisions and the Huffman coding stay on the host (deflate.cc: MatchParser over tables, TokenCoder over tokens), unless the handle
+// was opened by sp_deflate_open_emit: then the coder's block boundaries, histograms and bit emission are queued behind the parse
+// (deflate_emit.hip) and the host keeps the Huffman tables and bit offsets alone.
 // tdefl's rules themselves — hash, probe budget, find, the candidate filter, walk, the token word — are tdefl_rules.hpp, which the host runs
 // too; this file holds the kernels that apply them a position per lane, and the segment pipeline around them.
 //
@@ -42,6 +44,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 
+#include "deflate_emit.hpp"
 #include "internal.hpp"
 #include "tdefl_rules.hpp"
 
@@ -237,6 +240,10 @@ struct sp_deflate {
   DpCarry* carry = nullptr;  // [nseg + 1]: carry[s] is segment s's entry
   void* sel_tmp = nullptr;
   size_t sel_bytes = 0;
+  // the coder on the device too (sp_deflate_open_emit; deflate_emit.hip): the compacted tokens stay in its lists, the host gets block records
+  bool coded = false;
+  size_t chunk = 0;
+  DeEmit* emit = nullptr;
   size_t ntiles_of(size_t count) const { return (count + T - 1) / T; }
   size_t ngroups_of(size_t count) const { return (count + (size_t)T * G - 1) / ((size_t)T * G); }
   size_t first_of(size_t s) const { return s * seg; }
@@ -244,8 +251,10 @@ struct sp_deflate {
   // byte offsets into a pinned slot, set once at open. A and the tokens stand at 0.
   //   tables  [A: 4 seg][B: 4 seg][L: 2 seg][bytes: seg + DM_AHEAD]
   //   parse   [tokens: 4 (seg + 1), padded to 8][their number: 8][the next segment's entry: 16][bytes: seg + DM_AHEAD]
+  //   coded   [the next segment's entry: 16]: tokens and bytes stay on the device, the records come down through the coder's own slots
   struct Slot { size_t B = 0, L = 0, N = 0, C = 0, D = 0, bytes = 0; } slot;
   void lay_out_slot() {
+    if (coded) { slot.D = sizeof(DpCarry); slot.bytes = slot.D; return; }
     if (parse) { slot.N = (4 * (seg + 1) + 7) / 8 * 8; slot.C = slot.N + 8; slot.D = slot.C + sizeof(DpCarry); }
     else { slot.B = 4 * seg; slot.L = 8 * seg; slot.D = 10 * seg; }
     slot.bytes = slot.D + seg + DM_AHEAD;
@@ -258,6 +267,7 @@ void sp_deflate_close(sp_deflate* d) {
   if (!d) return;
   (void)hipSetDevice(d->ctx->dev);
   if (d->st) (void)hipStreamSynchronize(d->st);
+  de_close(d->emit);
   for (auto& slot : d->ev)
     for (hipEvent_t e : slot)
       if (e) (void)hipEventDestroy(e);
@@ -315,6 +325,7 @@ static int32_t deflate_open(sp_deflate* d, const uint8_t* data, int on_device) {
     HIPCHK(hipMalloc((void**)&d->Et, 4 * tiles));
     HIPCHK(hipMalloc((void**)&d->carry, sizeof(DpCarry) * (d->nseg + 1)));
     HIPCHK(hipMemsetAsync(d->carry, 0, sizeof(DpCarry) * (d->nseg + 1), d->st));
+    if (d->coded) SPCHK(de_open(&d->emit, d->st, d->dD, d->n, seg, d->nseg, d->chunk));
   }
   for (uint8_t*& p : d->pin) HIPCHK(hipHostMalloc((void**)&p, d->slot.bytes, hipHostMallocDefault));
   HIPCHK(hipMemsetAsync(d->head, 0, 2 * DM_DICT, d->st));
@@ -323,16 +334,17 @@ static int32_t deflate_open(sp_deflate* d, const uint8_t* data, int on_device) {
   return SP_OK;
 }
 static int32_t deflate_open_form(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, bool parse, size_t tile, size_t group,
-                                 sp_deflate** out) {
+                                 sp_deflate** out, bool coded = false, size_t chunk = 0) {
   if (!c || !out || (n && !data) || probes == 0 || probes > 0xFFF) return SP_EINVAL;
   if (!tile) tile = 1024;
   if (!group) group = 64;
   if (parse && (tile < 512 || tile > 4096 || group < 2 || group > 4096)) return SP_EINVAL;  // a tile holds a jump (384) and fits the exits' LDS
+  if (coded && chunk && (chunk < 256 || chunk > 65536)) return SP_EINVAL;                    // a chunk is a workgroup's worth of tokens at least
   sp_deflate* d = new (std::nothrow) sp_deflate();
   if (!d) return SP_ENOMEM;
   d->ctx = c;
   d->n = n;
-  d->parse = parse;
+  d->parse = parse; d->coded = coded; d->chunk = chunk;
   d->T = (uint32_t)tile; d->G = (uint32_t)group;
   const size_t opt = (size_t)c->opt.v[OPT_DIGEST_SEGMENT];
   d->seg = n < opt ? (n < DM_DICT ? DM_DICT : n) : opt;  // a short input is one segment of its own length (never below the window)
@@ -349,6 +361,10 @@ int32_t sp_deflate_open(sp_ctx* c, const uint8_t* data, size_t n, int on_device,
 }
 int32_t sp_deflate_open_parse(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, sp_deflate** out) {
   return deflate_open_form(c, data, n, on_device, probes, true, tile, group, out);
+}
+int32_t sp_deflate_open_emit(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, size_t chunk,
+                             sp_deflate** out) {
+  return deflate_open_form(c, data, n, on_device, probes, true, tile, group, out, true, chunk);
 }
 size_t sp_deflate_segments(const sp_deflate* d) { return d ? d->nseg : 0; }
 
@@ -398,16 +414,18 @@ int32_t sp_deflate_segment_start(sp_deflate* d, size_t s) {
     hipLaunchKernelGGL(k_dp_tokens, dm_grid(count), dim3(DM_BLOCK), 0, st, d->dD, n, Lw, Ab, Bb, first, cnt, d->mp[0], d->mp[1], (const uint16_t*)d->delta, d->tok,
                        carry);
     if (hipGetLastError() != hipSuccess) return SP_EHIP;
-    // the compaction writes the dense list and its length straight into the pinned slot
-    HIPCHK(rocprim::select(d->sel_tmp, d->sel_bytes, (const uint32_t*)d->tok, d->at<uint32_t>(k, 0), d->at<size_t>(k, d->slot.N), count + 1, DpNonZero(), st));
+    // the compaction writes the dense list and its length straight into the pinned slot, or into the device coder's list
+    HIPCHK(rocprim::select(d->sel_tmp, d->sel_bytes, (const uint32_t*)d->tok, d->coded ? de_tokens(d->emit, s) : d->at<uint32_t>(k, 0),
+                           d->coded ? de_ntok(d->emit, s) : d->at<size_t>(k, d->slot.N), count + 1, DpNonZero(), st));
     HIPCHK(hipEventRecord(d->ev[k][6], st));
+    if (d->coded) SPCHK(de_segment_blocks(d->emit, s, first, count));
     HIPCHK(hipMemcpyAsync(d->at<DpCarry>(k, d->slot.C), carry + 1, sizeof(DpCarry), hipMemcpyDeviceToHost, st));
   } else {
     HIPCHK(hipMemcpyAsync(d->at<uint32_t>(k, 0), d->Ab + 1, 4 * count, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(d->at<uint32_t>(k, d->slot.B), d->Bb, 4 * count, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(d->at<uint16_t>(k, d->slot.L), Lseg, 2 * count, hipMemcpyDeviceToHost, st));
   }
-  HIPCHK(hipMemcpyAsync(d->at<uint8_t>(k, d->slot.D), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
+  if (!d->coded) HIPCHK(hipMemcpyAsync(d->at<uint8_t>(k, d->slot.D), d->dD + first, nbytes, hipMemcpyDeviceToHost, st));
   if (s + 1 < d->nseg) {  // count == seg >= 32768 here: what the next segment needs of this one
     HIPCHK(hipMemcpyAsync(d->Ab, d->Ab + count, 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(d->Lw, d->Lw + count, 2 * DM_DICT, hipMemcpyDeviceToDevice, st));
@@ -418,8 +436,8 @@ int32_t sp_deflate_segment_start(sp_deflate* d, size_t s) {
 }
 
 // segment s of a handle of the given form is ready in its pinned slot
-static int32_t deflate_segment_ready(sp_deflate* d, bool parse, size_t s, size_t* first, size_t* count) {
-  if (!d || d->parse != parse || s >= d->started || s + 2 < d->started) return SP_EINVAL;
+static int32_t deflate_segment_ready(sp_deflate* d, bool parse, size_t s, size_t* first, size_t* count, bool coded = false) {
+  if (!d || d->parse != parse || d->coded != coded || s >= d->started || s + 2 < d->started) return SP_EINVAL;
   HIPCHK(hipSetDevice(d->ctx->dev));
   HIPCHK(hipEventSynchronize(d->ev[s & 1][4]));
   if (first) *first = d->first_of(s);
@@ -428,7 +446,7 @@ static int32_t deflate_segment_ready(sp_deflate* d, bool parse, size_t s, size_t
 }
 // device time of the segment's stages, between the events in the order the form recorded them (event 4 is the last of both)
 //   tables  links, search A, search B, copies
-//   parse   links, search A, search B, reachability, tokens + compaction, copies
+//   parse   links, search A, search B, reachability, tokens + compaction, copies (coded: the block stage and the records' copy)
 static int32_t deflate_stage_ms(const sp_deflate* d, int k, double* ms) {
   static const int order[2][7] = {{0, 1, 2, 3, 4, -1, -1}, {0, 1, 2, 3, 5, 6, 4}};
   const int* o = order[d->parse];
@@ -463,6 +481,28 @@ int32_t sp_deflate_segment_wait_tokens(sp_deflate* d, size_t s, size_t* first, s
   return deflate_stage_ms(d, k, ms);
 }
 
+int32_t sp_deflate_segment_wait_blocks(sp_deflate* d, size_t s, size_t* first, size_t* count, size_t* nblocks, const uint64_t** records,
+                                       const uint16_t** hist, uint64_t* adler, uint64_t* carry, double* ms) {
+  SPCHK(deflate_segment_ready(d, true, s, first, count, true));
+  const int k = (int)(s & 1);
+  SPCHK(de_blocks(d->emit, s, nblocks, records, hist, adler));
+  if (carry) {
+    const DpCarry* c = d->at<DpCarry>(k, d->slot.C);
+    carry[0] = d->first_of(s) + d->count_of(s) + c->entry; carry[1] = c->sl; carry[2] = c->sd; carry[3] = c->fallbacks;
+  }
+  return deflate_stage_ms(d, k, ms);
+}
+int32_t sp_deflate_segment_emit(sp_deflate* d, size_t s, size_t nblocks, const uint64_t* plans, const uint32_t* tables, const uint8_t* headers) {
+  if (!d || !d->coded || s >= d->started || s + 2 < d->started) return SP_EINVAL;
+  HIPCHK(hipSetDevice(d->ctx->dev));
+  return de_segment_emit(d->emit, s, nblocks, plans, tables, headers);
+}
+int32_t sp_deflate_emit_bytes(sp_deflate* d, uint8_t* out, size_t nbytes, double* ms) {
+  if (!d || !d->coded) return SP_EINVAL;
+  if (!d->emit) return nbytes ? SP_EINVAL : SP_OK;  // an empty input has no segment and no bytes here
+  HIPCHK(hipSetDevice(d->ctx->dev));
+  return de_bytes(d->emit, out, nbytes, ms);
+}
 }  // extern "C"
 
 // the whole input through an opened handle, one segment after the other: each(s) waits for segment s and takes what it wants; closes the handle
@@ -500,6 +540,34 @@ int32_t sp_deflate_tokens(sp_ctx* c, const uint8_t* data, size_t n, int on_devic
   });
   *ntok = total;
   if (info) { info[0] = held; info[1] = fallbacks; }
+  return rc;
+}
+int32_t sp_deflate_blocks(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, size_t tile, size_t group, uint64_t* records,
+                          uint16_t* hist, size_t cap, size_t* nblocks) {
+  if (!nblocks || !records || !hist) return SP_EINVAL;
+  if (!n) {  // no segment: the one block is the empty finish block
+    if (!c || !cap) return SP_EINVAL;
+    memset(records, 0, 8 * DE_REC_WORDS);
+    memset(hist, 0, 2 * DE_HIST);
+    records[3] = tdefl::RULE_FINISH;
+    *nblocks = 1;
+    return SP_OK;
+  }
+  sp_deflate* d = nullptr;
+  SPCHK(sp_deflate_open_emit(c, data, n, on_device, probes, tile, group, 0, &d));
+  size_t total = 0;
+  const int32_t rc = deflate_whole(d, [&](size_t s) -> int32_t {
+    size_t nb = 0;
+    const uint64_t* r;
+    const uint16_t* h;
+    SPCHK(sp_deflate_segment_wait_blocks(d, s, nullptr, nullptr, &nb, &r, &h, nullptr, nullptr, nullptr));
+    if (total + nb > cap) return SP_EINVAL;
+    memcpy(records + DE_REC_WORDS * total, r, 8 * DE_REC_WORDS * nb);
+    memcpy(hist + DE_HIST * total, h, 2 * DE_HIST * nb);
+    total += nb;
+    return SP_OK;
+  });
+  *nblocks = total;
   return rc;
 }
 int32_t sp_deflate_matches(sp_ctx* c, const uint8_t* data, size_t n, int on_device, uint32_t probes, uint16_t* L, uint32_t* A, uint32_t* B) {

@@ -31,7 +31,7 @@
   X(HOST_KECCAK, "host.keccak", 0, 0, 3, 0, "PROC. Keccak-f[1600] form of the host transcript: 0 = fastest by calibration, 1 = plain, 2 = BMI2, 3 = AVX-512") \
   X(HOST_PROOF_GATE, "host.proof_gate", 0, 0, 1, 0, "PROC. several proofs in flight on one device: admit one at a time to the throughput-bound part") \
   X(HOST_PIN_THREAD, "host.pin_thread", 1, 0, 1, 0, "PROC. sp_ctx_create narrows the calling thread's CPU affinity to the cores of the GPU's own NUMA node (sysfs local_cpulist of its PCI function): a proof is ~330 PCIe round trips between that thread and the device; 0 = leave the affinity alone") \
-  X(DIGEST_DEVICE, "digest.device", 1, 0, 2, 0, "R1CSShapeDigest of an instance: 1 = bincode(shape) serialised and tdefl's match search run on the device, the parse and the Huffman coding behind it on the host; 2 = the lazy parse on the device too (tiles of 1024 positions, groups of 64 tiles), the host codes its tokens; 0 = entries downloaded, everything on the host (the same bytes)") \
+  X(DIGEST_DEVICE, "digest.device", 1, 0, 3, 0, "R1CSShapeDigest of an instance: 1 = bincode(shape) serialised and tdefl's match search run on the device, the parse and the Huffman coding behind it on the host; 2 = the lazy parse on the device too (tiles of 1024 positions, groups of 64 tiles), the host codes its tokens; 3 = the coder's block boundaries, histograms, bit emission (4096 tokens a workgroup), stored-block copies and Adler-32 on the device as well, the host builds each block's Huffman tables and bit offsets; 0 = entries downloaded, everything on the host (the same bytes)") \
   X(DIGEST_SEGMENT, "digest.segment", 4194304, 32768, 268435456, 0, "input positions the device match search takes at a time (about 30 bytes of device scratch and 22 bytes of pinned host memory a position; with digest.device = 2 about 38 and 10)") \
   X(IPA_UNIFIED_TREE,"ipa.unified_tree", 0, 0, 1, 1, "inner-product rounds always with the unified (complete) addition tree")               \
   X(IPA_DEDICATED_UPLOADED, "ipa.dedicated_uploaded", 0, 0, 1, 1, "dedicated (incomplete, two-multiplication) addition tree also for caller-supplied generator lists (default: only for sets the library derived by hash-to-curve)") \

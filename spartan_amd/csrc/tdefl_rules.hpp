@@ -130,4 +130,79 @@ SP_HD void walk(const uint8_t* __restrict__ D, WalkState& w, size_t end, Lookup&
     }
   } while (w.sl && w.q < end);
 }
+
+// ---- the coder's rules: what a token costs, what it codes to, and when a block ends. tdefl's LZ code buffer holds a flag byte for every
+// eight tokens (the first opened with the block), one byte a literal and three a match; the block check after a TOK_CHECK token reads the
+// buffer's fill and the input bytes of the block so far, and the stored-block test at a check reads lookahead_pos and dict_size of the
+// parser's step that the token closes.
+constexpr unsigned LZBUF = 64 * 1024;
+constexpr unsigned BLOCK_TOKENS = 58249;  // the most tokens of a block: literals until 1 + k + k / 8 > 65528 (k = 58248), and one unchecked literal more
+enum BlockRule : uint32_t { RULE_NONE = 0, RULE_FULL = 1, RULE_RATIO = 2, RULE_FINISH = 3 };
+SP_HD unsigned tok_code_bytes(uint32_t t) { return tok_len(t) ? 3u : 1u; }
+SP_HD unsigned tok_input_bytes(uint32_t t) { const unsigned l = tok_len(t); return l ? l : 1u; }
+// the code buffer's fill after k tokens of a block whose tok_code_bytes sum to `sum`
+SP_HD uint64_t code_bytes_after(uint64_t sum, uint64_t k) { return 1 + sum + k / 8; }
+SP_HD BlockRule block_check(uint64_t code_bytes, uint64_t total_lz_bytes) {
+  if (code_bytes > LZBUF - 8) return RULE_FULL;
+  if (total_lz_bytes > 31 * 1024 && ((code_bytes * 115) >> 7) >= total_lz_bytes) return RULE_RATIO;
+  return RULE_NONE;
+}
+// lookahead_pos and dict_size after the parser's step that token t, which starts at input position pos, closes: a literal's step looked at
+// pos (at pos + 1 when a match is held) and moved 1; a match taken at once looked at pos and moved len; a held match was found at pos, its
+// step looked at pos + 1 and moved len - 1. The step at q with lookahead la = min(258, n - q) starts from dict_size = min(q, 32768 - la).
+SP_HD void tok_step(uint32_t t, uint64_t pos, uint64_t n, uint64_t* lookahead_pos, uint32_t* dict_size) {
+  const unsigned len = tok_len(t);
+  uint64_t step, move;
+  if (!len) { step = pos + ((t & TOK_HELD) ? 1 : 0); move = 1; }
+  else if (len >= TAKE) { step = pos; move = len; }
+  else { step = pos + 1; move = len - 1; }
+  const uint64_t left = n - step, la = left < MAXM ? left : MAXM;
+  const uint64_t ds = (step < DICT - la ? step : DICT - la) + move;
+  *lookahead_pos = step + move;
+  *dict_size = (uint32_t)(ds < DICT ? ds : DICT);
+}
+// RFC 1951's symbols in tdefl's indexing: a length 3..258 -> symbol 257..285, a distance 1..32768 -> symbol 0..29, each with the number of
+// extra bits and their value
+SP_HD void len_symbol(unsigned len, unsigned* sym, unsigned* nextra, unsigned* extra) {
+  const unsigned l = len - MINM;
+  if (l < 8) { *sym = 257 + l; *nextra = 0; *extra = 0; return; }
+  if (len == MAXM) { *sym = 285; *nextra = 0; *extra = 0; return; }
+  const unsigned e = (31 - (unsigned)__builtin_clz(l)) - 2;
+  *sym = 257 + 4 * e + 4 + ((l >> e) & 3); *nextra = e; *extra = l & ((1u << e) - 1);
+}
+SP_HD void dist_symbol(unsigned dist, unsigned* sym, unsigned* nextra, unsigned* extra) {
+  const unsigned d = dist - 1;
+  if (d < 4) { *sym = d; *nextra = 0; *extra = 0; return; }
+  const unsigned e = (31 - (unsigned)__builtin_clz(d)) - 1;
+  *sym = 2 * (e + 1) + ((d >> e) & 1); *nextra = e; *extra = d & ((1u << e) - 1);
+}
+// A block's code tables as 320 words, code | size << 16: 288 of the literal/length alphabet, then 32 of the distances. The bits of a token
+// under them, first bit lowest, at most 48 (15 + 5 + 15 + 13); returns their number.
+constexpr unsigned TABLE_WORDS = 288 + 32;
+SP_HD unsigned tok_bits(uint32_t t, const uint32_t* table, uint64_t* bits) {
+  const unsigned len = tok_len(t);
+  if (!len) { const uint32_t w = table[t & 0xFF]; *bits = w & 0xFFFF; return w >> 16; }
+  unsigned s, ne, ev;
+  len_symbol(len, &s, &ne, &ev);
+  uint32_t w = table[s];
+  uint64_t v = w & 0xFFFF;
+  unsigned nb = w >> 16;
+  v |= (uint64_t)ev << nb; nb += ne;
+  dist_symbol(tok_dist(t), &s, &ne, &ev);
+  w = table[288 + s];
+  v |= (uint64_t)(w & 0xFFFF) << nb; nb += w >> 16;
+  v |= (uint64_t)ev << nb; nb += ne;
+  *bits = v;
+  return nb;
+}
+// the same token's length in bits from the code sizes alone
+SP_HD unsigned tok_nbits(uint32_t t, const uint32_t* table) {
+  const unsigned len = tok_len(t);
+  if (!len) return table[t & 0xFF] >> 16;
+  unsigned s, ne, ev, nb;
+  len_symbol(len, &s, &ne, &ev);
+  nb = (table[s] >> 16) + ne;
+  dist_symbol(tok_dist(t), &s, &ne, &ev);
+  return nb + (table[288 + s] >> 16) + ne;
+}
 }  // namespace tdefl

@@ -31,6 +31,13 @@
 //   MatchParser, zlib_from_matches             TableLookup -> walk -> Coder, segment by segment: what digest.cc runs behind the device search
 //   deflate_tokens_host                        TableLookup -> walk -> a token list: the host model of the device parse
 //   TokenCoder, zlib_from_tokens               a token list -> Coder: what digest.cc runs behind the device parse
+//   deflate_blocks_host                        a token list -> block records and histograms, from prefix sums of token costs: the host model
+//                                              of the device coder's block stage (csrc/deflate_emit.hip)
+//   BlockPlanner                               a block's record and histogram -> its tables, header, stored-or-coded decision and bit offset
+//                                              (optimize_table, start_dynamic_block, start_static_block of Tdefl, untouched): what digest.cc
+//                                              runs behind the device coder
+//   zlib_from_blocks                           records -> BlockPlanner -> every token's bits ORed in at its own offset: the host model of the
+//                                              device's emission
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -449,22 +456,18 @@ struct Coder {
   // inlined into its callers' loops by force: left as a call it costs the coder 5-10 % (bench/deflate_host_probe.cc, time 16)
   __attribute__((always_inline)) void token(uint32_t t) {
     const unsigned len = tdefl::tok_len(t);
-    size_t step, move;  // the parser's step this token closes: where it looked, how far it moved
-    if (!len) {
-      d.record_literal((uint8_t)t);
-      step = pos + ((t & TOK_HELD) ? 1 : 0); move = 1;
-      pos += 1;
-    } else {
-      d.record_match(len, tdefl::tok_dist(t));
-      if (len >= tdefl::TAKE) { step = pos; move = len; } else { step = pos + 1; move = len - 1; }  // taken at once | the held match of step - 1
-      pos += len;
-    }
+    const size_t at = pos;  // where the token starts
+    if (!len) d.record_literal((uint8_t)t); else d.record_match(len, tdefl::tok_dist(t));
+    pos += tdefl::tok_input_bytes(t);
     if (!(t & TOK_CHECK)) return;
-    const unsigned la = (unsigned)std::min<size_t>(tdefl::MAXM, n - step);
-    d.lookahead_pos = (unsigned)(step + move);
-    d.dict_size = (unsigned)std::min<size_t>(std::min<size_t>(step, tdefl::DICT - la) + move, tdefl::DICT);
-    if (d.code_bytes > LZBUF - 8) { full_blocks++; d.flush_block(false); }
-    else if (d.total_lz_bytes > 31 * 1024 && ((d.code_bytes * 115) >> 7) >= d.total_lz_bytes) { ratio_blocks++; d.flush_block(false); }
+    uint64_t lookahead_pos;
+    uint32_t dict_size;
+    tdefl::tok_step(t, at, n, &lookahead_pos, &dict_size);  // the parser's step this token closes
+    d.lookahead_pos = (unsigned)lookahead_pos;
+    d.dict_size = dict_size;
+    const tdefl::BlockRule rule = tdefl::block_check(d.code_bytes, d.total_lz_bytes);
+    if (rule == tdefl::RULE_FULL) { full_blocks++; d.flush_block(false); }
+    else if (rule == tdefl::RULE_RATIO) { ratio_blocks++; d.flush_block(false); }
   }
   std::vector<uint8_t> finish() {
     d.adler = (s2 << 16) | s1;
@@ -607,6 +610,196 @@ std::vector<uint8_t> zlib_from_tokens(const uint8_t* D, size_t n, const uint32_t
   if (!ntok) tc.code(D, n, tokens, 0);
   std::vector<uint8_t> z = tc.finish();
   if (blocks) { blocks[0] = tc.full_blocks; blocks[1] = tc.ratio_blocks; blocks[2] = tc.stored_blocks; blocks[3] = tc.static_blocks; }
+  return z;
+}
+
+// ---- the coder split as the device runs it (csrc/deflate_emit.hip): block records from prefix sums of token costs, then tables and bit
+// offsets per block from its histogram alone, then every token's bits as an independent item
+namespace {
+void or_bits(std::vector<uint8_t>& z, uint64_t off, uint64_t v, unsigned nb) {  // v's low nb bits at bit `off`, first bit lowest
+  for (unsigned done = 0; done < nb;) {
+    const unsigned sh = (unsigned)((off + done) & 7), take = std::min(8 - sh, nb - done);
+    z[(off + done) >> 3] |= (uint8_t)(((v >> done) & ((1u << take) - 1)) << sh);
+    done += take;
+  }
+}
+unsigned len_extra_bits(unsigned sym) { return sym < 265 || sym == 285 ? 0 : (sym - 261) / 4; }
+unsigned dist_extra_bits(unsigned sym) { return sym < 4 ? 0 : sym / 2 - 1; }
+}  // namespace
+
+size_t deflate_blocks_host(const uint32_t* tokens, size_t ntok, size_t n, size_t segment, uint64_t* records, uint16_t* hist, size_t cap,
+                           uint64_t counters[BLKC_COUNT]) {
+  uint64_t own[BLKC_COUNT];
+  uint64_t* C = counters ? counters : own;
+  memset(C, 0, sizeof own);
+  if (!segment) segment = n ? n : 1;
+  const size_t nseg = n ? (n + segment - 1) / segment : 1;
+  std::vector<uint32_t> list;          // the open block's tokens, then the segment's
+  std::vector<uint64_t> code, lz;      // inclusive sums of the list's code bytes and input bytes
+  uint64_t gtok = 0, pos0 = 0;         // list[0]'s index in the whole token list, and its input position
+  size_t nb = 0, next = 0, span = 1;
+  uint64_t tpos = 0;                   // where token `next` starts
+  for (size_t s = 0; s < nseg; s++) {
+    const bool last = s + 1 == nseg;
+    const uint64_t end_pos = last ? n : (uint64_t)(s + 1) * segment;
+    if (s && !list.empty()) { C[BLKC_SEAM_OPEN]++; span++; }
+    while (next < ntok && (tpos < end_pos || last)) { list.push_back(tokens[next]); tpos += tdefl::tok_input_bytes(tokens[next]); next++; }
+    const size_t m = list.size();
+    code.resize(m); lz.resize(m);
+    for (size_t i = 0; i < m; i++) {
+      code[i] = (i ? code[i - 1] : 0) + tdefl::tok_code_bytes(list[i]);
+      lz[i] = (i ? lz[i - 1] : 0) + tdefl::tok_input_bytes(list[i]);
+    }
+    size_t start = 0;
+    auto close = [&](size_t end, tdefl::BlockRule rule) {  // the block list[start, end)
+      if (nb >= cap) throw Error("deflate_blocks_host: more blocks than the caller's arrays hold");
+      const size_t k = end - start;
+      if (k > tdefl::BLOCK_TOKENS) throw Error("deflate_blocks_host: a block of more than 58249 tokens");
+      const uint64_t lz0 = start ? lz[start - 1] : 0, total = end ? lz[end - 1] - lz0 : 0;
+      uint64_t la = 0;
+      uint32_t ds = 0;
+      if (k) {
+        const uint64_t at = pos0 + lz[end - 1] - tdefl::tok_input_bytes(list[end - 1]);
+        tdefl::tok_step(list[end - 1], at, n, &la, &ds);
+        la = (uint32_t)(la - (pos0 + lz0));
+      }
+      uint64_t* r = records + BLOCK_REC * nb;
+      r[0] = gtok + start; r[1] = k; r[2] = total; r[3] = rule; r[4] = la; r[5] = ds;
+      uint16_t* h = hist + BLOCK_HIST * nb;
+      memset(h, 0, sizeof(uint16_t) * BLOCK_HIST);
+      for (size_t i = start; i < end; i++) {
+        const unsigned len = tdefl::tok_len(list[i]);
+        if (!len) { h[list[i] & 0xFF]++; continue; }
+        unsigned sym, ne, ev;
+        tdefl::len_symbol(len, &sym, &ne, &ev); h[sym]++;
+        tdefl::dist_symbol(tdefl::tok_dist(list[i]), &sym, &ne, &ev); h[288 + sym]++;
+      }
+      C[BLKC_MAX_TOKENS] = std::max<uint64_t>(C[BLKC_MAX_TOKENS], k);
+      C[BLKC_MAX_SPAN] = std::max<uint64_t>(C[BLKC_MAX_SPAN], span);
+      if (rule == tdefl::RULE_FULL) C[BLKC_FULL]++;
+      if (rule == tdefl::RULE_RATIO) C[BLKC_RATIO]++;
+      if (rule == tdefl::RULE_FINISH && !k) C[BLKC_EMPTY_FINAL]++;
+      if (rule != tdefl::RULE_FINISH && end == m && !last) C[BLKC_SEAM_AT_BOUNDARY]++;
+      nb++; span = 1; start = end;
+    };
+    for (;;) {  // the chain: from a block's start, the first TOK_CHECK token at which the check fires
+      const uint64_t c0 = start ? code[start - 1] : 0, l0 = start ? lz[start - 1] : 0;
+      size_t hit = m;
+      tdefl::BlockRule rule = tdefl::RULE_NONE;
+      for (size_t i = start; i < m && hit == m; i++)
+        if ((list[i] & TOK_CHECK) && (rule = tdefl::block_check(tdefl::code_bytes_after(code[i] - c0, i - start + 1), lz[i] - l0)) != tdefl::RULE_NONE) hit = i;
+      if (hit == m) break;
+      close(hit + 1, rule);
+    }
+    if (last) close(m, tdefl::RULE_FINISH);
+    gtok += start; pos0 += start ? lz[start - 1] : 0;
+    list.erase(list.begin(), list.begin() + start);
+  }
+  return nb;
+}
+
+struct BlockPlanner::Impl {
+  Tdefl d;
+};
+BlockPlanner::BlockPlanner(unsigned probes, bool old_header) : m(new Impl()) {
+  Tdefl& d = m->d;
+  memset(d.count, 0, sizeof d.count); memset(d.codes, 0, sizeof d.codes); memset(d.sizes, 0, sizeof d.sizes);
+  // the zlib header as flush_block writes it before the first block
+  static const unsigned num_probes[11] = {0, 1, 6, 32, 16, 32, 128, 256, 512, 768, 1500};
+  unsigned i = 0, flevel = 3;
+  for (; i < 11; i++) if (num_probes[i] == (probes & 0xFFF)) break;
+  if (i < 2) flevel = 0; else if (i < 6) flevel = 1; else if (i == 6) flevel = 2;
+  unsigned header = (0x78u << 8) | (flevel << 6);
+  header += 31 - (header % 31);
+  head[0] = 0x78; head[1] = old_header ? 0x01 : (uint8_t)(header & 0xFF);
+}
+BlockPlanner::~BlockPlanner() { delete m; }
+void BlockPlanner::plan(const uint64_t* rec, const uint16_t* hist, BlockPlan& p) {
+  Tdefl& d = m->d;
+  const bool finish = rec[3] == tdefl::RULE_FINISH;
+  const uint64_t total = rec[2];
+  d.out.clear(); d.bitbuf = 0; d.bits_in = 0;
+  for (int i = 0; i < 288; i++) d.count[0][i] = hist[i];
+  for (int i = 0; i < 32; i++) d.count[1][i] = hist[288 + i];
+  d.total_lz_bytes = (unsigned)total;
+  d.put(finish ? 1 : 0, 1);
+  const bool is_static = total < 48;
+  if (is_static) d.start_static_block(); else d.start_dynamic_block();
+  const uint32_t hdr_bits = (uint32_t)(8 * d.out.size() + d.bits_in);
+  uint64_t tokbits = 0;  // the coded length from the histogram alone
+  for (unsigned i = 0; i < 288; i++)
+    if (i != 256) tokbits += (uint64_t)hist[i] * (d.sizes[0][i] + len_extra_bits(i));
+  for (unsigned i = 0; i < 32; i++) tokbits += (uint64_t)hist[288 + i] * (d.sizes[1][i] + dist_extra_bits(i));
+  const uint64_t P0 = bitpos, end_coded = P0 + hdr_bits + tokbits + d.sizes[0][256];
+  // flush_block's test counts whole bytes written since the block's first bit went in: it depends on the bits pending before the block
+  const bool stored = total && (end_coded / 8 - (P0 + 1) / 8 + 1) >= total && rec[4] <= rec[5];
+  memset(p.hdr, 0, sizeof p.hdr);
+  p.bit_off = P0; p.src = src; p.total = total;
+  if (stored) {
+    const unsigned pad = (unsigned)((8 - (P0 + 3) % 8) % 8);
+    p.kind = BLOCK_STORED; p.hdr_bits = 3 + pad + 32;
+    std::vector<uint8_t> h(sizeof p.hdr, 0);
+    or_bits(h, 0, finish ? 1 : 0, 3);
+    or_bits(h, 3 + pad, total & 0xFFFF, 16);
+    or_bits(h, 3 + pad + 16, (total ^ 0xFFFF) & 0xFFFF, 16);
+    memcpy(p.hdr, h.data(), sizeof p.hdr);
+    p.tok_off = P0 + p.hdr_bits; p.eob_off = 0; p.end_off = p.tok_off + 8 * total;
+    memset(p.table, 0, sizeof p.table);
+    stored_blocks++;
+    if (P0 % 8) stored_after_midbyte++;
+  } else {
+    if ((hdr_bits + 7) / 8 > sizeof p.hdr) throw Error("BlockPlanner: a block header longer than its slot");
+    p.kind = is_static ? BLOCK_STATIC : BLOCK_DYNAMIC; p.hdr_bits = hdr_bits;
+    if (!d.out.empty()) memcpy(p.hdr, d.out.data(), d.out.size());  // a static block's three bits fill no byte
+    if (d.bits_in) p.hdr[d.out.size()] = (uint8_t)d.bitbuf;
+    p.tok_off = P0 + hdr_bits; p.eob_off = p.tok_off + tokbits; p.end_off = end_coded;
+    for (unsigned i = 0; i < 288; i++) p.table[i] = d.codes[0][i] | ((uint32_t)d.sizes[0][i] << 16);
+    for (unsigned i = 0; i < 32; i++) p.table[288 + i] = d.codes[1][i] | ((uint32_t)d.sizes[1][i] << 16);
+    if (is_static) static_blocks++;
+  }
+  bitpos = p.end_off; src += total; blocks++;
+}
+void BlockPlanner::finish(std::vector<uint8_t>& z, uint32_t adler) const {
+  z.resize(stream_bytes(), 0);
+  z[0] |= head[0]; z[1] |= head[1];
+  for (int i = 0; i < 4; i++) z[z.size() - 4 + i] = (uint8_t)(adler >> (24 - 8 * i));
+}
+
+std::vector<uint8_t> zlib_from_blocks(const uint64_t* records, const uint16_t* hist, size_t nblocks, const uint32_t* tokens, const uint8_t* D, size_t n,
+                                      unsigned probes, bool old_header, uint64_t stats[3]) {
+  BlockPlanner bp(probes, old_header);
+  std::vector<BlockPlan> plans(nblocks);
+  for (size_t b = 0; b < nblocks; b++) bp.plan(records + BLOCK_REC * b, hist + BLOCK_HIST * b, plans[b]);  // tables, lengths, decisions, offsets: block by block
+  std::vector<uint8_t> z(bp.stream_bytes(), 0);
+  std::vector<uint32_t> off;
+  for (size_t b = 0; b < nblocks; b++) {  // the bits: every header, token and byte an item of its own, ORed in at its offset
+    const BlockPlan& p = plans[b];
+    const uint64_t* r = records + BLOCK_REC * b;
+    for (unsigned i = 0; 8 * i < p.hdr_bits; i++) or_bits(z, p.bit_off + 8 * i, p.hdr[i], std::min(8u, p.hdr_bits - 8 * i));
+    if (p.kind == BLOCK_STORED) {
+      if (p.src + p.total > n) throw Error("zlib_from_blocks: a stored block past the input's end");
+      memcpy(z.data() + p.tok_off / 8, D + p.src, p.total);
+      continue;
+    }
+    const uint32_t* t = tokens + r[0];
+    off.assign(r[1] + 1, 0);
+    for (size_t i = 0; i < r[1]; i++) off[i + 1] = off[i] + tdefl::tok_nbits(t[i], p.table);  // the exclusive scan of the lengths
+    if (p.tok_off + off[r[1]] != p.eob_off) throw Error("zlib_from_blocks: the tokens' bits differ from the histogram's");
+    for (size_t i = 0; i < r[1]; i++) {
+      uint64_t v;
+      const unsigned nbits = tdefl::tok_bits(t[i], p.table, &v);
+      or_bits(z, p.tok_off + off[i], v, nbits);
+    }
+    or_bits(z, p.eob_off, p.table[256] & 0xFFFF, p.table[256] >> 16);
+  }
+  uint32_t s1 = 1, s2 = 0;
+  for (size_t i = 0; i < n;) {
+    const size_t blk = std::min<size_t>(5552, n - i);
+    for (size_t k = 0; k < blk; k++) { s1 += D[i + k]; s2 += s1; }
+    s1 %= 65521; s2 %= 65521; i += blk;
+  }
+  bp.finish(z, (s2 << 16) | s1);
+  if (stats) { stats[0] = bp.stored_blocks; stats[1] = bp.static_blocks; stats[2] = bp.stored_after_midbyte; }
   return z;
 }
 

@@ -529,10 +529,12 @@ void spz_instance_digest_stats(void* inst, double stats[12]) { stats_out(((Insta
 namespace {
 void stats_out_all(const DeflateStats& s, double* o, size_t cap) {
   if (!o) return;
-  double v[17];
+  double v[26];
   stats_out(s, v);
   v[12] = s.parse; v[13] = s.tokens; v[14] = s.device_fallbacks; v[15] = s.ms_reach; v[16] = s.ms_emit;
-  memcpy(o, v, sizeof(double) * std::min<size_t>(cap, 17));
+  v[17] = s.emit; v[18] = s.tokens_coded; v[19] = s.blocks; v[20] = s.stored_blocks; v[21] = s.static_blocks; v[22] = s.ms_blocks; v[23] = s.ms_bits;
+  v[24] = s.ms_tables; v[25] = s.ms_bytes;
+  memcpy(o, v, sizeof(double) * std::min<size_t>(cap, 26));
 }
 }  // namespace
 size_t spz_deflate_tokens_host(const uint8_t* data, size_t n, unsigned probes, const size_t* geom, uint32_t* tokens, uint64_t* counters) {
@@ -551,6 +553,24 @@ size_t spz_zlib_device_parse(void* ctx, const uint8_t* data, size_t n, unsigned 
     stats_out_all(s, stats, stats_cap);
     return bytes_out(z, out, cap);
   });
+}
+size_t spz_zlib_device_emit(void* ctx, const uint8_t* data, size_t n, unsigned probes, int old_header, int parse, size_t tile, size_t group, size_t chunk,
+                            uint8_t* out, size_t cap, double* stats, size_t stats_cap) {
+  return guard((size_t)0, [&] {
+    if (!ctx || (n && !data) || probes == 0 || probes > 0xFFF || parse < -1 || parse > 2) throw bad_arguments("spz_zlib_device_emit");
+    DeflateStats s;
+    const std::vector<uint8_t> z = zlib_device(((Ctx*)ctx)->h, data, nullptr, n, probes, old_header != 0, &s, parse, tile, group, chunk);
+    stats_out_all(s, stats, stats_cap);
+    return bytes_out(z, out, cap);
+  });
+}
+long long spz_deflate_blocks_host(const uint32_t* tokens, size_t ntok, size_t n, size_t segment, uint64_t* records, uint16_t* hist, size_t cap,
+                                  uint64_t* counters) {
+  return guard((long long)-1, [&] { return (long long)deflate_blocks_host(tokens, ntok, n, segment, records, hist, cap, counters); });
+}
+size_t spz_zlib_from_blocks(const uint64_t* records, const uint16_t* hist, size_t nblocks, const uint32_t* tokens, const uint8_t* data, size_t n,
+                            unsigned probes, int old_header, uint8_t* out, size_t cap, uint64_t* stats) {
+  return guard((size_t)0, [&] { return bytes_out(zlib_from_blocks(records, hist, nblocks, tokens, data, n, probes, old_header != 0, stats), out, cap); });
 }
 void spz_instance_digest_stats_all(void* inst, double* stats, size_t stats_cap) { stats_out_all(((Instance*)inst)->digest_stats, stats, stats_cap); }
 const char* spz_keccak_variant() { return keccak_f1600_variant(); }

@@ -187,6 +187,11 @@ struct DeflateStats {
   // device time of the reachability kernels (jumps, exits, composition, entries, marks) and of the token kernel with its compaction.
   // ms_parse is then the token coder alone, ms_download the copies of tokens and bytes, lookups / fallbacks stay 0 (nothing is looked up here)
   double parse = 0, tokens = 0, device_fallbacks = 0, ms_reach = 0, ms_emit = 0;
+  // the device coder (digest.device = 3): 1 when it ran; then `tokens` stays 0 (none is handed over) and tokens_coded counts them from the
+  // block records; blocks, stored and static blocks among them; device time of the block stage (costs, scan, boundaries, histograms,
+  // Adler-32, the records' copy) and of the bit emission; host time of the table building (within ms_parse) and of the one download of the
+  // compressed bytes
+  double emit = 0, tokens_coded = 0, blocks = 0, stored_blocks = 0, static_blocks = 0, ms_blocks = 0, ms_bits = 0, ms_tables = 0, ms_bytes = 0;
 };
 
 // ---- instance ----
@@ -207,7 +212,8 @@ struct Instance {  // src/lib.rs:110-273 (R1CSInstance after padding) with the m
   // real C miniz 3.0.2 on the test corpus); a caller that holds the bytes of a real libspartan Instance may set them instead
   // (set_digest). With the option digest.device = 1 (the default) the stream is serialised and the deflater's match search runs on the
   // device, and only its parser and Huffman coding run here (digest.cc; the same bytes; digest.device = 2: the lazy parse on the device
-  // too, only the token coder here — 13 % faster at 2^20, not at 2^16: profiles/instance_digest_parse.txt). The computation is guarded: concurrent
+  // too, only the token coder here — 13 % faster at 2^20, not at 2^16: profiles/instance_digest_parse.txt; digest.device = 3: the coder on
+  // the device too, only the Huffman tables and bit offsets here — 3.2x faster at both: profiles/instance_digest_emit.txt). The computation is guarded: concurrent
   // NIZK::prove calls over one Instance compute it once; a caller that wants the deflate of a large shape (4.5 s at 2^20 with 9.4 M
   // entries, 19.9 s on the host alone: profiles/instance_digest.txt) out of its first prove calls compute_digest() right after
   // construction, as the reference's Instance::new does (lib.rs:228).
@@ -370,11 +376,62 @@ struct TokenCoder {
 // blocks (may be nullptr) = blocks ended by the code-buffer rule, by the 115/128 rule, stored blocks, static blocks
 std::vector<uint8_t> zlib_from_tokens(const uint8_t* data, size_t n, const uint32_t* tokens, size_t ntok, unsigned probes, bool old_header,
                                       size_t piece = 0, uint64_t blocks[4] = nullptr);
+// The coder split as the device runs it (csrc/deflate_emit.hip; the rules: csrc/tdefl_rules.hpp). A block record is BLOCK_REC 64-bit words —
+// the index of the block's first token in the whole list, its tokens, its input bytes (total_lz_bytes), the rule that closed it
+// (tdefl::BlockRule: 1 code buffer, 2 ratio, 3 finish), and the two numbers of flush_block's stored test, lookahead_pos - lz_dict_pos and
+// dict_size after the block's last token (0, 0 for an empty block) — with BLOCK_HIST 16-bit counters beside it: 288 of the literal/length
+// alphabet (the end-of-block symbol not counted), then 32 of the distances.
+constexpr size_t BLOCK_REC = 6, BLOCK_HIST = 320, BLOCK_HDR_BYTES = 320;
+// what deflate_blocks_host counts: conditions on an input and a segment length that the tests ask for
+enum BlockCounter { BLKC_FULL, BLKC_RATIO, BLKC_EMPTY_FINAL, BLKC_SEAM_OPEN, BLKC_MAX_SPAN, BLKC_SEAM_AT_BOUNDARY, BLKC_MAX_TOKENS, BLKC_COUNT };
+// The block records of a token list of n input bytes, found as the device finds them: segment by segment (tokens that start below a
+// multiple of `segment`; 0: one segment), over the open block's carried tokens followed by the segment's, from inclusive sums of the token
+// costs, by a chain of first-hit searches. records / hist hold `cap` blocks; returns their number (the last one is the finish block, which
+// may be empty). counters (may be nullptr): blocks closed by the code-buffer rule, by the ratio rule, empty final blocks, seams an open
+// block was carried over, the most segments one block touched, blocks whose last token was a segment's last, the most tokens of a block.
+// Throws Error for a block of more than 58249 tokens.
+size_t deflate_blocks_host(const uint32_t* tokens, size_t ntok, size_t n, size_t segment, uint64_t* records, uint16_t* hist, size_t cap,
+                           uint64_t counters[BLKC_COUNT]);
+enum BlockKind : uint32_t { BLOCK_DYNAMIC = 0, BLOCK_STATIC = 1, BLOCK_STORED = 2 };
+// What the host decides about one block, from its record and histogram alone: where its bits go and what they are made of.
+struct BlockPlan {
+  uint64_t bit_off = 0;   // of the block's first bit (the final-block flag) in the stream
+  uint64_t tok_off = 0;   // of its first token's bits; a stored block: of its first data byte (a multiple of 8)
+  uint64_t eob_off = 0;   // of its end-of-block symbol (coded blocks)
+  uint64_t end_off = 0;   // one past its last bit
+  uint64_t src = 0, total = 0;  // the input bytes it stands for: D[src, src + total)
+  uint32_t kind = 0, hdr_bits = 0;
+  uint32_t table[BLOCK_HIST];   // code | size << 16 (tdefl::tok_bits); zeros for a stored block
+  uint8_t hdr[BLOCK_HDR_BYTES]; // the bits from bit_off up to tok_off, first bit lowest: flag, type, and the dynamic header or LEN / NLEN
+};
+// Blocks in stream order: the unchanged optimize_table / start_dynamic_block / start_static_block for the tables and the header, the coded
+// length from the histogram, flush_block's stored-or-coded test with the bit position carried from block to block, the offsets.
+struct BlockPlanner {
+  BlockPlanner(unsigned probes, bool old_header);
+  ~BlockPlanner();
+  BlockPlanner(const BlockPlanner&) = delete;
+  void plan(const uint64_t* record, const uint16_t* hist, BlockPlan& p);
+  size_t stream_bytes() const { return (size_t)((bitpos + 7) / 8) + 4; }  // after the finish block: the stream with its Adler-32 trailer
+  void finish(std::vector<uint8_t>& z, uint32_t adler) const;            // z: the blocks' bits; sized, the zlib header and the trailer put in
+  uint8_t head[2];
+  uint64_t bitpos = 16, src = 0;
+  uint64_t blocks = 0, stored_blocks = 0, static_blocks = 0, stored_after_midbyte = 0;
+
+ private:
+  struct Impl;
+  Impl* m;
+};
+// the stream from block records: equals zlib_miniz_probes(data, n, probes, old_header) byte for byte. stats (may be nullptr; 3) = stored
+// blocks, static blocks, stored blocks that follow a block ending within a byte
+std::vector<uint8_t> zlib_from_blocks(const uint64_t* records, const uint16_t* hist, size_t nblocks, const uint32_t* tokens, const uint8_t* data, size_t n,
+                                      unsigned probes, bool old_header, uint64_t stats[3]);
 // zlib stream of n bytes at `data` (host memory) or `dev_data` (memory of the context's device), the matches searched on the device.
-// parse: 0 = MatchParser over the downloaded tables, 1 = the parse on the device too and TokenCoder behind it, -1 = as digest.device says
-// (2: the device parse); tile, group: positions a tile and tiles a group of the device parse (0: the library's defaults)
+// parse: 0 = MatchParser over the downloaded tables, 1 = the parse on the device too and TokenCoder behind it, 2 = the coder's block
+// boundaries, histograms and bit emission on the device as well and BlockPlanner behind it, -1 = as digest.device says (2: the device
+// parse, 3: the device coder); tile, group: positions a tile and tiles a group of the device parse, chunk: tokens a workgroup of the
+// emission (0: the library's defaults)
 std::vector<uint8_t> zlib_device(sp_ctx* c, const uint8_t* data, const uint8_t* dev_data, size_t n, unsigned probes, bool old_header, DeflateStats* st,
-                                 int parse = -1, size_t tile = 0, size_t group = 0);
+                                 int parse = -1, size_t tile = 0, size_t group = 0, size_t chunk = 0);
 // per-entry-point wall time of the option host.callstats (prover.cc), for driver files that cannot use its macro
 void callstats_add(const char* entry, double seconds);
 

@@ -66,6 +66,9 @@ SIGNATURES = {
     "spz_zlib_from_tokens": (sz, [vp, sz, vp, sz, ctypes.c_uint, _i, sz] + _BYTES + [vp]),
     "spz_zlib_device_parse": (sz, [vp, vp, sz, ctypes.c_uint, _i, _i, sz, sz] + _BYTES + [vp, sz]),
     "spz_instance_digest_stats_all": (None, [vp, vp, sz]),
+    "spz_deflate_blocks_host": (_ll, [vp, sz, sz, sz, vp, vp, sz, vp]),
+    "spz_zlib_from_blocks": (sz, [vp, vp, sz, vp, vp, sz, ctypes.c_uint, _i] + _BYTES + [vp]),
+    "spz_zlib_device_emit": (sz, [vp, vp, sz, ctypes.c_uint, _i, _i, sz, sz, sz] + _BYTES + [vp, sz]),
     "spz_keccak_run_variant": (_i, [_s, vp]), "spz_shake256": (None, [vp, sz, vp, sz]),
     "spz_merlin_script": (sz, _SCRIPT), "spz_merlin_state": (None, _SCRIPT), "spz_merlin_challenge_from_state": (None, [vp, _s, vp, sz]),
     "spz_tape_draws": (None, [vp, _s, sz, vp]), "spz_seed_scalar": (None, [_s, _u64, vp]),
@@ -369,22 +372,27 @@ def keccak_variant():
 
 
 DEFLATE_STATS = ("lookups", "fallbacks", "segments", "ms_links", "ms_search_a", "ms_search_b", "ms_download", "ms_parse", "ms_wait", "ms_stream",
-                 "ms_total", "device", "parse", "tokens", "device_fallbacks", "ms_reach", "ms_emit")
+                 "ms_total", "device", "parse", "tokens", "device_fallbacks", "ms_reach", "ms_emit",
+                 "emit", "tokens_coded", "blocks", "stored_blocks", "static_blocks", "ms_blocks", "ms_bits", "ms_tables", "ms_bytes")
 
 
-def zlib_device(ctx, data, probes=128, old_header=False, parse=0, tile=0, group=0):
+def zlib_device(ctx, data, probes=128, old_header=False, parse=0, tile=0, group=0, chunk=0):
     """(zlib stream of `data` as miniz writes it at this tdefl probe count, stats): the device-assisted deflate the instance digest runs over
     bincode(shape) — match search on the GPU in segments of the option digest.segment, parser and Huffman coding on the calling thread; with
     parse = 1 the lazy parse on the GPU too (tiles of `tile` positions, groups of `group` tiles; 0: the defaults) and only the token coder on
     the calling thread; parse = None: as the option digest.device says (2 = the device parse), which is what Instance.digest() follows.
     stats: lookups and those neither match table answered, segments, device ms of links / search A / search B / downloads, host ms of parse /
     wait / stream / total; parse = 1.0 when the device parsed, its tokens, the look-ups it searched on the spot, device ms of the reachability
-    kernels and of the token kernel with its compaction (ms_parse is then the token coder alone)."""
+    kernels and of the token kernel with its compaction (ms_parse is then the token coder alone). parse = 2 (digest.device = 3): the coder's
+    block boundaries, histograms, bit emission (`chunk` tokens a workgroup; 0: the default), stored-block copies and Adler-32 on the GPU as
+    well, the calling thread builds each block's Huffman tables and bit offsets from its histogram: emit = 1.0, tokens stays 0 (none comes
+    down) and tokens_coded counts them, blocks / stored_blocks / static_blocks, device ms of the block stage and of the bit emission, host ms
+    of the table building (within ms_parse) and of the download of the compressed bytes."""
     data = bytes(data)
     cap = 2 * len(data) + 1024
     out = (ctypes.c_uint8 * cap)(); st = (ctypes.c_double * len(DEFLATE_STATS))()
-    n = H.spz_zlib_device_parse(ctx.h, data, sz(len(data)), ctypes.c_uint(probes), 1 if old_header else 0, -1 if parse is None else int(parse),
-                                sz(tile), sz(group), out, sz(cap), st, sz(len(DEFLATE_STATS)))
+    n = H.spz_zlib_device_emit(ctx.h, data, sz(len(data)), ctypes.c_uint(probes), 1 if old_header else 0, -1 if parse is None else int(parse),
+                               sz(tile), sz(group), sz(chunk), out, sz(cap), st, sz(len(DEFLATE_STATS)))
     if n == 0:
         raise SpartanHipError(_failed("zlib_device"))
     return bytes(out[:n]), dict(zip(DEFLATE_STATS, st))
@@ -402,6 +410,21 @@ def deflate_tokens(ctx, data, probes=128, tile=0, group=0):
     if rc != 0:
         raise SpartanHipError("sp_deflate_tokens failed: %d" % rc)
     return tok, ntok.value, info[0], info[1]
+
+
+def deflate_blocks(ctx, data, probes=128, tile=0, group=0):
+    """test hook: (block records, histograms, their number) of `data` as the device finds them (sp_deflate_blocks): 6 64-bit words and 320
+    16-bit counters a block, laid out as spz_deflate_blocks_host's (include/spartan_host.h)."""
+    from .capi import lib
+    data = bytes(data)
+    n = len(data)
+    cap = n // 11306 + 4     # a block that is not the last holds more than 11306 tokens (include/spartan_hip.h)
+    rec = (ctypes.c_uint64 * (6 * cap))(); hist = (ctypes.c_uint16 * (320 * cap))(); nb = ctypes.c_size_t(0)
+    buf = (ctypes.c_uint8 * max(1, n)).from_buffer_copy(data) if n else (ctypes.c_uint8 * 1)()
+    rc = lib.sp_deflate_blocks(ctx.raw(), buf, sz(n), ctypes.c_int(0), ctypes.c_uint32(probes), sz(tile), sz(group), rec, hist, sz(cap), ctypes.byref(nb))
+    if rc != 0:
+        raise SpartanHipError("sp_deflate_blocks failed: %d" % rc)
+    return rec, hist, nb.value
 
 
 def seed_scalar(domain, seed):
