@@ -1,4 +1,7 @@
 // spartan_amd: row commitments: the latency-path kernels, reductions and encoders, the launch plan, and the sp_commit_rows* / sp_job_wait entry points.
+// Host side: msm_plan decides every form (throughput form, the latency path's tree form, nblk, encode route), msm_launch dispatches on it;
+// msm_enqueue_commit: the many-row enqueue, msm_tree1_enqueue: the one-block tree, msm_finish_few: the few-row ending; commit_args_ok, stage_blinds
+// and stage_indexed serve the entry points.
 #include "internal.hpp"
 #include "tree.hpp"
 #include <atomic>
@@ -265,7 +268,7 @@ __global__ void __launch_bounds__(256) k_ipa_round(IpaRoundArgs A, const Niels* 
   }
   signal_done(sig);
 }
-// unified: the tree with the complete addition formula (the re-run of a round whose row sum came back with Z = 0; SPARTAN_IPA_UNIFIED_TREE=1 selects it
+// unified: the tree with the complete addition formula (the re-run of a round whose row sum came back with Z = 0; ipa.unified_tree = 1 selects it
 // for every round: the A/B switch)
 int32_t ipa_round_launch(sp_ctx* c, const sp_gens* g, IpaRoundArgs* A, DoneSig* sig_out, int unified) {
   const size_t P = (A->n0 / 2) * (size_t)g->geom.nwin;
@@ -376,7 +379,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
   pt_encode_rows(in, rows, out);
 }
 
+// (The kernels above keep their repeated text on purpose: with the lookup, the tree kernels' front, the strided sum or the last-ticket tail as
+// __forceinline__ helpers, every kernel that used one came out with another register allocation or instruction count: not the measured kernels.)
 // MSM launch plan: kernel shapes and scratch sizes for a (rows x cols) fixed-base commit
+// (the latency path's tree forms: one workgroup per row, its sum final | more, the last of a row adds them | more, k_msm_reduce adds them)
+enum { MSM_TREE_NONE = 0, MSM_TREE1, MSM_TREE_FUSED, MSM_TREE_UNFUSED };
 struct MsmPlan {
   bool windowed, two_pass;
   bool lds = false;  // the LDS-staged small-window form (msm_lds.hip), P = runs per row-block
@@ -385,6 +392,11 @@ struct MsmPlan {
   int qrole = MSMQ_ALONE;
   int flat;  // 0: strip form; 2: balanced form (k_msm_flat), P = runs per row
   size_t strip, nstrips, P, chunk, nchunks, part_bytes, part2_bytes;
+  // msm_launch's latency path (few; a job reads none of this): its tree form (none: the sums above + k_msm_reduce), the tree's workgroups per row,
+  // and whether k_pt_encode runs the encode chain (encode.device) instead of the host core
+  bool few = false, encode_dev = false;
+  int tree = MSM_TREE_NONE;
+  size_t nblk = 0;
 };
 // (c: the LAUNCHING context — options, CU count and background share are its own; a virtual shard launches its parent's generator set)
 static MsmPlan msm_plan(const sp_ctx* c, const sp_gens* g, size_t rows, size_t cols, bool has_blinds, size_t bg_subblocks = 0 /* background launch: 256-thread tiles it runs at once */,
@@ -446,6 +458,19 @@ static MsmPlan msm_plan(const sp_ctx* c, const sp_gens* g, size_t rows, size_t c
   m.two_pass = m.P > 2048;
   m.part_bytes = (rows * m.P * sizeof(Pt) + 255) & ~(size_t)255;
   m.part2_bytes = m.two_pass ? ((rows * m.nchunks * sizeof(Pt10) + 255) & ~(size_t)255) : 0;
+  if (rows <= SP_HOST_ENCODE_ROWS) {  // latency path: the device sums, the host core runs the encode chain
+    // (encode.device: the sums stay in device memory and k_pt_encode runs the chain there — same bytes, ~100 us later)
+    m.few = true;
+    m.encode_dev = c->device_encode;
+    if (m.windowed) {
+      size_t nblk = (m.P + 255) / 256;  // nblk * rows * 160 B of partial sums <= part_bytes
+      m.nblk = nblk;
+      m.tree = nblk == 1 ? MSM_TREE1 : MSM_TREE_UNFUSED;
+      if (nblk > 1 && !c->device_encode && c->done_counter) {
+        m.tree = MSM_TREE_FUSED;  // one launch, its flag waited for
+      }
+    }
+  }
   return m;
 }
 // scratch of one commit: [partials: part_bytes][second-pass partials: part2_bytes][32 B x rows encodings, padded to 256][row sums as points]
@@ -515,6 +540,37 @@ static void msm_enqueue_reduce(sp_ctx* c, hipStream_t st, const MsmPlan& m, size
       hipLaunchKernelGGL(k_pt_encode, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, (const Pt*)sums, rows, dout);
   }
 }
+// one many-row commit on `st`: the sums, then the reduction with the batch encode, in `scratch` (layout lay); the encodings go to dout
+static void msm_enqueue_commit(sp_ctx* c, hipStream_t st, const MsmPlan& m, const MsmScratch& lay, const sp_gens* g, const Fq* dZ, size_t z_stride, size_t rows,
+                               size_t cols, size_t g_off, const uint32_t* didx, const Fq* dblinds, size_t h_idx, uint8_t* scratch, uint8_t* dout) {
+  const unsigned* qcounts = msm_enqueue_sums(c, st, m, g, dZ, z_stride, rows, cols, g_off, didx, dblinds, h_idx, scratch);
+  msm_enqueue_reduce(c, st, m, rows, scratch, dout, true, scratch + lay.sums_off, qcounts);
+}
+// the one-block tree on `st`: the sum of each row (at most 256 (column, window) pairs) as a point at sums_out. The caller holds the profile scope
+static void msm_tree1_enqueue(hipStream_t st, const sp_gens* g, const Fq* dZ, size_t z_stride, size_t rows, size_t cols, size_t g_off, const uint32_t* didx,
+                              size_t idx_row_stride, const Fq* dblinds, size_t h_idx, uint8_t* sums_out) {
+  hipLaunchKernelGGL((k_msm_windows_tree<true>), dim3(1, (unsigned)rows), dim3(256), 0, st, dZ, z_stride, cols, (const Niels*)g->table, g_off, didx, idx_row_stride,
+                     dblinds, h_idx, (void*)sums_out, g->geom);
+}
+// the ending of a few-row commit: the row sums lie at `sums` (the host-mapped page; device memory when the plan encodes on the device) and go out as
+// points, as host-core encodings or through k_pt_encode. waited: the launch that wrote them has already been waited for (the fused tree's flag)
+static int32_t msm_finish_few(sp_ctx* c, const MsmPlan& m, size_t rows, const uint8_t* sums, bool waited, uint8_t* out_host, Pt* points_out) {
+  if (m.encode_dev) {
+    {
+      ProfScope ps(c, PF_MSM_REDUCE, 160.0 * (double)rows);
+      hipLaunchKernelGGL(k_pt_encode, dim3(1), dim3(64), 0, c->stream, (const Pt*)sums, rows, hres(c));
+    }
+    SPCHK(fetch_small(c, out_host, 32 * rows));
+    return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
+  }
+  if (!waited) SPCHK(sync_spin(c));
+  if (hipGetLastError() != hipSuccess) return SP_EHIP;
+  Pt pts[SP_HOST_ENCODE_ROWS];  // out of the host-mapped page first: the encodes read each coordinate several times
+  memcpy(pts, sums, sizeof(Pt) * rows);
+  if (points_out) memcpy(points_out, pts, sizeof(Pt) * rows);
+  else pt_compress_many(pts, rows, out_host);
+  return SP_OK;
+}
 // core: Z on device (row stride in elements), optional idx (device), optional blinds (device); synchronous
 int32_t msm_launch(sp_ctx* c, const sp_gens* g, const Fq* dZ, size_t z_stride, size_t rows, size_t cols, size_t g_off,
                    const uint32_t* didx, const Fq* dblinds, size_t h_idx, uint8_t* out_host, size_t idx_row_stride, Pt* points_out) {
@@ -523,76 +579,56 @@ int32_t msm_launch(sp_ctx* c, const sp_gens* g, const Fq* dZ, size_t z_stride, s
   MsmPlan m = msm_plan(c, g, rows, cols, dblinds != nullptr, 0, 0, c->bg_inflight > 0);
   const MsmScratch lay = msm_scratch(m, rows);
   SPCHK(ensure(&c->scratch, &c->scratch_cap, lay.bytes));
-  if (rows <= SP_HOST_ENCODE_ROWS) {  // latency path: the device sums, the host core runs the encode chain
-    // (SPARTAN_DEVICE_ENCODE: the sums stay in device memory and k_pt_encode runs the chain there — same bytes, ~100 us later)
-    uint8_t* sums_dst = c->device_encode ? (uint8_t*)c->scratch + lay.sums_off : hres(c);
-    if (m.windowed) {
-      size_t nblk = (m.P + 255) / 256;
-      Pt10* part = (Pt10*)c->scratch;  // nblk * rows * 160 B <= part_bytes
-      if (nblk > 1 && !c->device_encode && c->done_counter) {
-        DoneSig sig = sig_make(c, nblk * rows);
-        {
-          ProfScope ps(c, PF_MSM_WINDOWS, 32.0 * (double)(rows * cols) + 160.0 * (double)(rows * nblk));
-          hipLaunchKernelGGL(k_msm_windows_tree_fused, dim3((unsigned)nblk, (unsigned)rows), dim3(256), 0, c->stream, dZ, z_stride, cols, (const Niels*)g->table, g_off,
-                             didx, idx_row_stride, dblinds, h_idx, part, c->done_counter + 4, (Pt*)hres(c), g->geom, sig);
-        }
-        SPCHK(sig_wait(c, sig));
-        if (hipGetLastError() != hipSuccess) return SP_EHIP;
-        Pt sums[SP_HOST_ENCODE_ROWS];  // out of the host-mapped page first: the encodes read each coordinate several times
-        memcpy(sums, hres(c), sizeof(Pt) * rows);
-        if (points_out) memcpy(points_out, sums, sizeof(Pt) * rows);
-        else pt_compress_many(sums, rows, out_host);
-        return SP_OK;
-      }
-      {
-        ProfScope ps(c, PF_MSM_WINDOWS, 32.0 * (double)(rows * cols) + 160.0 * (double)(rows * nblk));
-        if (nblk == 1)
-          hipLaunchKernelGGL((k_msm_windows_tree<true>), dim3(1, (unsigned)rows), dim3(256), 0, c->stream, dZ, z_stride, cols, (const Niels*)g->table,
-                             g_off, didx, idx_row_stride, dblinds, h_idx, (void*)sums_dst, g->geom);
-        else
-          hipLaunchKernelGGL((k_msm_windows_tree<false>), dim3((unsigned)nblk, (unsigned)rows), dim3(256), 0, c->stream, dZ, z_stride, cols,
-                             (const Niels*)g->table, g_off, didx, idx_row_stride, dblinds, h_idx, (void*)part, g->geom);
-      }
-      if (nblk > 1) {
-        ProfScope ps(c, PF_MSM_REDUCE, 160.0 * (double)(rows * nblk) + 128.0 * (double)rows);
-        hipLaunchKernelGGL((k_msm_reduce<true, false>), dim3((unsigned)rows), dim3(256), 0, c->stream, (const void*)part, nblk, sums_dst, (const unsigned*)nullptr);
-      }
-    } else {
-      if (idx_row_stride) {  // per-row index lists exist on the lookup+tree path only: longer rows go out one at a time, each with its own list
-        for (size_t r = 0; r < rows; r++)  // (an inner-product round of more than 2^19 lookups that is not fusable: n0 = 32768, or 16384 at narrow windows)
-          SPCHK(msm_launch(c, g, dZ + r * z_stride, z_stride, 1, cols, g_off, didx + r * idx_row_stride, dblinds ? dblinds + r : nullptr, h_idx,
-                           out_host ? out_host + 32 * r : nullptr, 0, points_out ? points_out + r : nullptr));
-        return SP_OK;
-      }
-      const unsigned* qcounts = msm_enqueue_sums(c, c->stream, m, g, dZ, z_stride, rows, cols, g_off, didx, dblinds, h_idx, (uint8_t*)c->scratch);
-      msm_enqueue_reduce(c, c->stream, m, rows, (uint8_t*)c->scratch, sums_dst, false, nullptr, qcounts);
-    }
-    if (c->device_encode) {
-      {
-        ProfScope ps(c, PF_MSM_REDUCE, 160.0 * (double)rows);
-        hipLaunchKernelGGL(k_pt_encode, dim3(1), dim3(64), 0, c->stream, (const Pt*)sums_dst, rows, hres(c));
-      }
-      SPCHK(fetch_small(c, out_host, 32 * rows));
-      return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
-    }
-    Pt sums[SP_HOST_ENCODE_ROWS];
-    SPCHK(fetch_small(c, sums, sizeof(Pt) * rows));
-    if (hipGetLastError() != hipSuccess) return SP_EHIP;
-    if (points_out) memcpy(points_out, sums, sizeof(Pt) * rows);
-    else pt_compress_many(sums, rows, out_host);
-    return SP_OK;
+  uint8_t* const scratch = (uint8_t*)c->scratch;
+  if (!m.few) {
+    bool small_out = 32 * rows <= HMAP_SIZE - HMAP_IN;
+    uint8_t* dout = small_out ? hres(c) : scratch + lay.out_off;
+    msm_enqueue_commit(c, c->stream, m, lay, g, dZ, z_stride, rows, cols, g_off, didx, dblinds, h_idx, scratch, dout);
+    if (small_out) SPCHK(fetch_small(c, out_host, 32 * rows));
+    else SPCHK(fetch_out(c, dout, out_host, 32 * rows));
+    return hipGetLastError() == hipSuccess ? SP_OK : SP_EHIP;
   }
-  bool small_out = 32 * rows <= HMAP_SIZE - HMAP_IN;
-  uint8_t* dout = small_out ? hres(c) : (uint8_t*)c->scratch + lay.out_off;
-  const unsigned* qcounts = msm_enqueue_sums(c, c->stream, m, g, dZ, z_stride, rows, cols, g_off, didx, dblinds, h_idx, (uint8_t*)c->scratch);
-  msm_enqueue_reduce(c, c->stream, m, rows, (uint8_t*)c->scratch, dout, true, (uint8_t*)c->scratch + lay.sums_off, qcounts);
-  if (small_out) SPCHK(fetch_small(c, out_host, 32 * rows));
-  else SPCHK(fetch_out(c, dout, out_host, 32 * rows));
-  if (hipGetLastError() != hipSuccess) return SP_EHIP;
-  return SP_OK;
+  uint8_t* sums_dst = m.encode_dev ? scratch + lay.sums_off : hres(c);
+  if (m.tree == MSM_TREE_NONE) {
+    if (idx_row_stride) {  // per-row index lists exist on the lookup+tree path only: longer rows go out one at a time, each with its own list
+      for (size_t r = 0; r < rows; r++)  // (an inner-product round of more than 2^19 lookups that is not fusable: n0 = 32768, or 16384 at narrow windows)
+        SPCHK(msm_launch(c, g, dZ + r * z_stride, z_stride, 1, cols, g_off, didx + r * idx_row_stride, dblinds ? dblinds + r : nullptr, h_idx,
+                         out_host ? out_host + 32 * r : nullptr, 0, points_out ? points_out + r : nullptr));
+      return SP_OK;
+    }
+    const unsigned* qcounts = msm_enqueue_sums(c, c->stream, m, g, dZ, z_stride, rows, cols, g_off, didx, dblinds, h_idx, scratch);
+    msm_enqueue_reduce(c, c->stream, m, rows, scratch, sums_dst, false, nullptr, qcounts);
+    return msm_finish_few(c, m, rows, sums_dst, false, out_host, points_out);
+  }
+  Pt10* part = (Pt10*)scratch;
+  const DoneSig sig = m.tree == MSM_TREE_FUSED ? sig_make(c, m.nblk * rows) : sig_none();
+  {
+    ProfScope ps(c, PF_MSM_WINDOWS, 32.0 * (double)(rows * cols) + 160.0 * (double)(rows * m.nblk));
+    if (m.tree == MSM_TREE1)
+      msm_tree1_enqueue(c->stream, g, dZ, z_stride, rows, cols, g_off, didx, idx_row_stride, dblinds, h_idx, sums_dst);
+    else if (m.tree == MSM_TREE_FUSED)
+      hipLaunchKernelGGL(k_msm_windows_tree_fused, dim3((unsigned)m.nblk, (unsigned)rows), dim3(256), 0, c->stream, dZ, z_stride, cols, (const Niels*)g->table, g_off,
+                         didx, idx_row_stride, dblinds, h_idx, part, c->done_counter + 4, (Pt*)sums_dst, g->geom, sig);
+    else
+      hipLaunchKernelGGL((k_msm_windows_tree<false>), dim3((unsigned)m.nblk, (unsigned)rows), dim3(256), 0, c->stream, dZ, z_stride, cols,
+                         (const Niels*)g->table, g_off, didx, idx_row_stride, dblinds, h_idx, (void*)part, g->geom);
+  }
+  if (m.tree == MSM_TREE_FUSED) SPCHK(sig_wait(c, sig));
+  if (m.tree == MSM_TREE_UNFUSED) {
+    ProfScope ps(c, PF_MSM_REDUCE, 160.0 * (double)(rows * m.nblk) + 128.0 * (double)rows);
+    hipLaunchKernelGGL((k_msm_reduce<true, false>), dim3((unsigned)rows), dim3(256), 0, c->stream, (const void*)part, m.nblk, sums_dst, (const unsigned*)nullptr);
+  }
+  return msm_finish_few(c, m, rows, sums_dst, m.tree == MSM_TREE_FUSED, out_host, points_out);
 }
 
 extern "C" {
+// the argument check of the table-based entry points: a rows x cols matrix at Z[z_off..] (rows z_stride apart) against the generators
+// [g_off, g_off + cols) and, with blinds, generator h_idx; `out` is the entry point's result pointer
+static bool commit_args_ok(const sp_ctx* c, const sp_gens* g, const sp_table* Z, const void* out, size_t g_off, size_t h_idx, bool blinds, size_t z_off,
+                           size_t z_stride, size_t rows, size_t cols) {
+  return c && g && Z && out && rows != 0 && cols != 0 && z_stride >= cols && g_off + cols <= g->n && (!blinds || h_idx < g->n) &&
+         z_off + (rows - 1) * z_stride + cols <= Z->cap;
+}
 // host blinds -> the device staging buffer (async on the main stream); *dbl = null when there are none
 static int32_t stage_blinds(sp_ctx* c, const uint64_t* blinds, size_t rows, const Fq** dbl) {
   *dbl = nullptr;
@@ -626,7 +662,7 @@ static void job_abandon(sp_job* j) {
 // ---- background commit (overlaps a throughput-bound MSM with the latency-bound rounds that follow on the main stream)
 int32_t sp_commit_rows_dev_begin(sp_ctx* c, const sp_gens* g, size_t g_off, const sp_table* Z, size_t z_off, size_t rows, size_t cols,
                                  sp_job** out) {
-  if (!c || !g || !Z || !out || rows == 0 || cols == 0 || g_off + cols > g->n || z_off + rows * cols > Z->cap) return SP_EINVAL;
+  if (!commit_args_ok(c, g, Z, out, g_off, 0, false, z_off, cols, rows, cols)) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
   MsmPlan m = msm_plan(c, g, rows, cols, false, c->bg_blocks > 0 ? (size_t)c->bg_blocks * 4 : 0);
   sp_job* j = nullptr;
@@ -637,8 +673,7 @@ int32_t sp_commit_rows_dev_begin(sp_ctx* c, const sp_gens* g, size_t g_off, cons
   // the job reads Z as produced by everything queued so far on the main stream
   (void)hipEventRecord(ready, c->stream);
   (void)hipStreamWaitEvent(c->stream_bg, ready, 0);
-  const unsigned* qcounts = msm_enqueue_sums(c, c->stream_bg, m, g, Z->d + z_off, cols, rows, cols, g_off, nullptr, nullptr, 0, j->scratch);
-  msm_enqueue_reduce(c, c->stream_bg, m, rows, j->scratch, j->scratch + lay.out_off, true, j->scratch + lay.sums_off, qcounts);
+  msm_enqueue_commit(c, c->stream_bg, m, lay, g, Z->d + z_off, cols, rows, cols, g_off, nullptr, nullptr, 0, j->scratch, j->scratch + lay.out_off);
   (void)hipEventRecord(j->done, c->stream_bg);
   (void)hipEventDestroy(ready);
   if (hipGetLastError() != hipSuccess) { job_abandon(j); return SP_EHIP; }
@@ -651,9 +686,7 @@ int32_t sp_commit_rows_dev_begin(sp_ctx* c, const sp_gens* g, size_t g_off, cons
 // commitment into the transcript (0.65 ms of Keccak at 2^20) while the witness commitment is being computed.
 int32_t sp_commit_rows_dev_start(sp_ctx* c, const sp_gens* g, size_t g_off, size_t h_idx, const sp_table* Z, size_t z_off, size_t rows, size_t cols,
                                  const uint64_t* blinds, sp_job** out) {
-  if (!c || !g || !Z || !out || rows <= SP_HOST_ENCODE_ROWS || cols == 0 || g_off + cols > g->n || (blinds && h_idx >= g->n) ||
-      z_off + rows * cols > Z->cap)
-    return SP_EINVAL;
+  if (!commit_args_ok(c, g, Z, out, g_off, h_idx, blinds != nullptr, z_off, cols, rows, cols) || rows <= SP_HOST_ENCODE_ROWS) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
   const Fq* dbl = nullptr;
   SPCHK(stage_blinds(c, blinds, rows, &dbl));
@@ -661,8 +694,7 @@ int32_t sp_commit_rows_dev_start(sp_ctx* c, const sp_gens* g, size_t g_off, size
   sp_job* j = nullptr;
   MsmScratch lay;
   SPCHK(job_open(c, c->stream, m, rows, &j, &lay));
-  const unsigned* qcounts = msm_enqueue_sums(c, c->stream, m, g, Z->d + z_off, cols, rows, cols, g_off, nullptr, dbl, h_idx, j->scratch);
-  msm_enqueue_reduce(c, c->stream, m, rows, j->scratch, j->scratch + lay.out_off, true, j->scratch + lay.sums_off, qcounts);
+  msm_enqueue_commit(c, c->stream, m, lay, g, Z->d + z_off, cols, rows, cols, g_off, nullptr, dbl, h_idx, j->scratch, j->scratch + lay.out_off);
   (void)hipEventRecord(j->done, c->stream);
   if (hipGetLastError() != hipSuccess) { job_abandon(j); return SP_EHIP; }
   *out = j;
@@ -675,9 +707,7 @@ int32_t sp_commit_rows_dev_start(sp_ctx* c, const sp_gens* g, size_t g_off, size
 // lookup form) take copy-then-commit.
 int32_t sp_commit_rows_upload_start(sp_ctx* c, const sp_gens* g, size_t g_off, size_t h_idx, sp_table* Z, size_t z_off, const uint64_t* src, size_t rows,
                                     size_t cols, const uint64_t* blinds, sp_job** out) {
-  if (!c || !g || !Z || !src || !out || rows <= SP_HOST_ENCODE_ROWS || cols == 0 || g_off + cols > g->n || (blinds && h_idx >= g->n) ||
-      z_off + rows * cols > Z->cap)
-    return SP_EINVAL;
+  if (!commit_args_ok(c, g, Z, out, g_off, h_idx, blinds != nullptr, z_off, cols, rows, cols) || !src || rows <= SP_HOST_ENCODE_ROWS) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
   const size_t nch = (size_t)c->opt.v[OPT_UPLOAD_CHUNKS];
   const bool chunked_on = c->opt.v[OPT_UPLOAD_OVERLAP] != 0;  // A/B switch
@@ -751,15 +781,10 @@ int32_t sp_job_wait(sp_job* j, uint8_t* out) {
 
 int32_t sp_commit_rows_dev(sp_ctx* c, const sp_gens* g, size_t g_off, size_t h_idx, const sp_table* Z, size_t z_off, size_t rows, size_t cols,
                            const uint64_t* blinds, uint8_t* out) {
-  if (!c || !g || !Z || !out || rows == 0 || cols == 0) return SP_EINVAL;
-  if (g_off + cols > g->n || (blinds && h_idx >= g->n) || z_off + rows * cols > Z->cap) return SP_EINVAL;
+  if (!commit_args_ok(c, g, Z, out, g_off, h_idx, blinds != nullptr, z_off, cols, rows, cols)) return SP_EINVAL;
   HIPCHK(hipSetDevice(c->dev));
   const Fq* dbl = nullptr;
-  if (blinds) {
-    SPCHK(ensure_dstage(c, 32 * rows));
-    SPCHK(stage_in(c, 0, blinds, 32 * rows));
-    dbl = (const Fq*)c->dstage;
-  }
+  SPCHK(stage_blinds(c, blinds, rows, &dbl));
   return msm_launch(c, g, Z->d + z_off, cols, rows, cols, g_off, nullptr, dbl, h_idx, out);
 }
 // A commitment restricted to a run of generators, left as points: sum_j Z[r * z_stride + j] * G[g_off + j], j < cols, for rows <= 8, no
@@ -768,9 +793,7 @@ int32_t sp_commit_rows_dev(sp_ctx* c, const sp_gens* g, size_t g_off, size_t h_i
 // with fewer rows than shards (Cx of DotProductProofLog, a small instance's witness).
 int32_t sp_commit_rows_partial(sp_ctx* c, const sp_gens* g, size_t g_off, const sp_table* Z, size_t z_off, size_t z_stride, size_t rows, size_t cols,
                                sp_host_point* out) {
-  if (!c || !g || !Z || !out || rows == 0 || rows > SP_HOST_ENCODE_ROWS || cols == 0 || z_stride < cols || g_off + cols > g->n ||
-      z_off + (rows - 1) * z_stride + cols > Z->cap)
-    return SP_EINVAL;
+  if (!commit_args_ok(c, g, Z, out, g_off, 0, false, z_off, z_stride, rows, cols) || rows > SP_HOST_ENCODE_ROWS) return SP_EINVAL;
   static_assert(sizeof(sp_host_point) == sizeof(Pt), "sp_host_point carries an extended point");
   HIPCHK(hipSetDevice(c->dev));
   return msm_launch(c, g, Z->d + z_off, z_stride, rows, cols, g_off, nullptr, nullptr, 0, nullptr, 0, (Pt*)out);
@@ -791,34 +814,44 @@ int32_t sp_commit_rows(sp_ctx* c, const sp_gens* g, size_t g_off, size_t h_idx, 
   }
   return msm_launch(c, g, (const Fq*)c->scratch2, cols, rows, cols, g_off, nullptr, dbl, h_idx, out);
 }
-int32_t msm_small_enqueue(sp_ctx* c, hipStream_t st, const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows,
-                          uint8_t* sums_out) {
-  if (!c || !g || !idx || !S || !sums_out || rows == 0 || rows > SP_HOST_ENCODE_ROWS || cols == 0 || cols * (size_t)g->geom.nwin > 256) return SP_EINVAL;
+static bool idx_in_set(const sp_gens* g, const uint32_t* idx, size_t cols) {
   for (size_t j = 0; j < cols; j++)
-    if (idx[j] >= g->n) return SP_EINVAL;
-  size_t sb = 32 * rows * cols, ib = (4 * cols + 31) & ~(size_t)31;
-  if (sb + ib > HMAP_GEN) return SP_EINVAL;
-  const Fq* ds = (const Fq*)stage_small(c, 0, S, sb);
-  const uint32_t* di = (const uint32_t*)stage_small(c, sb, idx, 4 * cols);
-  ProfScope ps(c, PF_MSM_WINDOWS, 32.0 * (double)(rows * cols) + 128.0 * (double)rows, st);
-  hipLaunchKernelGGL((k_msm_windows_tree<true>), dim3(1, (unsigned)rows), dim3(256), 0, st, ds, cols, cols, (const Niels*)g->table, (size_t)0, di, (size_t)0,
-                     (const Fq*)nullptr, (size_t)0, (void*)sums_out, g->geom);
-  return SP_OK;
+    if (idx[j] >= g->n) return false;
+  return true;
 }
-int32_t sp_msm_indexed(sp_ctx* c, const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, uint8_t* out) {
-  if (!c || !g || !idx || !S || !out || rows == 0 || cols == 0) return SP_EINVAL;
-  for (size_t j = 0; j < cols; j++)
-    if (idx[j] >= g->n) return SP_EINVAL;
-  HIPCHK(hipSetDevice(c->dev));
+// rows x cols scalars and one index list, staged where the kernel reads them: *ds, *di. page_only: refused when they do not fit the page
+static int32_t stage_indexed(sp_ctx* c, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, bool page_only, const Fq** ds, const uint32_t** di) {
   size_t sb = 32 * rows * cols, ib = (4 * cols + 31) & ~(size_t)31;
   if (sb + ib <= HMAP_GEN) {  // Sigma-protocol sized: the kernel reads scalars and indices straight from the host-mapped page
-    const Fq* ds = (const Fq*)stage_small(c, 0, S, sb);
-    const uint32_t* di = (const uint32_t*)stage_small(c, sb, idx, 4 * cols);
-    return msm_launch(c, g, ds, cols, rows, cols, 0, di, nullptr, 0, out);
+    *ds = (const Fq*)stage_small(c, 0, S, sb);
+    *di = (const uint32_t*)stage_small(c, sb, idx, 4 * cols);
+    return SP_OK;
   }
+  if (page_only) return SP_EINVAL;
   SPCHK(ensure_dstage(c, sb + ib));
   SPCHK(stage_in(c, 0, S, sb));
   SPCHK(stage_in(c, sb, idx, 4 * cols));
-  return msm_launch(c, g, (const Fq*)c->dstage, cols, rows, cols, 0, (const uint32_t*)((uint8_t*)c->dstage + sb), nullptr, 0, out);
+  *ds = (const Fq*)c->dstage;
+  *di = (const uint32_t*)((uint8_t*)c->dstage + sb);
+  return SP_OK;
+}
+int32_t msm_small_enqueue(sp_ctx* c, hipStream_t st, const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows,
+                          uint8_t* sums_out) {
+  if (!c || !g || !idx || !S || !sums_out || rows == 0 || rows > SP_HOST_ENCODE_ROWS || cols == 0 || cols * (size_t)g->geom.nwin > 256) return SP_EINVAL;
+  if (!idx_in_set(g, idx, cols)) return SP_EINVAL;
+  const Fq* ds = nullptr;
+  const uint32_t* di = nullptr;
+  SPCHK(stage_indexed(c, idx, cols, S, rows, true, &ds, &di));
+  ProfScope ps(c, PF_MSM_WINDOWS, 32.0 * (double)(rows * cols) + 128.0 * (double)rows, st);
+  msm_tree1_enqueue(st, g, ds, cols, rows, cols, 0, di, 0, nullptr, 0, sums_out);
+  return SP_OK;
+}
+int32_t sp_msm_indexed(sp_ctx* c, const sp_gens* g, const uint32_t* idx, size_t cols, const uint64_t* S, size_t rows, uint8_t* out) {
+  if (!c || !g || !idx || !S || !out || rows == 0 || cols == 0 || !idx_in_set(g, idx, cols)) return SP_EINVAL;
+  HIPCHK(hipSetDevice(c->dev));
+  const Fq* ds = nullptr;
+  const uint32_t* di = nullptr;
+  SPCHK(stage_indexed(c, idx, cols, S, rows, false, &ds, &di));
+  return msm_launch(c, g, ds, cols, rows, cols, 0, di, nullptr, 0, out);
 }
 }  // extern "C"

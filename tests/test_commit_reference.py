@@ -29,6 +29,32 @@ def test_every_threshold_is_still_in_the_source():
     assert CR.constants() == K
 
 
+def _csrc(fn):
+    import os
+    return open(os.path.join(CR._CSRC, fn)).read()
+
+
+def test_every_rule_and_every_launch_stands_once():
+    """one place per decision: every threshold pattern and every restated line of commit.hip and msm_rows.hip occurs exactly once in its file,
+    and so do the launches of the latency path's kernels; msm_plan is called from msm_launch and the three job entry points, nowhere else"""
+    import re
+    for fn, pat, _ in CR._PATTERNS:
+        if fn in ("commit.hip", "msm_rows.hip"):
+            assert len(re.findall(pat, _csrc(fn))) == 1, (fn, pat)
+    for fn in ("commit.hip", "msm_rows.hip"):
+        for text in CR.SOURCE_TEXT[fn]:
+            assert _csrc(fn).count(text) == 1, (fn, text)
+    src = _csrc("commit.hip")
+    for launch in ("k_msm_windows_tree_fused,", "(k_msm_windows_tree<true>),", "(k_msm_windows_tree<false>),", "(k_msm_reduce<true, false>),", "k_pt_encode, dim3(1)"):
+        assert src.count(launch) == 1, launch
+    code = re.sub(r"//.*", "", src)      # (a comment may speak of msm_plan(...))
+    callers = []
+    for m in re.finditer(r"(?<!static MsmPlan )\bmsm_plan\(", code):
+        heads = re.findall(r"^int32_t (\w+)\(", code[:m.start()], re.M)
+        callers.append(heads[-1])
+    assert callers == ["msm_launch", "sp_commit_rows_dev_begin", "sp_commit_rows_dev_start", "sp_commit_rows_upload_start"], callers
+
+
 # ------------------------------------------------------------------ reach
 # boundary -> predicate over a plan: True | False are its two sides, None: the plan does not come by it
 def _in(form):

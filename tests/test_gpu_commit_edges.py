@@ -498,6 +498,120 @@ def test_indexed_commitments_on_both_sides_of_the_staging_boundary(ctx, orc, gse
     _eq("positions", got, want, "indexed %dx%d staged in the %s" % (rows, cols, "page" if CR.indexed_staging(rows, cols) else "buffer"))
 
 
+# ------------------------------------------------------------------ what every plan's call leaves behind
+# the smallest shape of every plan (all from the lists above), sp_commit_rows_partial at 2 rows and sp_msm_indexed on both sides of its staging boundary
+RECORD_CASES = [K("tree", "n32", 1, 8, 0, "host"), K("tree", "n32", 1, 9, 0, "sync"), K("tree", "n32", 1, 9, 0, "sync", device_encode=1),
+                K("reduce", "w5", 9, 40, 0), K("reduce", "w5", 9, 41, 0), K("line", "w5", 8, 1286, 0, "sync"),
+                K("queue", "w5", 256, 41, 1), K("queue", "w5", 256, 41, 0, "begin"), K("queue", "w5", 256, 41, 1, "start"), K("queue", "w5", 256, 41, 1, "start_shared"),
+                K("flat", "w5", 1024, 12, 1, "upload"), K("queue", "w5", 1024, 12, 1, "upload", upload_chunks=1)]
+RECORD_PARTIAL = (2, 9, 11)      # rows, cols, z_stride
+RECORD_INDEXED = [(1, 625), (1, 626)]
+# call -> (round trips by sp_ctx_trips: of a synchronous call its own; of a job those of its start and of its sp_job_wait (start_shared: begin, start,
+# wait of the foreground job, wait of the background job), {profile family: (records, algorithmic bytes)} of every family the call left a record in).
+# MEASURED, not derived from the code under test: this test printed the table on the library as it stood before the row commitments were given one
+# plan and one launch path (256 compute units), and it was written down here as literals. The calls must go on leaving exactly this behind.
+COMMIT_RECORDS = {
+    'n32-1x8-host': ((1,), {'msm_windows_fixed': (1, 416.0)}),
+    'n32-1x9-sync': ((1,), {'msm_windows_fixed': (1, 608.0)}),
+    'n32-1x9-sync-device_encode1': ((1,), {'msm_windows_fixed': (1, 608.0), 'msm_reduce_compress': (2, 608.0)}),
+    'w5-9x40-sync': ((1,), {'msm_windows_fixed': (1, 2361600.0), 'msm_reduce_compress': (1, 2350368.0)}),
+    'w5-9x41-sync': ((1,), {'msm_windows_fixed': (1, 2420640.0), 'msm_reduce_pass': (1, 2413152.0), 'msm_reduce_compress': (1, 4608.0)}),
+    'w5-8x1286-sync': ((1,), {'msm_rows_fixed': (1, 329472.0), 'msm_reduce_compress': (1, 1317120.0)}),
+    'w5-256x41+b-sync': ((1,), {'msm_rows_fixed': (1, 344064.0), 'msm_reduce_compress': (2, 27312128.0)}),
+    'w5-256x41-begin': ((0, 0), {'msm_rows_fixed': (1, 344064.0), 'msm_reduce_compress': (2, 18923520.0)}),
+    'w5-256x41+b-start': ((0, 0), {'msm_rows_fixed': (1, 344064.0), 'msm_reduce_compress': (2, 27312128.0)}),
+    'w5-256x41+b-start_shared': ((0, 0, 0, 0), {'msm_rows_fixed': (2, 688128.0), 'msm_reduce_compress': (4, 37847040.0)}),
+    'w5-1024x12+b-upload': ((0, 0), {'msm_rows_fixed': (4, 425984.0), 'msm_reduce_compress': (2, 21823488.0)}),
+    'w5-1024x12+b-upload-upload_chunks1': ((0, 0), {'msm_rows_fixed': (1, 425984.0), 'msm_reduce_compress': (2, 33751040.0)}),
+    'partial-2x9': ((1,), {'msm_windows_fixed': (1, 1216.0)}),
+    'indexed-1x625': ((1,), {'msm_windows_fixed': (1, 40000.0)}),
+    'indexed-1x626': ((1,), {'msm_windows_fixed': (1, 40032.0)}),
+}
+
+
+def test_records_and_round_trips_of_every_plan(ctx, orc, gsets):
+    """one call of every plan of msm_launch and of the job entry points, sp_commit_rows_partial and sp_msm_indexed: each result against the oracle,
+    the round trips each call makes and the profile records it leaves (how many per family, and their algorithmic bytes) are those of COMMIT_RECORDS"""
+    from spartan_amd import capi
+    from tests.ipa_reference import _msm
+    L = capi.lib
+    got = {}
+    trips = []
+    tick = lambda: trips.append(L.sp_ctx_trips(ctx.h))
+
+    def begin():
+        ctx.prof_reset()
+        del trips[:]
+        tick()
+
+    def end(key):
+        rec = {n: (v["launches"], v["alg_bytes"]) for n, v in ctx.prof_read().items() if v["launches"] or v["alg_bytes"]}
+        got[key] = (tuple(b - a for a, b in zip(trips, trips[1:])), rec)
+    for case in RECORD_CASES:
+        g, P = gsets(case.set)
+        rows, cols, what = case.rows, case.cols, case.name
+        h_idx = SETS[case.set][0] - 1
+        want_b, want_n = expected_of(orc, P, case)
+        want = want_b if case.blind else want_n
+        Z, bl = flat_matrix(case)
+        Zm, blm = mont_bulk(Z), (mont_bulk(bl) if case.blind else None)
+        out, bg, fg = (ctypes.c_uint8 * (32 * rows))(), vp(), vp()
+        with _Options(ctx, case.opts):
+            t = capi.Table.alloc(ctx, rows * cols) if case.role == "upload" else capi.Table.upload(ctx, Zm, rows * cols)
+            _ok(L.sp_ctx_sync(ctx.h), "sp_ctx_sync")
+            begin()
+            if case.role == "host":
+                _ok(L.sp_commit_rows(ctx.h, g.h, sz(0), sz(h_idx), Zm, sz(rows), sz(cols), blm, out), "sp_commit_rows " + what)
+            elif case.role == "sync":
+                _ok(L.sp_commit_rows_dev(ctx.h, g.h, sz(0), sz(h_idx), t.h, sz(0), sz(rows), sz(cols), blm, out), "sp_commit_rows_dev " + what)
+            elif case.role == "upload":
+                _ok(L.sp_commit_rows_upload_start(ctx.h, g.h, sz(0), sz(h_idx), t.h, sz(0), Zm, sz(rows), sz(cols), blm, ctypes.byref(fg)), "sp_commit_rows_upload_start " + what)
+            if case.role in ("host", "sync", "upload"):
+                tick()
+            if case.role in ("begin", "start_shared"):
+                _ok(L.sp_commit_rows_dev_begin(ctx.h, g.h, sz(0), t.h, sz(0), sz(rows), sz(cols), ctypes.byref(bg)), "sp_commit_rows_dev_begin " + what)
+                tick()
+            if case.role in ("start", "start_shared"):
+                _ok(L.sp_commit_rows_dev_start(ctx.h, g.h, sz(0), sz(h_idx), t.h, sz(0), sz(rows), sz(cols), blm, ctypes.byref(fg)), "sp_commit_rows_dev_start " + what)
+                tick()
+            if case.role in ("host", "sync"):
+                _eq(case.sec, bytes(out), want, what)
+            if fg:
+                res = wait(fg, rows, what)
+                tick()
+                _eq(case.sec, res, want, what)
+            if bg:
+                res = wait(bg, rows, what)
+                tick()
+                _eq(case.sec, res, want_n, what + " (dev_begin)")
+            end(what)
+            t.free()
+    g, P = gsets("w5")
+    vals = value_pool("w5")
+    rows, cols, stride = RECORD_PARTIAL
+    M = [vals[(7 * i + 2) % len(vals)] for i in range(3 + rows * stride)]
+    t = capi.Table.upload(ctx, mont_bulk(M), len(M))
+    pts, out = (ctypes.c_uint64 * (16 * rows))(), (ctypes.c_uint8 * (32 * rows))()
+    _ok(L.sp_ctx_sync(ctx.h), "sp_ctx_sync")
+    begin()
+    _ok(L.sp_commit_rows_partial(ctx.h, g.h, sz(1), t.h, sz(3), sz(stride), sz(rows), sz(cols), pts), "sp_commit_rows_partial")
+    tick()
+    end("partial-%dx%d" % (rows, cols))
+    _ok(L.sp_host_points_sum_encode(pts, sz(1), sz(rows), out), "sp_host_points_sum_encode")
+    _eq("positions", bytes(out), b"".join(_msm(orc, M[3 + r * stride:3 + r * stride + cols], P[1:1 + cols]) for r in range(rows)), "partial %dx%d" % (rows, cols))
+    t.free()
+    for rows, cols in RECORD_INDEXED:
+        idx = [(5 * j + 1) % SETS["w5"][0] for j in range(cols)]
+        S = [vals[(11 * i + 5) % len(vals)] for i in range(rows * cols)]
+        Sm = mont_bulk(S)
+        begin()
+        res = g.msm_indexed(idx, Sm, rows)
+        tick()
+        end("indexed-%dx%d" % (rows, cols))
+        _eq("positions", res, b"".join(_msm(orc, S[r * cols:(r + 1) * cols], [P[j] for j in idx]) for r in range(rows)), "indexed %dx%d" % (rows, cols))
+    assert got == COMMIT_RECORDS, "".join("\n    %r: %r," % kv for kv in got.items() if COMMIT_RECORDS.get(kv[0]) != kv[1])
+
+
 # ------------------------------------------------------------------ 11. refusals
 def test_refusals_change_nothing(ctx, orc, gsets):
     """every argument check of the seven entry points returns SP_EINVAL before anything is launched; a correct call on the same context follows
